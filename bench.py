@@ -8,7 +8,13 @@ cull_maln_from_fsdb + consensus_assembly_string, inputs resident in HBM.
 Headline (`value`): BASELINE.json configs[1] -- 1 M synthetic 100 bp reads (1 % subs, 0.1 % indels, both strands)
 against the 16 619 bp mt311 reference, circular, flat matrix.  Pass-1 coordinates are the generator's true positions
 (pass 1 is reported separately under "pass1"); every iteration re-aligns every read in its +-50 window exactly as the
-reference does.  At N = 1 the same JSON line also carries
+reference does.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) makes the workload, warms up, times EXACTLY K steps as one block,
+writes what the last step computed if --dump-outputs DIR is given, and prints the line: the headline keys, `ms_per_step`,
+the workload and the library it ran.  Its timed steps are those of a --full run.  Everything else is measured with --full
+(then 5 timed blocks of K steps by default, the line reporting the median block): the per-kernel stage table and roofline,
+the certificate, the measured device peaks, the CPU baselines, bench_extras.json, and at N = 1 the line also carries
   "configs2"  configs[2]: 1 M aDNA-damaged reads, matrices/ancient.submat.txt, iterated from mt311 itself to convergence
   "configs4"  configs[4] at its size on one GPU: 5 M reads of 150 bp against a 100 kb linear reference, ancient matrix
               ("configs4_share": 625 k of them, one GPU's share of the 8-GPU job)
@@ -24,9 +30,9 @@ N > 1 (one process per GPU; `python bench.py --gpus N` starts the N ranks itself
 launcher did, and fails loudly when the box has fewer GPUs): reads are sharded in contiguous fsdb blocks; per iteration the
 int32 column tallies are all-reduced (sum) and the gap lengths (max), insert events are all-gathered -- inside libmia_hip
 (mia_hip_iterate over its RCCL communicator; the line carries the rank count RCCL itself reports).  The default job at
-N > 1 is north_star's: STRONG scaling of configs[3] (10 M paired reads in total, split over the ranks) as `value`, and the
-weak figure (configs[1], 1 M reads per GPU) under "weak".  --scaling weak: --reads is PER GPU.  --scaling strong: --reads
-is the whole job, split over the ranks.
+N > 1 is north_star's: STRONG scaling of configs[3] (10 M paired reads in total, split over the ranks) as `value`, and with
+--full the weak figure (configs[1], 1 M reads per GPU) under "weak".  --scaling weak: --reads is PER GPU.  --scaling
+strong: --reads is the whole job, split over the ranks.
 """
 import argparse
 import hashlib
@@ -186,6 +192,28 @@ def certificate(hip, cons, fixed_point=None):
     if fixed_point is not None:
         c["consensus_is_fixed_point"] = bool(fixed_point)
     return c
+
+
+DUMP_MAX_BYTES = 64_000_000 - 4096                  # (room for the .npy headers)
+
+
+def dump_outputs(out_dir, hip, cons):
+    """--dump-outputs: what a caller of the timed step receives after the last one, as float64 .npy files (exact for int32) --
+    consensus.npy, the consensus string mia_hip_iterate returned (ASCII codes), and score.npy / as.npy / ae.npy, every read's
+    alignment (mia_hip_get_alignments).  Past 64 MB in all, the per-read arrays are a fixed sample of the reads
+    (seed 0), their indices in read_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    sc, a, e = hip.alignments()
+    arrays = {"consensus": np.frombuffer(cons.encode(), np.uint8)}
+    room = (DUMP_MAX_BYTES - 8 * len(arrays["consensus"])) // (8 * 3)
+    if len(sc) > room:
+        room = (DUMP_MAX_BYTES - 8 * len(arrays["consensus"])) // (8 * 4)
+        idx = np.sort(np.random.default_rng(0).choice(len(sc), room, replace=False))
+        sc, a, e = sc[idx], a[idx], e[idx]
+        arrays["read_index"] = idx
+    arrays.update({"score": sc, "as": a, "ae": e})
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(x, dtype=np.float64))
 
 
 # ---- one iteration ------------------------------------------------------------------------------------------------
@@ -709,18 +737,19 @@ def _r(x, nd=4):
 def headline(out, extras_path):
     """The driver's line: the contract's keys, the roofline of the dominant KERNEL (a name of the rocprofv3 kernel trace),
     the CPU baseline, and the product-speed figures (first iteration, to convergence); the rest is in `extras`."""
-    ro = out["roofline"]
     h = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "blocks", "higher_is_better", "scaling", "vs_baseline",
                              "dtype", "data", "config") if k in out}
-    rl = {k: ro.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms", "launches", "reads_per_launch",
-                                 "primary_bound", "peak_measured_copy", "frac_of_measured_copy")}
-    rl["bytes_per_read"] = out["config"].get("bytes_per_read")
-    if ro.get("valu"):
-        rl["valu"] = {k: ro["valu"].get(k) for k in ("achieved", "peak", "unit", "frac")}
-    if ro.get("dp_phase"):
-        rl["dp_phase"] = {k: ro["dp_phase"].get(k) for k in ("wall_ms", "frac", "gcups")}
-    rl["pmc"] = ro.get("pmc")
-    h["roofline"] = rl
+    if "roofline" in out:                           # (--full)
+        ro = out["roofline"]
+        rl = {k: ro.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms", "launches", "reads_per_launch",
+                                     "primary_bound", "peak_measured_copy", "frac_of_measured_copy")}
+        rl["bytes_per_read"] = out["config"].get("bytes_per_read")
+        if ro.get("valu"):
+            rl["valu"] = {k: ro["valu"].get(k) for k in ("achieved", "peak", "unit", "frac")}
+        if ro.get("dp_phase"):
+            rl["dp_phase"] = {k: ro["dp_phase"].get(k) for k in ("wall_ms", "frac", "gcups")}
+        rl["pmc"] = ro.get("pmc")
+        h["roofline"] = rl
     if "cpu_baseline" in out:
         cb = dict(out["cpu_baseline"])
         cb["sample"] = str(cb.get("sample", ""))[:200]
@@ -750,7 +779,8 @@ def headline(out, extras_path):
         h["value_to_convergence"] = conv.get("configs2", {}).get("value_to_convergence")
     if "weak" in out:
         h["weak"] = {k: out["weak"].get(k) for k in ("value", "ms_per_step", "reads_per_gpu", "total_reads")}
-    h["extras"] = extras_path
+    if extras_path:
+        h["extras"] = extras_path
     return _r(h)
 
 
@@ -812,7 +842,8 @@ def timed_job(a, env, cfg, reads, scaling, peaks=None):
         st = hip.stage_stats()
         dominant = max((k for k in STAGES if k in ROCPROF_NAME), key=lambda k: st[k][0])
         # HIP events cost the stream a few microseconds each: over the timed region only the dominant kernel carries them;
-        # the other stages are timed in as many instrumented steps after it
+        # the other stages are timed in as many instrumented steps after it (--full).  A plain run keeps these events as well:
+        # its timed steps stay the ones the headline has always timed (with no stage evented, the step measured no faster)
         hip.set_timed_stages([dominant])
     # one block of a.steps iterations is 16 ms of GPU time -- a.blocks such blocks, each timed EXACTLY as the
     # contract says (barrier + synchronize on both sides, the longest rank counts); `value` is the MEDIAN block, min / max ride along
@@ -843,14 +874,16 @@ def timed_job(a, env, cfg, reads, scaling, peaks=None):
     if dominant and len(block_dt) > 1:             # the dominant kernel's events: the average over all blocks, as launches of ONE block
         dom_ms, dom_launches = dom_ms / len(block_dt), dom_launches // len(block_dt)
     dt = sorted(block_dt)[len(block_dt) // 2]
-    cert = certificate(hip, cur, fixed_point=(cur == step_in) if a.steps > 0 else None)      # (of this rank's reads; the consensus is every rank's)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, hip, cur)      # (of rank 0's reads; the consensus is every rank's)
+    cert = certificate(hip, cur, fixed_point=(cur == step_in) if a.steps > 0 else None) if a.full else None   # (of this rank's reads; the consensus is every rank's)
     if world > 1:
         tot = torch.tensor([n], dtype=torch.int64, device="cuda")
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         total_reads = int(tot.item())
     else:
         total_reads = n
-    if dominant:                                    # the stage table: the same steps again, every stage timed
+    if dominant and a.full:                         # the stage table: the same steps again, every stage timed
         hip.set_timed_stages(None)
         pipe.reset_stats()
         cur = run_steps(pipe, cur, a.steps)
@@ -879,7 +912,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps iterations each; the line reports the median block (min / max beside it)")
+    ap.add_argument("--blocks", type=int, default=None, help="timed blocks of --steps iterations each, default 1 (5 with --full); the line reports the median block (min / max beside it)")
     ap.add_argument("--reads", type=int, default=None, help="reads per GPU (weak) or in the whole job (strong); default 1 M on one GPU, 10 M (strong) on several")
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None, help="default: weak on one GPU, strong (north_star's target) on several")
     ap.add_argument("--config", type=int, default=None, choices=(1, 2, 3, 4), help="BASELINE.json configs[k] for the timed steps; default 1 on one GPU, 3 on several")
@@ -888,7 +921,17 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="the headline line only (no configs2/configs3/configs4/pass1/myers sections, no weak figure)")
     ap.add_argument("--pmc-run", default=None, help="reduced run under rocprofv3 --pmc: only the timed steps of this config, plus k_peak_copy for the FETCH_SIZE calibration")
     ap.add_argument("--allow-alt-build", action="store_true", help="run although a non-release MIA_HIP_* switch is set (the alt build is then timed, and the line says so)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: stage table, roofline, certificate, device peaks, "
+                                                        "CPU baselines, the extra sections (see --no-extras), bench_extras.json; implied by --pmc-run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64, "
+                                                                         "at most 64 MB; see dump_outputs)")
     a = ap.parse_args()
+    if a.pmc_run:
+        a.full = True
+    if not a.full:
+        a.no_cpu_baseline = a.no_extras = True
+    if a.blocks is None:
+        a.blocks = 5 if a.full else 1
 
     # a leftover MIA_HIP_* switch silently selects libmia_hip_alt.so (debug branches, other launch paths): refuse, or say so
     sys.path.insert(0, ROOT)
@@ -941,7 +984,7 @@ def main():
     scaling = a.scaling if a.scaling else ("weak" if world == 1 else "strong")
     reads = a.reads if a.reads else (1_000_000 if world == 1 else 10_000_000)
     peaks = None
-    if rank == 0 and world == 1 and not a.pmc_run:
+    if a.full and rank == 0 and world == 1 and not a.pmc_run:
         hp = mia_amd.MiaHip(local)
         gbs, ginst = hp.measure_peaks(1 << 30)
         issue, mhz = hp.measure_issue()
@@ -962,10 +1005,6 @@ def main():
         live2["hip"].close()
 
     if rank == 0:
-        tag = f"cfg{cfg}"
-        pmc, stale = load_pmc(tag)
-        stages, counts = pipe.stages(a.steps, peaks, pmc, stale)
-        use_timed_region(stages, live["dominant"], live["dom_ms"], live["dom_launches"], a.steps)
         out = {
             "metric": "reads aligned/sec per iteration (16.5kb mito ref, 100bp reads)",
             "value": job["value"], "unit": "reads/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -973,13 +1012,17 @@ def main():
             "vs_baseline": None, "dtype": "int32", "data": "synthetic",
             "config": {"workload": job["workload"], "reads_per_gpu": n, "total_reads": job["total_reads"], "consensus_len": job["consensus_len"],
                        "bytes_per_read": job["bytes_per_read"]},
-            "roofline": roofline(stages, peaks, tag, stale),
-            "read_fate": counts,
-            "certificate": dict(job["certificate"], workload="make_workload(%d, %d, seed=%d)" % (cfg, n, 1 + rank)),
-            "step_traffic": step_traffic(pmc, stale, n, job["bytes_per_read"]),
             "library": {"path": os.path.relpath(hip.lib_path, ROOT), "alt_build": hip.is_alt_build, "switches": mia_amd.alt_switches_set(),
                         "source_hash": source_hash()},
         }
+        if a.full:
+            tag = f"cfg{cfg}"
+            pmc, stale = load_pmc(tag)
+            stages, counts = pipe.stages(a.steps, peaks, pmc, stale)
+            use_timed_region(stages, live["dominant"], live["dom_ms"], live["dom_launches"], a.steps)
+            out.update({"roofline": roofline(stages, peaks, tag, stale), "read_fate": counts,
+                        "certificate": dict(job["certificate"], workload="make_workload(%d, %d, seed=%d)" % (cfg, n, 1 + rank)),
+                        "step_traffic": step_traffic(pmc, stale, n, job["bytes_per_read"])})
         for k in ("collectives", "communicator", "collectives_note"):
             if k in job:
                 out[k] = job[k]
@@ -1069,7 +1112,7 @@ def main():
             # held a context with a million reads on the same GPU: the child's first mia_hip_iterate then took 30-60 ms -- two processes
             # taking turns on one device -- against 2.6-2.7 ms when it has the GPU to itself, which is how a user runs it.)
             out["cli"] = section_cli(w)
-        extras_path = write_extras(out)
+        extras_path = write_extras(out) if a.full else None
         hl = headline(out, extras_path)
         line = json.dumps(hl, separators=(",", ":"))
         # never die for a long line after everything was measured -- drop optional keys (all of them are in the extras file)

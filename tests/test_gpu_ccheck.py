@@ -82,12 +82,17 @@ def test_ccheck_picks_newest_iteration(workdir, hashes):
 
 
 def test_ccheck_against_reference_binary_when_present(workdir):
-    """where the real ccheck was built (oracle/_ref, this container and the snapshot that travels to the GPU box):
-    a run that is not among the goldens"""
-    ref = os.path.join(ROOT, "oracle", "_ref", "ccheck")
-    if not os.path.exists(ref):
-        pytest.skip("oracle/_ref/ccheck not built")
-    args = ["-f", "-a", "-n", "3", "-s", "500-15000", "-vv", "cc_anc.maln"]
-    want = subprocess.run([ref] + args, cwd=workdir, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    """a run that is not among runs.json: against the real ccheck where it was built (oracle/_ref), and always against
+    the exit code and the digests of both streams that binary printed for it (ref_binary.json)"""
+    pinned = json.load(open(os.path.join(GC, "ref_binary.json")))
+    args = pinned["args"]
     got = subprocess.run([CC] + args, cwd=workdir, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert (got.returncode, got.stdout, got.stderr) == (want.returncode, want.stdout, want.stderr)
+    ref = os.path.join(ROOT, "oracle", "_ref", "ccheck")
+    if os.path.exists(ref):
+        want = subprocess.run([ref] + args, cwd=workdir, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert (got.returncode, got.stdout, got.stderr) == (want.returncode, want.stdout, want.stderr)
+
+    def digest(b):
+        return {"bytes": len(b), "sha256": hashlib.sha256(b).hexdigest()}
+
+    assert (got.returncode, digest(got.stdout), digest(got.stderr)) == (pinned["rc"], pinned["stdout"], pinned["stderr"]), got.stderr[-400:]

@@ -4,7 +4,7 @@ PART=${PART:-all}
 if [ $PART != pmc ]; then
 for c in 1 2 3 4; do
   reads=1000000; [ $c = 3 ] && reads=10000000; [ $c = 4 ] && reads=5000000
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_cfg$c -o p -- python3 $R/bench.py --config $c --reads $reads --no-extras --no-cpu-baseline --steps 10 --warmup 3 > $O/ks_cfg$c.json 2> $O/ks_cfg$c.err || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_cfg$c -o p -- python3 $R/bench.py --full --config $c --reads $reads --no-extras --no-cpu-baseline --steps 10 --warmup 3 > $O/ks_cfg$c.json 2> $O/ks_cfg$c.err || exit 1
   python3 $R/tools/timeline.py $O/ks_cfg$c > $O/cfg${c}_timeline.txt
   rm -f $O/ks_cfg$c/*kernel_trace.csv $O/ks_cfg$c/*agent_info.csv
 done

@@ -3,7 +3,7 @@ of bench.py's step with synchronised timers (MIA_BENCH_FORCE_DIST=1: the RCCL pa
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["MIA_BENCH_FORCE_DIST"]="1"
-sys.argv=["bench.py","--no-cpu-baseline","--steps","10","--warmup","3"]
+sys.argv=["bench.py","--full","--no-cpu-baseline","--steps","10","--warmup","3"]
 sys.path.insert(0, ROOT)
 import torch, torch.distributed as dist
 import mia_amd

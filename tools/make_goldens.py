@@ -659,6 +659,12 @@ def ccheck_cases(mt311_path):
         with open(os.path.join(out_dir, f"{key}.rc"), "w") as f:
             f.write(f"{r.returncode}\n")
         print(f"ccheck {key}: rc {r.returncode}, {len(r.stdout)} B out, {len(r.stderr)} B err")
+    # test_ccheck_against_reference_binary_when_present: a run outside runs.json, pinned by exit code and digests
+    args = ["-f", "-a", "-n", "3", "-s", "500-15000", "-vv", "cc_anc.maln"]
+    r = subprocess.run([os.path.join(RB, "ccheck")] + args, cwd=tmp, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    with open(os.path.join(out_dir, "ref_binary.json"), "w") as f:
+        json.dump({"args": args, "rc": r.returncode, "stdout": {"bytes": len(r.stdout), "sha256": hashlib.sha256(r.stdout).hexdigest()},
+                   "stderr": {"bytes": len(r.stderr), "sha256": hashlib.sha256(r.stderr).hexdigest()}}, f, indent=1)
     with open(os.path.join(out_dir, "runs.json"), "w") as f:
         json.dump(runs, f, indent=1)
     with open(os.path.join(out_dir, "hashes.json"), "w") as f:

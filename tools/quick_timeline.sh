@@ -5,7 +5,7 @@ c=$1; reads=$2; tag=$3
 if [ "$4" = first ]; then
   timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/$tag -o p -- python3 $R/tools/first_iter_probe.py $c $reads > $O/$tag.txt 2>&1
 else
-  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/$tag -o p -- python3 $R/bench.py --config $c --reads $reads --no-extras --no-cpu-baseline --steps 10 --warmup 3 > $O/$tag.json 2> $O/$tag.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/$tag -o p -- python3 $R/bench.py --full --config $c --reads $reads --no-extras --no-cpu-baseline --steps 10 --warmup 3 > $O/$tag.json 2> $O/$tag.err
 fi
 python3 $R/tools/timeline.py $O/$tag > $O/${tag}_timeline.txt
 rm -rf $O/$tag
