@@ -45,8 +45,6 @@ struct BxDev {
   int32_t listed_mark;     // bin_of of a read on a list: -5 (the planner leaves it alone: it runs BESIDE the band kernels), or 0 (open: round 2's order)
   int64_t list_stride;
   uint32_t* ctr;           // BXC_*
-  int32_t lazy_scripts;    // the scripts of reads finished as pure diagonals are not written (k_diag_scripts makes them when asked for)
-  uint8_t* early;          // [n] or nullptr: 1 for the reads the plan finishes (the early tally, mia_consensus_kernels.h: k_rec_early), 0 for all others
   uint32_t dbg;            // MIA_HIP_BX_DEBUG (profiling only, results are wrong): 1 no traceback, 2 one DP row only
   // k_bx_plan in two launches (phase 1 / phase 2): the reads whose anchors lie on two diagonals (or that want the end-indel
   // rescue) are handed from the first to the second through this list; nullptr: one launch, the block's first threads finish them
@@ -55,9 +53,6 @@ struct BxDev {
   // ... and the reads whose loss exceeds what the 10-mers vouch for go on to a third launch (phase 3: bx_fine_anchors); nullptr: no third launch
   struct BxCandRec* cand2;
   uint32_t* cand2_n;
-  // the band DPs in two rounds (align_all: split_dp): `snap` holds the lengths of the values / trace lists as the plan's first launch left
-  // them (k_bx_snap); round 1 takes the entries below, round 2 -- behind the plan's last launch -- the ones from there on
-  const uint32_t* snap;
   // round 6: the reads the plan leaves OPEN (given up on, or strand unknown) listed by the plan itself -- at steady state a few hundred per
   // million, which k_align_open then takes one per wavefront, instead of the planner's count / scan / fill over ALL reads and a quad pass
   // (align_all: direct_open); nullptr: the planner bins them
@@ -81,9 +76,6 @@ struct BxDev {
   // workgroups), 147 with eight (two wavefronts per SIMD); 10 M solexa reads 5.44 ms per step with four, 5.33 with eight
   int32_t qch;
 };
-// which entries of the plan's lists a launch of the band DPs takes
-enum { BX_PART_ALL = 0, BX_PART_HEAD = 1, BX_PART_TAIL = 2 };
-__global__ void k_bx_snap(const uint32_t* ctr, uint32_t* snap);
 struct BxCandRec { int32_t i; BxAnchors an; };
 constexpr int BX_FINE_LANES = 1;         // lanes that share the fine blocks of one read in the plan's third launch (measured: what a read costs there is
                                          // bx_finish, which one lane walks alone -- eight lanes per read made the launch no shorter and the bulk case four times longer)
@@ -155,7 +147,7 @@ __device__ __forceinline__ void bx_diag_scripts(const ReadSet& rs, unsigned long
   }
 }
 
-// The scripts the band pipeline did not write (BxDev::lazy_scripts): a read finished as a pure diagonal (ST_DIAG, abr = 0)
+// The scripts the band pipeline does not write: a read finished as a pure diagonal (ST_DIAG, abr = 0)
 // sits on consecutive columns from as - refstart on.  Nothing on the device reads the script of such a read (k_rec_geom,
 // the tallies and the insert events all go by the flag); the host does, through mia_hip_get_scripts.
 __global__ __launch_bounds__(256) void k_diag_scripts(ReadSet rs) {
@@ -267,8 +259,10 @@ __device__ unsigned long long g_plan_clk[64 * 16];
 // 64-bit words of dynamic LDS the quick plan's per-read arrays take (two 16-bit words and a byte per read), in front of the planes
 __host__ __device__ constexpr int bx_quick_lds_words(int qch) { return (256 * qch * 5 + 7) / 8; }
 constexpr int BX_QCH = 8;          // stretches of 256 reads a workgroup of the quick plan (phase 4) takes AT MOST (BxDev::qch: four up to four million reads, eight beyond)
+// (the second launch for reads of 193 .. 256 bases is held to three wavefronts per SIMD, 170 VGPRs: left to itself the allocator takes 176 and
+// the compute unit holds two workgroups instead of three; no other instance changes with the bound, and this one's scratch stays at 80 bytes)
 template <int NW, int PH>
-__global__ __launch_bounds__(256) void k_bx_plan(ReadSet rs, RefInfo ref, RefPlanes rp, KmerHash ko, int64_t n_ref, BxDev bx, const int32_t* in_list,
+__global__ __launch_bounds__(256, (NW == 4 && PH == 2) ? 3 : 1) void k_bx_plan(ReadSet rs, RefInfo ref, RefPlanes rp, KmerHash ko, int64_t n_ref, BxDev bx, const int32_t* in_list,
                                                   const uint32_t* n_in_p, int64_t n_all, int32_t* bin_of) {
   // PH: 0 everything in one launch; 1 / 2 / 3 the three launches of the full plan; 4 the quick plan, 5 the same with the reference's planes in
   // LDS; 6 = phase 0 over a list that may be LONGER than the grid (the quick plan's undecided reads, taken beside the band DPs by a grid
@@ -358,7 +352,6 @@ __global__ __launch_bounds__(256) void k_bx_plan(ReadSet rs, RefInfo ref, RefPla
     __syncthreads();
     if (which >= 0) bx.lists[(int64_t)((late ? 3 * BX_NCLS : 0) + which) * bx.list_stride + blk_base[which] + rank] = r.i;
     if (to_fine) { BxCandRec rec; rec.i = r.i; rec.an = an; bx.cand2[blk_base[2 * BX_NCLS] + rank] = rec; }
-    if (!bx.lazy_scripts) bx_diag_scripts(rs, __ballot(bp.mode == BX_DONE), r.i, bp.dstar, r.len2);
     __syncthreads();
     if (threadIdx.x <= SLOT_FINE) blk_cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -462,7 +455,6 @@ __global__ __launch_bounds__(256) void k_bx_plan(ReadSet rs, RefInfo ref, RefPla
       const unsigned long long fm = __ballot(planned && bp.mode == BX_DONE), sm = __ballot(r.ok);
       if (lane == 0 && fm) atomicAdd(&q_fin, (uint32_t)__popcll(fm));
       if (lane == 0 && sm) atomicAdd(&q_seen, (uint32_t)__popcll(sm));
-      if (!bx.lazy_scripts) bx_diag_scripts(rs, fm, r.i, bp.dstar, r.len2);
       PLAN_CLK(3);
     }
     __syncthreads();
@@ -482,7 +474,6 @@ __global__ __launch_bounds__(256) void k_bx_plan(ReadSet rs, RefInfo ref, RefPla
       }
       const unsigned long long fm = __ballot(planned && bp.mode == BX_DONE);
       if (lane == 0 && fm) atomicAdd(&q_fin, (uint32_t)__popcll(fm));
-      if (!bx.lazy_scripts) bx_diag_scripts(rs, fm, r.i, bp.dstar, r.len2);
     }
     PLAN_CLK(4);
     __syncthreads();
@@ -579,7 +570,6 @@ __global__ __launch_bounds__(256) void k_bx_plan(ReadSet rs, RefInfo ref, RefPla
     if (waits) rr.ok = false;
     emit(rr, bp, marks && t0 + threadIdx.x < total && !waits, to_fine, an);
     PLAN_CLK(5);
-    if (bx.early && !in_list && t0 + threadIdx.x < total) bx.early[t0 + threadIdx.x] = bp.mode == BX_DONE ? 1 : 0;      // (every read passes here once)
     if (P == 1) {                                  // hand the waiting reads over: one reservation per block
       __shared__ uint32_t cand_base;
       __syncthreads();
@@ -667,7 +657,6 @@ __global__ __launch_bounds__(256) void k_bx_plan(ReadSet rs, RefInfo ref, RefPla
     Rd rr = r;
     if (to_fine) rr.ok = false;
     emit(rr, bp, marks && rr.ok, to_fine, an);
-    if (bx.early && rr.ok && bp.mode == BX_DONE) bx.early[r.i] = 1;
   }
   }
   if (PH != 6) return;
@@ -752,7 +741,6 @@ __global__ __launch_bounds__(256) void k_bx_values(ReadSet rs, RefInfo ref, BxDe
     }
     // (a read whose best score is not the plan's diagonal's has a gap or a soft clip: it stays open -- bin_of = 0 -- and the
     // planner hands it to the full-window kernels; a second trace launch for these few would cost a whole chunk's latency)
-    if (!bx.lazy_scripts) bx_diag_scripts(rs, __ballot(ok), r.i, r.d0 + r.jstar, r.len2);
   }
   for (int o = 32; o; o >>= 1) done += __shfl_xor(done, o);
   if (lane == 0 && done) atomicAdd(bxc(bx.ctr, BXC_DONE_VALUES), done);
@@ -812,20 +800,13 @@ __global__ __launch_bounds__(256) void k_bx_trace(ReadSet rs, RefInfo ref, BxDev
 // width, so every wavefront gets its share of the long ones).  A shared cursor looks more flexible, but thousands of
 // wavefronts adding to ONE word are served one after the other by the L2 (~12 ns each): with a grid as large as the chunk
 // list that was 60-75 us of every launch, more than the DP itself took (tools/bxl_probe.py).
-// part (BX_PART_*; HEAD / TAIL only for the plan's own lists, whose counters are the first 2 BX_NCLS: hi_ctr = BXC_LIST0 or BXC_LIST0 + BX_NCLS)
-__device__ __forceinline__ bool bxl_chunk_at(const BxDev& bx, uint32_t chunk, int hi_ctr, BxChunk* out, int part = BX_PART_ALL) {
+__device__ __forceinline__ bool bxl_chunk_at(const BxDev& bx, uint32_t chunk, int hi_ctr, BxChunk* out) {
   for (int c = BX_NCLS - 1; c >= 0; c--) {
-    const uint32_t live = *bxc(bx.ctr, hi_ctr + c);
-    const uint32_t mark = part == BX_PART_ALL ? 0u : bx.snap[hi_ctr - BXC_LIST0 + c];
-    const uint32_t lo = part == BX_PART_TAIL ? mark : 0u, hi = part == BX_PART_HEAD ? mark : live;
-    const uint32_t cnt = hi > lo ? hi - lo : 0u, per = (uint32_t)bxl_chunk_reads(c), nch = (cnt + per - 1u) / per;
-    if (chunk < nch) { out->cls = c; out->first = lo + chunk * per; out->count = hi; return true; }
+    const uint32_t cnt = *bxc(bx.ctr, hi_ctr + c), per = (uint32_t)bxl_chunk_reads(c), nch = (cnt + per - 1u) / per;
+    if (chunk < nch) { out->cls = c; out->first = chunk * per; out->count = cnt; return true; }
     chunk -= nch;
   }
   return false;
-}
-__global__ void k_bx_snap(const uint32_t* ctr, uint32_t* snap) {
-  if (blockIdx.x == 0 && threadIdx.x < 2 * BX_NCLS) snap[threadIdx.x] = *bxc(ctr, BXC_LIST0 + (int)threadIdx.x);
 }
 // what the wavefronts of a workgroup finished, added up in LDS: one atomic per workgroup on the statistics word
 __device__ __forceinline__ void bxl_count_done(uint32_t done, uint32_t* lds_word, uint32_t* global_word) {
@@ -870,7 +851,6 @@ __device__ __forceinline__ uint32_t bxl_values_chunk(const ReadSet& rs, const Re
     rs.status[r.i] = ST_DIAG;
     bin_of[r.i] = -4;
   }
-  if (!bx.lazy_scripts) bx_diag_scripts(rs, __ballot(ok), r.i, r.d0 + r.jstar, r.len2);
   // a read whose best score is not the plan's diagonal's has a gap or a soft clip: on to the late trace list of its class
   // (k_bxl_trace runs once more, behind this kernel); with listed_mark == 0 it simply stays open for the planner
   if (bx.listed_mark != 0)
@@ -878,7 +858,7 @@ __device__ __forceinline__ uint32_t bxl_values_chunk(const ReadSet& rs, const Re
   return ok ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(256, 4) void k_bxl_values(ReadSet rs, RefInfo ref, BxDev bx, int32_t* bin_of, int32_t part) {
+__global__ __launch_bounds__(256, 4) void k_bxl_values(ReadSet rs, RefInfo ref, BxDev bx, int32_t* bin_of) {
   // the step's chain runs through this kernel and the late trace behind it, while k_bxl_trace beside them has slack: their
   // wavefronts go first wherever a SIMD has both to choose from (MIA_HIP_BX_DEBUG=128: all at priority 0)
   if (!(bx.dbg & 128u)) __builtin_amdgcn_s_setprio(2);
@@ -891,7 +871,7 @@ __global__ __launch_bounds__(256, 4) void k_bxl_values(ReadSet rs, RefInfo ref, 
   uint32_t done = 0;
   BxChunk ch;
   const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
-  for (uint32_t chunk = wave; bxl_chunk_at(bx, chunk, BXC_LIST0, &ch, part); chunk += waves) {
+  for (uint32_t chunk = wave; bxl_chunk_at(bx, chunk, BXC_LIST0, &ch); chunk += waves) {
     switch (ch.cls) {
       case 0: done += bxl_values_chunk<1>(rs, ref, bx, bin_of, ch, sub_lds); break;
       case 1: done += bxl_values_chunk<2>(rs, ref, bx, bin_of, ch, sub_lds); break;
@@ -918,8 +898,8 @@ __device__ __forceinline__ uint32_t bxl_trace_chunk(const ReadSet& rs, const Ref
     const int32_t* sub = sub_lds + r.st * (31 * 4 * BX_SUB_ROW);
     int16_t* cols = rs.cols + (int64_t)r.i * rs.stride;
     const int rows = (bx.dbg & 2u) ? 1 : r.len2;
-    got = edge ? bxl_trace<LPR, true>(bx.refnib, r.s, r.l1, r.rw, rows, r.d0, sub, u, (int)(threadIdx.x & 63), slab, cols, &res, bx.lazy_scripts != 0, (bx.dbg & 1u) != 0)
-               : bxl_trace<LPR, false>(bx.refnib, r.s, r.l1, r.rw, rows, r.d0, sub, u, (int)(threadIdx.x & 63), slab, cols, &res, bx.lazy_scripts != 0, (bx.dbg & 1u) != 0);
+    got = edge ? bxl_trace<LPR, true>(bx.refnib, r.s, r.l1, r.rw, rows, r.d0, sub, u, (int)(threadIdx.x & 63), slab, cols, &res, (bx.dbg & 1u) != 0)
+               : bxl_trace<LPR, false>(bx.refnib, r.s, r.l1, r.rw, rows, r.d0, sub, u, (int)(threadIdx.x & 63), slab, cols, &res, (bx.dbg & 1u) != 0);
   }
   if (got) {                                   // (not got on a read's first lane: the reference's index-0 quirk -- the full-window kernels take the read)
     rs.score[r.i] = res.score;
@@ -939,8 +919,7 @@ __device__ __forceinline__ uint32_t bxl_trace_chunk(const ReadSet& rs, const Ref
 // trace slab of a wavefront: [row][lane][2 words]
 constexpr int BXL_SLAB_ROW_WORDS = 128;
 // list0 / ctr0: BX_NCLS / BXC_LIST0 + BX_NCLS for the plan's trace lists, 2 BX_NCLS / BXC_LATE0 for the values DP's left-overs
-__device__ __forceinline__ void bxl_trace_grid(const ReadSet& rs, const RefInfo& ref, const BxDev& bx, uint32_t* slabs, int64_t slab_words, int32_t* bin_of, int list0, int ctr0,
-                                               int part = BX_PART_ALL) {
+__device__ __forceinline__ void bxl_trace_grid(const ReadSet& rs, const RefInfo& ref, const BxDev& bx, uint32_t* slabs, int64_t slab_words, int32_t* bin_of, int list0, int ctr0) {
   __shared__ int32_t sub_lds[BX_SUB_WORDS];
   for (int k = threadIdx.x; k < BX_SUB_WORDS; k += 256) sub_lds[k] = bx.sub256[k];
   __syncthreads();
@@ -951,7 +930,7 @@ __device__ __forceinline__ void bxl_trace_grid(const ReadSet& rs, const RefInfo&
   uint32_t done = 0;
   BxChunk ch;
   const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
-  for (uint32_t chunk = wave; bxl_chunk_at(bx, chunk, ctr0, &ch, part); chunk += waves) {
+  for (uint32_t chunk = wave; bxl_chunk_at(bx, chunk, ctr0, &ch); chunk += waves) {
     switch (ch.cls) {
       case 0: done += bxl_trace_chunk<1>(rs, ref, bx, bin_of, ch, sub_lds, slab, list0); break;
       case 1: done += bxl_trace_chunk<2>(rs, ref, bx, bin_of, ch, sub_lds, slab, list0); break;
@@ -963,8 +942,8 @@ __device__ __forceinline__ void bxl_trace_grid(const ReadSet& rs, const RefInfo&
   bxl_count_done(done, &done_wg, bxc(bx.ctr, BXC_DONE_TRACE));
 }
 // (two names for one body: a profile tells the plan's lists and the values DP's left-overs apart)
-__global__ __launch_bounds__(256, 4) void k_bxl_trace(ReadSet rs, RefInfo ref, BxDev bx, uint32_t* slabs, int64_t slab_words, int32_t* bin_of, int32_t part) {
-  bxl_trace_grid(rs, ref, bx, slabs, slab_words, bin_of, BX_NCLS, BXC_LIST0 + BX_NCLS, part);
+__global__ __launch_bounds__(256, 4) void k_bxl_trace(ReadSet rs, RefInfo ref, BxDev bx, uint32_t* slabs, int64_t slab_words, int32_t* bin_of) {
+  bxl_trace_grid(rs, ref, bx, slabs, slab_words, bin_of, BX_NCLS, BXC_LIST0 + BX_NCLS);
 }
 __global__ __launch_bounds__(256, 4) void k_bxl_trace_late(ReadSet rs, RefInfo ref, BxDev bx, uint32_t* slabs, int64_t slab_words, int32_t* bin_of) {
   if (!(bx.dbg & 128u)) __builtin_amdgcn_s_setprio(3);

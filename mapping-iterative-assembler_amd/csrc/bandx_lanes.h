@@ -343,7 +343,7 @@ __device__ __forceinline__ void bxl_values_star(const uint32_t* refnib, int s, c
 // finished here; false: the reference's index-0 quirk, or nothing alive in the last row.
 template <int LPR, bool EDGE>
 __device__ __forceinline__ bool bxl_trace(const uint32_t* refnib, int s, int len1, const uint32_t* rwords, int len2, int d0, const int32_t* sub256, int u,
-                                          int lane_in_wave, uint32_t* trace, int16_t* cols_out, BxResult* res, bool lazy_diag, bool no_traceback = false) {
+                                          int lane_in_wave, uint32_t* trace, int16_t* cols_out, BxResult* res, bool no_traceback = false) {
   constexpr int DEAD = BX_NEG * 256;
   constexpr int STEP = 1 - GEP * 256;                 // a running maximum ages by one position: value - GEP, length + 1
   constexpr int CAND = -GOP * 256 + STEP - 0xFF;      // a cell (packed as a diagonal source) becomes a gap source
@@ -497,7 +497,7 @@ __device__ __forceinline__ bool bxl_trace(const uint32_t* refnib, int s, int len
   }
   const int abr = r, abc = c;
   res->score = best; res->abc = abc; res->aec = aec; res->abr = abr; res->gaps = gaps; res->gap_desc = gap_desc;
-  if (gaps == 0 && abr == 0 && lazy_diag) return true;   // a pure diagonal from row 0: k_diag_scripts writes it when somebody asks
+  if (gaps == 0 && abr == 0) return true;   // a pure diagonal from row 0: k_diag_scripts writes it when somebody asks
   if (gaps <= EV) {
     // row q (>= abr) sits on column q + off, off = aec - R plus the shifts of every break above it; the rows a row gap
     // skipped are inserts

@@ -624,35 +624,6 @@ __global__ void k_links_apply(const int64_t* links, const int32_t* n_links_p, in
 }
 
 // depth-code parameters and multiplicities of every read's records + its dropped bits, after all links are in
-// ---- the early tally (round 4) ------------------------------------------------------------------------------------------
-// Four reads in five are finished by the PLAN (k_bx_plan: a proven gap-free diagonal) and do not change while the band DPs work
-// on the rest -- a quarter of a millisecond per million reads during which the tally's LDS pipes have nothing to do.  Their tally
-// runs then, beside the DPs, on what is known of them at that point: end points, strand, bases.  What is NOT known yet is what the
-// cull decides (it needs every read's records: AlnSeq slots are numbered across all reads, `dropped` lives in the slot) -- the
-// read's dropped marks, and the parameters of formerly split or doubly listed records.  The early tally ASSUMES the ordinary
-// case (not dropped, listed once, its own depth codes: the record k_rec_early writes); k_rec_params, which knows, puts every
-// early read whose true record differs on a list, and k_tally_fix takes the assumed contribution off again and adds the true
-// one (integer sums: exact).  k_bx_plan marks the reads it finishes in early[].
-__device__ __forceinline__ void rec_default_params(const RecGeom& g, int n_al, int32_t* p, int* actf) {
-  const int flen = g.ncols_f, blen = g.split ? g.ncols_b : 0;          // a gap-free read: a record's asp_len is its columns
-  *actf = g.split ? g.ncols_f : n_al;
-  p[0] = 0; p[1] = 0; p[2] = flen + blen; p[3] = 1;
-  p[4] = g.split ? flen : 0; p[5] = g.split ? *actf : 0; p[6] = g.split ? flen + blen : 0; p[7] = g.split ? 1 : 0;
-}
-__global__ __launch_bounds__(256) void k_rec_early(ReadSet rs, int32_t L, const uint8_t* early, int32_t* trec, const int32_t* umax = nullptr) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= rs.n || !early[i]) return;
-  const RecGeom g = rec_geom(rs.as[i], rs.ae[i], L);
-  int32_t p[8];
-  int actf;
-  rec_default_params(g, (int)rs.len[i], p, &actf);
-  int4* t4 = reinterpret_cast<int4*>(trec + i * 16);
-  t4[0] = make_int4(rs.as[i], rs.ae[i], (int32_t)(uint32_t)rs.len[i], (rs.rc[i] ? TRF_RC : 0) | TRF_DIAG | TRF_SK | ((umax && umax[i] >= 0) ? TRF_NO_N : 0));      // (abr = 0: the plan's reads start in row 0)
-  t4[1] = make_int4(rs.refstart[i], (int32_t)rs.roff[i], actf, 0);
-  t4[2] = make_int4(p[0], p[1], p[2], p[3]);
-  t4[3] = make_int4(p[4], p[5], p[6], p[7]);
-}
-
 // skip_if_no_links: k_cull_records has written every record already (its with_records argument) -- they stand unless a link exists:
 // a link changes the dropped bit, the multiplicity or the depth-code parameters of the slot it points at, and the record of the
 // read it comes from (its back length)
@@ -660,7 +631,7 @@ __global__ void k_rec_params(ReadSet rs, int32_t L, const int64_t* slot, const u
                              RecInfo ri, SlotInfo si, const int64_t* links, const int32_t* link_len, const int32_t* link_act, const int32_t* n_links_p,
                              int32_t cap, int64_t read_base,
                              uint8_t* drop_front, uint8_t* drop_back, uint32_t* flags, const int32_t* abort_if = nullptr,
-                             const uint8_t* early = nullptr, int32_t* fix_list = nullptr, int32_t* n_fix = nullptr, const int32_t* umax = nullptr,
+                             const int32_t* umax = nullptr,
                              int32_t skip_if_no_links = 0) {
   if (abort_if && *abort_if != 0) return;     // (mia_hip_iterate queued this launch before the alignment's exact-kernel count was known: see iterate_body)
   if (skip_if_no_links && *n_links_p == 0) return;
@@ -711,15 +682,6 @@ __global__ void k_rec_params(ReadSet rs, int32_t L, const int64_t* slot, const u
   }
   const uint32_t st = rs.status[i];
   rec_write(rs, i, ri.trec, drop_front, drop_back, df, db, p, st, ri.actf[i], umax);
-  if (early && early[i]) {
-    // tallied already, on the ordinary record (k_rec_early): does the true one say the same?
-    int32_t q[8];
-    int actf0;
-    rec_default_params(rec_geom(rs.as[i], rs.ae[i], L), (int)rs.len[i], q, &actf0);
-    bool same = df == 0 && db == 0 && rs.sk[i] && ri.actf[i] == actf0 && (st & ST_DIAG) && !(st & ST_TOO_LONG) && rs.abr[i] == 0;
-    for (int k = 0; k < 8; k++) same = same && p[k] == q[k];
-    if (!same) fix_list[atomicAdd(n_fix, 1)] = (int32_t)i;
-  }
 }
 
 // ---- tally: one read per wavefront, one read row per lane (4 passes for 256-base reads) ----
@@ -732,8 +694,7 @@ __device__ __forceinline__ int depth_code(int dff, int dfb) {   // src/fsdb.c:57
 // LDS and flushed once; anything outside the window (the back part of a read that wraps
 // around the origin) takes the global atomic.  Same integer sums either way.
 constexpr int TALLY_EV_CAP = 256;    // insert events a workgroup buffers in LDS
-constexpr int TALLY_CHUNK_LATE = 256;  // reads per workgroup of the tally's second half when the plan's reads went through the early tally
-constexpr int TALLY_CHUNK_LINEAR = 256;  // ... with the linear matrix: measured best of 256 / 512 / 768 (0.899 / 0.906 / 0.934 ms per million-read step)
+constexpr int TALLY_CHUNK_LINEAR = 256;  // reads per tally workgroup with the linear matrix: measured best of 256 / 512 / 768 (0.899 / 0.906 / 0.934 ms per million-read step)
 constexpr int TALLY_BUCKET = 128, TALLY_WIN = 384, TALLY_CHUNK = 512;   // 20 KB of LDS per workgroup: 8 workgroups (32 waves) per CU
 
 // The LDS window of a workgroup is circular: slot k holds column win_base + k, and past the end of the reference the
@@ -872,43 +833,16 @@ __global__ __launch_bounds__(256) void k_tally(ReadSet rs, RefInfo ref, const in
 }
 
 // ---- bucketing of the reads by alignment start (counting sort, one pass per iteration) ----
-// the early tally's corrections: one read per wavefront, its assumed contribution (the record k_rec_early wrote) off again --
-// the same adds with multiplicity -1 -- and its true one (k_rec_params' record) on; global atomics (a handful of reads)
-__global__ __launch_bounds__(256) void k_tally_fix(ReadSet rs, RefInfo ref, const int32_t* pssm2, const uint8_t* drop_front, const uint8_t* drop_back, TallyBuf tb,
-                                                    const int32_t* rec_true, const int32_t* rec_early, const int32_t* rec_actf, const int32_t* fix_list,
-                                                    const int32_t* n_fix, const int32_t* abort_if = nullptr) {
-  if (abort_if && *abort_if != 0) return;
-  __shared__ int32_t stage[4][16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int n = *n_fix;
-  for (int k = (int)blockIdx.x * 4 + wv; k < n; k += (int)gridDim.x * 4) {
-    const int i = fix_list[k];
-    if (lane < 16) {
-      int v = rec_early[(int64_t)i * 16 + lane];
-      if (lane == TREC_PARAMS + 3 || lane == TREC_PARAMS + 7) v = -v;          // the two records' multiplicities
-      stage[wv][lane] = v;
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    tally_one_read<false>(i, lane, rs, ref, pssm2, drop_front, drop_back, tb, nullptr, 0, rec_early, rec_actf, nullptr, nullptr, nullptr, nullptr, stage[wv]);
-    __builtin_amdgcn_wave_barrier();
-    tally_one_read<false>(i, lane, rs, ref, pssm2, drop_front, drop_back, tb, nullptr, 0, rec_true, rec_actf, nullptr, nullptr, nullptr);
-  }
-}
-
 constexpr int BUCKET_PER = 8;   // reads per thread of the bucketing kernels
 // zero / zero_words: a buffer this launch clears on the side (the tally, the gaps and the ranks' event-count slots behind them:
 // nothing adds to them before the tally kernel, which runs behind this one), or nullptr
-// part / want (the early tally, k_rec_early): only the reads with (part[i] != 0) == (want != 0) are sorted; part == nullptr: all
 // a read's bucket: its alignment start's stretch of TALLY_BUCKET columns -- and, split != 0 (the position-specific matrices' tally:
 // a workgroup's reads all of one strand, so that its vertical counters need no strand), the strand in the lowest bit.  nb counts
 // all buckets (twice the column stretches when split).
 __device__ __forceinline__ int bucket_of(const ReadSet& rs, int64_t i, int nb, int split) {
   return (min(rs.as[i] / TALLY_BUCKET, (nb >> split) - 1) << split) | (split ? (rs.rc[i] ? 1 : 0) : 0);
 }
-__device__ __forceinline__ bool bucket_takes(const ReadSet& rs, int64_t i, const uint8_t* part, int want) {
-  return i < rs.n && rs.sk[i] && (!part || (part[i] != 0) == (want != 0));
-}
+__device__ __forceinline__ bool bucket_takes(const ReadSet& rs, int64_t i) { return i < rs.n && rs.sk[i]; }
 // the key of the second sort (k_sort2_*: every bucket by alignment start), worked out where the reads are walked in their own order
 // (k_bucket_fill) and carried beside `order` as a byte: looked up through `order` it was three gathers per read and launch, and the two
 // launches -- 0.47 + 0.51 ms at 10 M reads, beside the cull on the other stream -- took the cull's memory bandwidth (k_cull_records 0.48 -> 1.29 ms)
@@ -922,7 +856,7 @@ __device__ __forceinline__ int sort2_key(const ReadSet& rs, int64_t i, int b, in
   return k < 0 ? 0 : (k >= SORT2_KEYS - 1 ? SORT2_KEYS - 2 : k);
 }
 __global__ __launch_bounds__(256) void k_bucket_count(ReadSet rs, int32_t nb, int32_t* count, int32_t* zero, int64_t zero_words, const int32_t* abort_if = nullptr,
-                                                       const uint8_t* part = nullptr, int32_t want = 0, int32_t split = 0) {
+                                                       int32_t split = 0) {
   if (abort_if && *abort_if != 0) return;     // (mia_hip_iterate queued this launch before the alignment's exact-kernel count was known: see iterate_body)
   extern __shared__ int32_t hist[];
   for (int b = threadIdx.x; b < nb; b += blockDim.x) hist[b] = 0;
@@ -930,13 +864,13 @@ __global__ __launch_bounds__(256) void k_bucket_count(ReadSet rs, int32_t nb, in
   __syncthreads();
   for (int k = 0; k < BUCKET_PER; k++) {
     const int64_t i = ((int64_t)blockIdx.x * BUCKET_PER + k) * 256 + threadIdx.x;
-    if (bucket_takes(rs, i, part, want)) atomicAdd(&hist[bucket_of(rs, i, nb, split)], 1);
+    if (bucket_takes(rs, i)) atomicAdd(&hist[bucket_of(rs, i, nb, split)], 1);
   }
   __syncthreads();
   for (int b = threadIdx.x; b < nb; b += blockDim.x) if (hist[b]) atomicAdd(&count[b], hist[b]);
 }
 // off[b] = first read of bucket b in `order`, wgoff[b] = first workgroup of bucket b (TALLY_CHUNK reads each)
-// chunk: reads per tally workgroup (TALLY_CHUNK at most; the late half of a split tally takes fewer -- its reads are the slow ones)
+// chunk: reads per tally workgroup (TALLY_CHUNK at most)
 __global__ __launch_bounds__(256) void k_bucket_scan(int32_t* count, int32_t nb, int32_t* off, int32_t* wgoff, int32_t* cursor, int32_t* wg_bucket, const int32_t* abort_if = nullptr,
                                                       int32_t chunk = TALLY_CHUNK) {
   if (abort_if && *abort_if != 0) return;     // (mia_hip_iterate queued this launch before the alignment's exact-kernel count was known: see iterate_body)
@@ -966,7 +900,7 @@ __global__ __launch_bounds__(256) void k_bucket_scan(int32_t* count, int32_t nb,
   if (t == 255) { off[nb] = s_run[255]; wgoff[nb] = s_wg[255]; }
 }
 __global__ __launch_bounds__(256) void k_bucket_fill(ReadSet rs, int32_t nb, const int32_t* off, int32_t* cursor, int32_t* order, const int32_t* abort_if = nullptr,
-                                                      const uint8_t* part = nullptr, int32_t want = 0, int32_t split = 0, uint8_t* okey = nullptr, int32_t packed = 0) {
+                                                      int32_t split = 0, uint8_t* okey = nullptr, int32_t packed = 0) {
   if (abort_if && *abort_if != 0) return;     // (mia_hip_iterate queued this launch before the alignment's exact-kernel count was known: see iterate_body)
   extern __shared__ int32_t sh[];
   int32_t* hist = sh;
@@ -977,7 +911,7 @@ __global__ __launch_bounds__(256) void k_bucket_fill(ReadSet rs, int32_t nb, con
   for (int k = 0; k < BUCKET_PER; k++) {
     const int64_t i = ((int64_t)blockIdx.x * BUCKET_PER + k) * 256 + threadIdx.x;
     bb[k] = -1; rank[k] = 0;
-    if (bucket_takes(rs, i, part, want)) { bb[k] = bucket_of(rs, i, nb, split); rank[k] = atomicAdd(&hist[bb[k]], 1); }
+    if (bucket_takes(rs, i)) { bb[k] = bucket_of(rs, i, nb, split); rank[k] = atomicAdd(&hist[bb[k]], 1); }
   }
   __syncthreads();
   for (int k = threadIdx.x; k < nb; k += blockDim.x) if (hist[k]) base[k] = atomicAdd(&cursor[k], hist[k]);

@@ -40,8 +40,8 @@ constexpr int64_t OPEN_SLAB_BYTES = (int64_t)MAX_READ * 64 * 12;   // its trace 
 constexpr int CTRL_BINS = 0;                                   // [count N_BINS][off N_BINS][cursor N_BINS][wide_count][retry_count]
 constexpr int CTRL_HDR = (3 * N_BINS + 2 + 1) & ~1;            // PH_* (8-byte aligned: the DP kernels fetch their range as a pair)
 constexpr int CTRL_FILTER = CTRL_HDR + PH_WORDS;               // 4 words (k_diag_filter / k_band_align)
-constexpr int CTRL_LKN = CTRL_FILTER + 4, CTRL_CULLF = CTRL_LKN + 1, CTRL_NEV = CTRL_CULLF + 1, CTRL_TFLAGS = CTRL_NEV + 1, CTRL_FIXN = CTRL_TFLAGS + 1;   // FIXN: reads on the early tally's fix list
-constexpr int CTRL_GENN = CTRL_FIXN + 1;                           // reads k_tally_binned left to k_tally_general
+constexpr int CTRL_LKN = CTRL_FILTER + 4, CTRL_CULLF = CTRL_LKN + 1, CTRL_NEV = CTRL_CULLF + 1, CTRL_TFLAGS = CTRL_NEV + 1;
+constexpr int CTRL_GENN = CTRL_TFLAGS + 2;                           // reads k_tally_binned left to k_tally_general (the word in front of it is reserved: the block's layout stays as it was)
 constexpr int CTRL_BXC = (CTRL_GENN + 1 + 63) & ~63;           // BXC_* counters, a cache line each
 constexpr int CTRL_WORDS = CTRL_BXC + BXC_WORDS;
 constexpr int CTRL_C0 = CTRL_BINS + 3 * N_BINS, CTRL_CN = CTRL_WORDS - CTRL_C0;    // what the host looks at behind an alignment: wide / retry counts, planner header, filter and band counters
@@ -61,78 +61,110 @@ static inline const char* alt_env(const char*) { return nullptr; }
 
 struct mia_hip_ctx {
   int device = 0;
-  int32_t* d_ctrl = nullptr;
-  uint32_t stage_mask = ~0u;               // timed stages (mia_hip_set_stage_mask): an event pair costs the stream a few microseconds
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the trace DP of the plan's own lists runs beside the values DP
-  hipStream_t stream3 = nullptr; hipEvent_t ev_join3 = nullptr;                      // ... and both beside the planner and the full-window kernels of the reads the plan gave up on
-  int32_t* d_retry2 = nullptr; int64_t retry2_cap = 0;                              // reads no band kernel could finish
-  uint32_t* d_bx_slabs_late = nullptr; int64_t bx_slab_late_cap = 0; int bx_late_wgs = 0;
-  uint32_t* d_bx_slabs_late2 = nullptr; bool dp_aside = false;      // the second late trace's slabs; this alignment's values DP and late trace are on stream2 (align_all: fork_at_quick)
-  // mia_hip_iterate without a host wait behind the alignment: cull, tally and consensus are queued at once and every one of
-  // their kernels returns at its first instruction if *abort_if != 0 (reads are waiting for the exact one-read-per-thread
-  // kernel: the host sees that with the consensus, runs it, and queues the chain again)
-  const int32_t* abort_if = nullptr;
-  bool spec_ok = false, spec_pending = false, spec_filtered = false, spec_bx = false, spec_plain = false;
-  int64_t spec_redone = 0;                  // iterations whose cull / tally / consensus were queued twice (reads for the exact kernel)
-  bool pend_encode = false; int32_t pend_L = 0, pend_wl = 0, pend_total = 0;      // mia_hip_iterate: d_ascii holds the new reference, d_ref not yet
-  uint32_t* d_prep_bar = nullptr; uint32_t prep_bar_count = 0; bool no_prep_fuse = false;   // k_ref_prep's grid barrier (MIA_HIP_NO_PREP_FUSE=1: six launches)
-  // round 6: the band plan lists the reads it leaves open itself and k_align_open takes them one per wavefront (align_all: direct_open;
-  // MIA_HIP_NO_DIRECT_OPEN=1, alt build: the planner's count / scan / fill and the quad kernels, as in every iteration with many open reads)
-  KbPair* d_kbits = nullptr;            // the quick plan's bitmaps over all 4^10 10-mers (bandx_body.h: KmerBits), remade with the table
-  int use_quick = 1; int64_t quick_steps = 0;      // the quick plan in front of k_bx_plan's launches (MIA_HIP_NO_QUICK_PLAN=1, alt build: the full plan for every read)
-  bool direct_open_now = false;        // this alignment's open reads are on d_open_list (set by align_all, read by bx_join_and_retry)
-  int32_t* d_open_list = nullptr; int64_t open_cap = 0; unsigned char* d_slabs_open = nullptr; bool use_direct_open = true; int64_t direct_open_steps = 0;   // the plan's own open list (n entries), k_align_open's trace slabs (one per workgroup of its grid)
-  bool spec_force = false; int32_t* d_one = nullptr;      // MIA_HIP_SPEC_TEST=1 (tests): a word that holds 1
-  bool zero_copy = true;        // mia_hip_iterate: the last kernel writes consensus and counters into pinned host memory itself (MIA_HIP_NO_ZERO_COPY=1: two copies)
-  // the launches other streams wait for signal their events themselves (launch_k) instead of a marker behind them; MIA_HIP_NO_EXT_EVENTS=1: markers
-  bool cull_scan = false, tail_scans = false, stage_markers = false;
-  bool spin_wait = true;        // mia_hip_iterate's one wait asks (hipStreamQuery) instead of sleeping on an interrupt; MIA_HIP_SPIN_WAIT=0: hipStreamSynchronize
-  uint32_t ext_events = 31u; bool planner_end_signalled = false, align_end_signalled = false;
-  BxCandRec* d_bx_cand2 = nullptr; int use_fine = 1;      // the third launch's list (reads for the fine blocks); MIA_HIP_NO_FINE=1: none; MIA_HIP_FINE=2: in every iteration
-  BxCandRec* d_bx_cand = nullptr; int64_t cand_cap = 0, cand2_cap = 0; bool plan_split = true;      // k_bx_plan's hand-over list between its two launches (MIA_HIP_NO_PLAN_SPLIT=1: one launch)
-  bool no_spec = false;                     // MIA_HIP_NO_SPEC=1: wait for the alignment's counters before the cull is queued
-  bool no_side_buckets = false;             // MIA_HIP_NO_SIDE_BUCKETS=1
-  int buckets_queued = 0;                   // the tally's counting sort is already queued: 1 on the context's stream, 2 on stream2 (ev_join behind it)
-  // the early tally (mia_consensus_kernels.h, k_rec_early): the reads the plan finishes are tallied on stream4 beside the band DPs
-  hipStream_t stream4 = nullptr; hipEvent_t ev_early = nullptr;
-  // the band DPs in two rounds (align_all: split_dp): the first beside the plan's second and third launch, on the lists its first launch made
-  hipEvent_t ev_snap = nullptr, ev_v1 = nullptr; uint32_t* d_bx_snap = nullptr; int split_dp_mode = 0;      // mode: 0 auto, 1 always (MIA_HIP_SPLIT_DP=1), -1 never (MIA_HIP_SPLIT_DP=0)
-  bool cull_with_records = true;      // k_cull_records writes the tally records of an iteration without links itself (MIA_HIP_NO_CULL_RECORDS=1: k_rec_params always)
-  int64_t split_dp_steps = 0;
-  // MIA_HIP_EARLY_TALLY=1 (alt build only; an experiment that measured SLOWER): the plan's reads tallied beside the band DPs
-  bool use_early = false, early_queued = false;
-  int early_wgs_per_cu = 2;
-  uint8_t* d_early = nullptr; int32_t* d_trec_early = nullptr; int32_t* d_order_e = nullptr; int32_t* d_fix_list = nullptr; int64_t early_cap = 0;
-  int32_t* d_bucket_e = nullptr; int bucket_e_cap = 0, bucket_e_clean_nb = -1;
-  int32_t* d_tally_slabs_e = nullptr; int64_t tally_slab_e_cap = 0;
-  unsigned char* d_slabs_retry[3] = {nullptr, nullptr, nullptr};      // trace slabs of the band kernels' retry launch (see launch_window)
-  bool bx_planner_aside = false;            // this call: the planner and the full-window kernels run on stream2, the band DPs on the context's stream
-  bool bx_pending_join = false;                                                     // band kernels are still running on stream2 / stream3
+  int cus = 1;
   std::string err;
   struct PoolBlock { void* p; size_t cap; bool lent; };
   std::vector<PoolBlock> pool;             // device temporaries of the one-off calls (pool_alloc)
+  // pinned staging: small copies to and from pageable memory wait for the stream, pinned ones do not
+  unsigned char* h_pin = nullptr; static constexpr size_t PIN_BYTES = 1 << 20, PIN_MISC = 64 << 10;
+  int32_t* d_ctrl = nullptr;               // the control block (CTRL_*)
+  uint32_t dbg = 0;                        // timing experiments only, results are wrong when set (read_alt_switches)
+
+  // ---- streams and events ------------------------------------------------------------------------------------------------
+  hipStream_t stream = nullptr;
+  hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the trace DP of the plan's own lists runs beside the values DP
+  hipStream_t stream3 = nullptr; hipEvent_t ev_join3 = nullptr;                      // ... and both beside the planner and the full-window kernels of the reads the plan gave up on
+  // the launches other streams wait for signal their events themselves (launch_k) instead of a marker behind them: a bit per launch, all or none
+  uint32_t ext_events = 31u; bool planner_end_signalled = false, align_end_signalled = false;
+  bool spin_wait = true;                   // mia_hip_iterate's one wait asks (hipStreamQuery) instead of sleeping on an interrupt; MIA_HIP_SPIN_WAIT=0: hipStreamSynchronize
+  // HIP-event timers of the kernels bench.py reports, one per stage (mia_hip_stage_stats); pairs are recycled through ev_free
+  uint32_t stage_mask = ~0u;               // timed stages (mia_hip_set_stage_mask): an event pair costs the stream a few microseconds
+  struct StageTimer { std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; int64_t launches = 0; };
+  StageTimer stg[STG_COUNT];
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
+
+  // ---- reads (and the matrices they are scored with), reference --------------------------------------------------------------
   // PSSMs (fwd, rc)
   int32_t* d_pssm = nullptr;
   int max_abs = 0;
-  int tally_pk_bias = -1;                   // the tally's packed end-base sums (k_tally_binned): the bias that makes every score positive, or -1: entries too large
   int max_pos = 0;   // largest positive PSSM entry: bounds any score by rows * max_pos
   bool have_pssm = false;
+  bool flat = false;
   PackSet packs;
-  // reads
   ReadSet rs{};
   uint8_t* d_packed = nullptr; uint32_t* d_roff = nullptr; uint16_t* d_len = nullptr;
   uint8_t* d_rc = nullptr; uint8_t* d_sk = nullptr;
   int32_t *d_as = nullptr, *d_ae = nullptr, *d_score = nullptr, *d_refstart = nullptr;
   int16_t* d_abr = nullptr; uint32_t* d_status = nullptr; int16_t* d_cols = nullptr;
   int max_len = 0;
-  // plan
-  int32_t *d_bin_of = nullptr, *d_list = nullptr, *d_wide_list = nullptr, *d_retry_list = nullptr;
-  int use_band = 1;   // MIA_HIP_NO_BAND=1: the quad kernel stores the full trace
-  int32_t* d_bins = nullptr;  // [count N_BINS][off N_BINS][cursor N_BINS][wide_count 1]
+  int min_len = 0;                          // shortest stored read
+  std::vector<int32_t> h_len;               // read lengths on the host (the score-cut regression of reads of different lengths)
+  uint64_t* d_rplanes = nullptr; int rplane_words = 0;   // bit planes of the stored reads (k_read_planes)
+  int32_t* d_umax = nullptr; bool umax_valid = false;
   // reference
   uint8_t* d_ref = nullptr; int ref_cap = 0; int L = 0, wrap = 0; int explicit_win = 0; bool have_ref = false; bool aligned = false;
-  // cull
+  bool ref_mostly_bases = true;            // fewer than 2 % of the reference columns are N
+  bool ref_few_n = true;                   // ... fewer than 0.2 %: four windows in five hold none (the quick plan asks those even where the table spells out N columns)
+  int64_t kh_entries = 0;                  // > 0: the reference has N columns and its 10-mer table lists them (bandx_body.h, N COLUMNS)
+
+  // ---- plan and full-window kernels ----------------------------------------------------------------------------------------
+  int32_t *d_bin_of = nullptr, *d_list = nullptr, *d_wide_list = nullptr, *d_retry_list = nullptr;
+  int32_t* d_bins = nullptr;  // [count N_BINS][off N_BINS][cursor N_BINS][wide_count 1]
+  int32_t* d_plan_hdr = nullptr;            // PH_* (k_plan_scan)
+  bool deferred = false;                    // align_all: no host round trip before its end
+  // trace slabs of the persistent DP grid (one per workgroup, per CPL class)
+  unsigned char* d_slabs[N_CPL] = {nullptr, nullptr, nullptr};
+  unsigned char* d_slabs_retry[3] = {nullptr, nullptr, nullptr};      // trace slabs of the band kernels' retry launch (see launch_window)
+  unsigned char* d_quad_slabs = nullptr;
+  int quad_wgs = 0;
+  int grid_wgs = 0;
+  int window_wgs[N_CPL] = {0, 0, 0};
+  int64_t plain_retried = 0, plain_total = 0;
+  bool wide_to_caller = false;             // run_wide marks its reads ST_ESCAPE instead of aligning them (the anchored pass 1)
+  // wide scratch
+  int32_t* d_scratch = nullptr; int64_t scratch_cap = 0; int64_t* d_scratch_off = nullptr; int64_t scratch_off_cap = 0;
+  // round 6: the band plan lists the reads it leaves open itself and k_align_open takes them one per wavefront (align_all: direct_open):
+  // the plan's own open list (n entries), k_align_open's trace slabs (one per workgroup of its grid)
+  int32_t* d_open_list = nullptr; int64_t open_cap = 0; unsigned char* d_slabs_open = nullptr; bool use_direct_open = true; int64_t direct_open_steps = 0;
+  bool direct_open_now = false;        // this alignment's open reads are on d_open_list (set by align_all, read by bx_join_and_retry)
+
+  // ---- band pipeline, round 1: the diagonal filter (diag_filter.h) and its banded DP (band_body.h), flat matrix only -----------
+  int use_filter = 1;
+  int32_t *d_kocc_cnt = nullptr, *d_kocc_pos = nullptr;   // 10-mer table of the reference (diag_filter.h: KmerOcc)
+  uint64_t* d_planes = nullptr; int64_t plane_cap = 0;   // lo | hi | ok, plane_cap words each
+  uint32_t* d_filter_n = nullptr; int64_t filter_proven = 0, filter_seen = 0;   // device: {finished by the filter, left over, finished by the banded DP}
+  int use_banddp = 1;
+  int32_t* d_left_list = nullptr; int64_t left_cap = 0;
+  uint32_t* d_band_slabs = nullptr; int64_t band_slab_cap = 0;
+  int64_t band_done = 0;
+
+  // ---- band pipeline for any PSSM (bandx_kernels.h): plan -> values-only DP -> trace DP ------------------------------------------
+  bool bx_ok = false;                       // the matrices allow it (bx_make_tables)
+  int use_bx = 1, use_lanes = 1; bool bx_serial = false; uint32_t bx_dbg = 0;
+  int32_t *d_bx_sub = nullptr, *d_bx_mrow = nullptr; int16_t *d_bx_loss = nullptr, *d_bx_dl = nullptr;   // sub | sub * 256; M; losses; block costs
+  int32_t bx_min_m = 0, bx_max_m = 0;
+  uint32_t* d_refnib = nullptr; int64_t refnib_cap = 0;
+  uint32_t* d_khash = nullptr; int32_t* d_khash_ovf = nullptr; uint32_t khash_cap = 0;   // 10-mers of the reference (bandx_body.h: KmerHash)
+  KbPair* d_kbits = nullptr;            // the quick plan's bitmaps over all 4^10 10-mers (bandx_body.h: KmerBits), remade with the table
+  int use_quick = 1; int64_t quick_steps = 0;      // the quick plan in front of k_bx_plan's launches
+  uint32_t* d_prep_bar = nullptr; uint32_t prep_bar_count = 0; bool no_prep_fuse = false;   // k_ref_prep's grid barrier
+  uint32_t* d_bx_plan = nullptr; int32_t* d_bx_expect = nullptr; int32_t* d_bx_lists = nullptr; int64_t bx_cap = 0;
+  BxCandRec* d_bx_cand = nullptr; int64_t cand_cap = 0, cand2_cap = 0; bool plan_split = true;      // k_bx_plan's hand-over list between its two launches
+  BxCandRec* d_bx_cand2 = nullptr; int use_fine = 1;      // the third launch's list (reads for the fine blocks)
+  uint32_t* d_bx_ctr = nullptr;
+  uint32_t* d_bx_slabs = nullptr; int64_t bx_slab_cap = 0;
+  int bx_values_wgs = 0, bx_trace_wgs = 0;
+  uint32_t* d_bx_slabs_late = nullptr; int64_t bx_slab_late_cap = 0; int bx_late_wgs = 0;
+  uint32_t* d_bx_slabs_late2 = nullptr; bool dp_aside = false;      // the second late trace's slabs; this alignment's values DP and late trace are on stream2 (align_all: fork_at_quick)
+  int32_t* d_retry2 = nullptr; int64_t retry2_cap = 0;                              // reads no band kernel could finish
+  bool bx_planner_aside = false;            // this call: the planner and the full-window kernels run on stream2, the band DPs on the context's stream
+  bool bx_pending_join = false;             // band kernels are still running on stream2 / stream3
+  bool diag_scripts_missing = false;       // the last alignment left the scripts of its ST_DIAG reads unwritten (k_diag_scripts)
+  int64_t bx_seen = 0, bx_done[3] = {0, 0, 0};   // reads planned on; finished by the plan / the values DP / the trace DP
+  int64_t bx_launches = 0;
+  uint32_t bx_last[BXC_COUNTERS] = {0};     // counters of the last call (list lengths, reasons a read was not planned)
+
+  // ---- cull ----------------------------------------------------------------------------------------------------------------
   int64_t* d_slot = nullptr; int64_t* d_partial = nullptr; int64_t* d_total = nullptr;
   uint8_t *d_slot_dropped = nullptr, *d_drop_f = nullptr, *d_drop_b = nullptr; int64_t n_slots = 0;
   // stale back_asp emulation (mia_consensus_kernels.h, k_cull_mark)
@@ -147,109 +179,69 @@ struct mia_hip_ctx {
   int32_t* d_n_links_all = nullptr; int64_t links_cap_all = 0; int32_t* d_n_links_gathered = nullptr;
   int32_t* d_link_len = nullptr; int64_t link_len_cap = 0;
   uint32_t* d_cull_flags = nullptr;
+  uint32_t* d_cull_sync = nullptr;          // k_slot_count's arrival counter (zero between launches)
   unsigned long long* d_sums = nullptr;
   int64_t read_base = 0;                   // global index of this context's first read (sharded runs)
   int64_t slot_base = 0;
   bool culled = false, links_applied = false;
   std::vector<int64_t*> owned_links;       // gathered link buffers (mia_hip_set_links)
-  // tally
+  bool cull_scan = false, tail_scans = false;
+  bool cull_with_records = true;           // k_cull_records writes the tally records of an iteration without links itself
+  int64_t pre_cull_records = 0, pre_cull_links = 0; bool pre_cull_valid = false;   // mia_hip_score_sums' by-products
+
+  // ---- tally and consensus -------------------------------------------------------------------------------------------------
   TallyBuf tb{}; int tally_cap = 0; int32_t* d_ins_off = nullptr; int32_t* d_ins_total = nullptr;
   int32_t* d_ins_tally = nullptr; int64_t ins_tally_cap = 0; char* d_calls = nullptr; char* d_ins_calls = nullptr;
   int64_t ins_calls_cap = 0; int32_t n_events_host = 0; bool tallied = false;
-  // trace slabs of the persistent DP grid (one per workgroup, per CPL class)
-  unsigned char* d_slabs[N_CPL] = {nullptr, nullptr, nullptr};
-  unsigned char* d_quad_slabs = nullptr;
-  int quad_wgs = 0;
-  int use_quad = 1;   // MIA_HIP_NO_QUAD=1 routes everything through the one-read-per-wave kernels
-  int plain_behind_band = 0;
-  int use_plain = 1;  // MIA_HIP_NO_PLAIN=1: no values-only first pass, every quad goes straight to the trace kernel
-  int64_t plain_retried = 0, plain_total = 0;
-  // the diagonal filter (diag_filter.h): flat matrix only
-  bool tally_linear = false;               // MIA_HIP_NO_LINEAR_TALLY=1: the tally adds the four scores of every base
-  bool ref_mostly_bases = true;            // fewer than 2 % of the reference columns are N
-  bool ref_few_n = true;                   // ... fewer than 0.2 %: four windows in five hold none (the quick plan asks those even where the table spells out N columns)
-  int64_t kh_entries = 0;                  // > 0: the reference has N columns and its 10-mer table lists them (bandx_body.h, N COLUMNS)
-  bool diag_scripts_missing = false;       // the last alignment left the scripts of its ST_DIAG reads unwritten (k_diag_scripts)
-  int lazy_scripts = 1;                    // MIA_HIP_EAGER_SCRIPTS=1: the band pipeline writes them as it goes
-  bool wide_to_caller = false;             // run_wide marks its reads ST_ESCAPE instead of aligning them (the anchored pass 1)
-  int use_wild = 1;                        // MIA_HIP_NO_WILD=1: reads whose window holds an N go to the full-window kernels
-  bool flat = false; int use_filter = 1;   // MIA_HIP_NO_DIAG_FILTER=1 sends every read to the DP kernels
-  int64_t pre_cull_records = 0, pre_cull_links = 0; bool pre_cull_valid = false;   // mia_hip_score_sums' by-products
-  int32_t *d_kocc_cnt = nullptr, *d_kocc_pos = nullptr;   // 10-mer table of the reference (diag_filter.h: KmerOcc)
-  uint64_t* d_planes = nullptr; int64_t plane_cap = 0;   // lo | hi | ok, plane_cap words each
-  uint32_t* d_filter_n = nullptr; int64_t filter_proven = 0, filter_seen = 0;   // device: {finished by the filter, left over, finished by the banded DP}
-  int use_banddp = 1;                       // MIA_HIP_NO_BAND_DP=1: the filter's left-overs go straight to the full-window kernels
-  int32_t* d_left_list = nullptr; int64_t left_cap = 0;
-  uint32_t* d_band_slabs = nullptr; int64_t band_slab_cap = 0;
-  int64_t band_done = 0;
-  // the matrix-agnostic band pipeline (bandx_kernels.h): plan -> values-only DP -> trace DP, for any PSSM
-  bool bx_ok = false;                       // the matrices allow it (bx_make_tables)
-  uint32_t* d_cull_sync = nullptr;          // k_slot_count's arrival counter (zero between launches)
-  double myers_kernel_ms = 0; bool myers_no_lanes = false, myers_no_ond = false, fake_event_overflow = false;   // the kernels of the last mia_hip_myers call (HIP events); MIA_HIP_MYERS_NO_LANES=1: every pair through k_myers
-  int bucket_clean_nb = -1;                 // the tally's bucket counts are zero for this bucket count (k_bucket_scan leaves them so)
-  bool no_auto_plain = false;               // MIA_HIP_NO_AUTO_PLAIN=1: the values-only pass behind the band only when MIA_HIP_PLAIN_BEHIND_BAND asks for it
-  bool bx_serial = false;                   // MIA_HIP_BX_SERIAL=1
-  uint32_t bx_dbg = 0;                      // MIA_HIP_BX_DEBUG (profiling): 1 no traceback, 2 one DP row, 4 no values launch, 8 no trace launch
-  int use_lanes = 1;                        // MIA_HIP_NO_LANES=1: the band DPs one read per lane (bx_values / bx_trace) instead of W/8 lanes per read (bandx_lanes.h)
-  int use_bx = 1;                           // MIA_HIP_NO_BANDX=1: the round-1 path (flat: filter + k_band_align; PSSM: full-window kernels)
-  int bx_filter_first = 0;                  // MIA_HIP_BX_FILTER=1 (flat matrix): k_diag_filter runs ahead of the plan
-  int32_t *d_bx_sub = nullptr, *d_bx_mrow = nullptr; int16_t *d_bx_loss = nullptr, *d_bx_dl = nullptr;   // sub | sub * 256; M; losses; block costs
-  int32_t bx_min_m = 0, bx_max_m = 0;
-  uint64_t* d_rplanes = nullptr; int rplane_words = 0;   // bit planes of the stored reads (k_read_planes)
-  uint32_t* d_refnib = nullptr; int64_t refnib_cap = 0;
-  uint32_t* d_khash = nullptr; int32_t* d_khash_ovf = nullptr; uint32_t khash_cap = 0;   // 10-mers of the reference (bandx_body.h: KmerHash)
-  int32_t* d_umax = nullptr; bool umax_valid = false;
-  uint32_t* d_bx_plan = nullptr; int32_t* d_bx_expect = nullptr; int32_t* d_bx_lists = nullptr; int64_t bx_cap = 0;
-  uint32_t* d_bx_ctr = nullptr;
-  uint32_t* d_bx_slabs = nullptr; int64_t bx_slab_cap = 0;
-  int bx_values_wgs = 0, bx_trace_wgs = 0;
-  bool planner_beside = false;            // MIA_HIP_PLANNER_BESIDE=1 (alt build): the planner's head kernels beside the band DPs in every iteration
-  int64_t bx_seen = 0, bx_done[3] = {0, 0, 0};   // reads planned on; finished by the plan / the values DP / the trace DP
-  int64_t bx_launches = 0;
-  uint32_t bx_last[BXC_COUNTERS] = {0};     // counters of the last call (list lengths, reasons a read was not planned)
-  int grid_wgs = 0;
-  int window_wgs[N_CPL] = {0, 0, 0};
-  int cus = 1;
-  uint32_t dbg = 0;   // MIA_HIP_DEBUG_SKIP: timing experiments only, results are wrong when set
+  int64_t ins_total_host = 0;
+  bool consensus_done = false;
+  bool fake_event_overflow = false;
+  bool no_linear_tally = false, sort2_unpacked = false;
+  bool tally_linear = false;               // the score words of a column are linear in its base counts: the tally counts only (mia_hip_set_pssm)
+  int tally_pk_bias = -1;                   // the tally's packed end-base sums (k_tally_binned): the bias that makes every score positive, or -1: entries too large
   // read bucketing for the LDS-privatised tally
+  int use_binned_tally = 1;
   int32_t* d_bucket = nullptr; int bucket_cap = 0; int32_t* d_order = nullptr;
-  int use_binned_tally = 1;   // MIA_HIP_NO_BINNED_TALLY=1: plain global-atomic tally
+  int bucket_clean_nb = -1;                 // the tally's bucket counts are zero for this bucket count (k_bucket_scan leaves them so)
+  int buckets_queued = 0;                   // the tally's counting sort is already queued: 1 on the context's stream, 2 on stream2 (ev_join behind it)
+  bool no_side_buckets = false;
   int32_t* d_tally_slabs = nullptr; int64_t tally_slab_cap = 0;   // one LDS window per tally workgroup, summed by k_tally_reduce
   int32_t* d_gen_list = nullptr; int64_t gen_cap = 0;             // the reads k_tally_binned leaves to k_tally_reduce's extra workgroups (a thousand in a million; room for all)
-  // MIA_HIP_STRAND_SPLIT=1 (alt build only): position-specific matrices, the tally's buckets by column AND strand, the rows of depth code 15
-  // through the vertical counters.  Measured: configs[2] 1.313 -> 1.306 ms, configs[4] at 5 M reads 9.91 -> 10.2 ms (twice the part-filled
-  // workgroups and slabs; the end rows' packed atomics are what the kernel waits for either way) -- off
-  bool tally_strand_split = true;          // position-specific matrices: a workgroup's reads all of one strand, sorted by start (round 5; MIA_HIP_STRAND_SPLIT=0: round 4's tally)
-  bool tally_rall = true;                  // reads of 129 .. 256 bases: every row through the runs (MIA_HIP_NO_TALLY_RALL=1: round 4's tally for them)
-  bool tally_runs = true;                  // ... and the rows at either end of a read reduced over runs of equal starts (MIA_HIP_NO_TALLY_RUNS=1: per read)
+  bool tally_defer = true;                 // ... false: they are taken inside k_tally_binned, one per wavefront
+  // position-specific matrices: a workgroup's reads all of one strand, sorted by start (round 5).  Measured against round 4's tally:
+  // configs[2] 1.313 -> 1.306 ms, configs[4] at 5 M reads 9.91 -> 10.2 ms (twice the part-filled workgroups and slabs; the end rows'
+  // packed atomics are what the kernel waits for either way)
+  bool tally_strand_split = true;
+  bool tally_rall = true;                  // reads of 129 .. 256 bases: every row through the runs
+  bool tally_runs = true;                  // ... and the rows at either end of a read reduced over runs of equal starts
   int32_t* d_order2 = nullptr; uint8_t* d_okey = nullptr; int32_t* d_sort2 = nullptr; int64_t sort2_cap = 0;      // the reads of every bucket by start; histogram + cursors of that sort
-  int tally_chunk_linear = TALLY_CHUNK_LINEAR;                    // MIA_HIP_TALLY_CHUNK=256|512|768 (alt build)
-  bool tally_defer = true;                                        // MIA_HIP_TALLY_INLINE=1 (alt build): they are taken inside k_tally_binned, one per wavefront
-  // wide scratch
-  int32_t* d_scratch = nullptr; int64_t scratch_cap = 0; int64_t* d_scratch_off = nullptr; int64_t scratch_off_cap = 0;
-  // timing
-  // HIP-event timers of the kernels bench.py reports, one per stage (mia_hip_stage_stats); pairs are recycled through ev_free
-  struct StageTimer { std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; int64_t launches = 0; };
-  StageTimer stg[STG_COUNT];
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
-  // pinned staging: small copies to and from pageable memory wait for the stream, pinned ones do not
-  unsigned char* h_pin = nullptr; static constexpr size_t PIN_BYTES = 1 << 20, PIN_MISC = 64 << 10;
-  double pass1_ms = 0; int64_t pass1_filtered = 0, pass1_anchored = 0;   // reads of the last pass-1 call that the diagonal filter decided
-  bool consensus_done = false;
-  // mia_hip_iterate: one iteration with the planner's answers, the cut line and the insert-event count left on the device
-  bool deferred = false;                    // align_all: no host round trip before its end
+
+  // ---- iterate: one iteration with the planner's answers, the cut line and the insert-event count left on the device ------------
   bool in_iterate = false;                  // the control block was cleared as a whole by the alignment's one memset
-  int32_t* d_plan_hdr = nullptr;            // PH_* (k_plan_scan)
+  // no host wait behind the alignment: cull, tally and consensus are queued at once and every one of their kernels returns at its
+  // first instruction if *abort_if != 0 (reads are waiting for the exact one-read-per-thread kernel: the host sees that with the
+  // consensus, runs it, and queues the chain again)
+  const int32_t* abort_if = nullptr;
+  bool spec_ok = false, spec_pending = false, spec_filtered = false, spec_bx = false, spec_plain = false;
+  int64_t spec_redone = 0;                  // iterations whose cull / tally / consensus were queued twice (reads for the exact kernel)
+  bool no_spec = false;
+  bool spec_force = false; int32_t* d_one = nullptr;      // (tests) every iteration takes the second round; a word that holds 1
+  bool pend_encode = false; int32_t pend_L = 0, pend_wl = 0, pend_total = 0;      // d_ascii holds the new reference, d_ref not yet
+  bool zero_copy = true;                   // the last kernel writes consensus and counters into pinned host memory itself
   const double* dev_cut = nullptr; double* d_cut_buf = nullptr;
-  int min_len = 0;                          // shortest stored read
-  std::vector<int32_t> h_len;               // read lengths on the host (the score-cut regression of reads of different lengths)
   char* d_ascii = nullptr; int64_t ascii_cap = 0; const char* ascii_src = nullptr;     // ascii_src: where the pending reference is read from (d_ascii, or the pinned staging area)
   char* d_cons = nullptr; int64_t cons_cap = 0;              // result of an iteration: [CH_WORDS header][consensus string]
   int32_t* d_cons_pos = nullptr; int64_t cons_pos_cap = 0;
   unsigned char* h_pin2 = nullptr; size_t pin2_bytes = 0;   // results of an iteration (header + consensus string)
   int64_t iter_fallbacks = 0;
-  // sharded runs: one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
-  // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream
+
+  // ---- one-off calls: pass 1, Myers, trimming ---------------------------------------------------------------------------------
+  double pass1_ms = 0; int64_t pass1_filtered = 0, pass1_anchored = 0;   // reads of the last pass-1 call that the diagonal filter decided
+  double myers_kernel_ms = 0; bool myers_no_lanes = false, myers_no_ond = false;   // the kernels of the last mia_hip_myers call (HIP events)
+  int64_t trim_escapes = 0;   // reads of the last mia_hip_trim call that took the exact scalar path
+
+  // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
+  // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------
   mia_hip_collectives coll{}; bool comm = false; int comm_ranks = 1, comm_rank = 0; std::string coll_name;
   unsigned long long* d_gather = nullptr;   // [PRE_WORDS * ranks] score sums, record, link and exact-kernel counts of every rank
   std::vector<int64_t> h_gather;            // ... on the host, once the alignment's one wait is over
@@ -258,9 +250,51 @@ struct mia_hip_ctx {
   int64_t* d_lmine = nullptr; int64_t lmine_cap = 0;
   int64_t* d_lall = nullptr; int64_t lall_cap = 0;
   int32_t* d_scores_all = nullptr; int64_t scores_all_cap = 0;
-  int64_t trim_escapes = 0;   // reads of the last mia_hip_trim call that took the exact scalar path
-  int64_t ins_total_host = 0;
 };
+
+// The alternative routes and diagnostics of libmia_hip_alt.so (alt_env reads nothing in the release build), one line each.  The rest
+// are read where they apply: MIA_HIP_ITER_DEBUG and MIA_HIP_EV_PAD (mia_hip_iterate), MIA_HIP_P1_TIMING / _CPL / _PLAIN
+// (mia_hip_pass1), MIA_HIP_PEAK_DEBUG (mia_hip_peak).
+static void read_alt_switches(mia_hip_ctx* ctx) {
+  auto on = [](const char* name) { const char* v = alt_env(name); return v && atoi(v) != 0; };
+  // alignment: which kernels take the reads
+  if (on("MIA_HIP_NO_DIAG_FILTER")) { ctx->use_filter = 0; ctx->use_bx = 0; }      // every shortcut off: the full-window DP kernels only
+  if (on("MIA_HIP_NO_BAND_DP")) { ctx->use_banddp = 0; ctx->use_bx = 0; }          // flat matrix: the filter's left-overs go straight to the full-window kernels
+  if (on("MIA_HIP_NO_BANDX")) ctx->use_bx = 0;                 // the round-1 path (flat: filter + k_band_align; PSSM: full-window kernels)
+  if (on("MIA_HIP_NO_LANES")) ctx->use_lanes = 0;              // the band DPs one read per lane (k_bx_values / k_bx_trace) instead of W/8 lanes per read
+  if (on("MIA_HIP_BX_SERIAL")) ctx->bx_serial = true;          // round 2's order: band kernels, then the planner over everything they left open
+  if (on("MIA_HIP_NO_PLAN_SPLIT")) ctx->plan_split = false;    // k_bx_plan in one launch
+  if (on("MIA_HIP_NO_FINE")) ctx->use_fine = 0;                // no third launch of the plan (fine blocks)
+  if (const char* v = alt_env("MIA_HIP_FINE")) ctx->use_fine = atoi(v);            // 2: the third launch in every iteration
+  if (on("MIA_HIP_NO_QUICK_PLAN")) ctx->use_quick = 0;         // the full plan for every read
+  if (const char* v = alt_env("MIA_HIP_QUICK_PLAN")) ctx->use_quick = atoi(v);     // 2: the quick plan also where align_all's size rule says no
+  if (on("MIA_HIP_NO_DIRECT_OPEN")) ctx->use_direct_open = false;                  // open reads through the planner's count / scan / fill and the quad kernels
+  if (on("MIA_HIP_NO_PREP_FUSE")) ctx->no_prep_fuse = true;    // six launches instead of k_ref_prep
+  // mia_hip_iterate: what is queued when
+  if (on("MIA_HIP_NO_SPEC")) ctx->no_spec = true;              // wait for the alignment's counters before the cull is queued
+  if (on("MIA_HIP_SPEC_TEST")) ctx->spec_force = true;         // every iteration queues cull / tally / consensus twice
+  if (on("MIA_HIP_NO_SIDE_BUCKETS")) ctx->no_side_buckets = true;                  // the tally's counting sort behind the cull, not beside it
+  if (on("MIA_HIP_NO_ZERO_COPY")) ctx->zero_copy = false;      // consensus and counters by two copies
+  if (on("MIA_HIP_NO_EXT_EVENTS")) ctx->ext_events = 0u;       // marker events behind the launches other streams wait for
+  if (on("MIA_HIP_FAKE_EVENT_OVERFLOW")) ctx->fake_event_overflow = true;          // (tests) this rank pretends its insert-event list overflowed
+  // cull and tally
+  if (on("MIA_HIP_CULL_SCAN")) ctx->cull_scan = true;          // the slot scan as a kernel of its own (k_scan_partials)
+  if (on("MIA_HIP_TAIL_SCANS")) ctx->tail_scans = true;        // the consensus tail's scans as single-workgroup kernels of their own
+  if (on("MIA_HIP_NO_CULL_RECORDS")) ctx->cull_with_records = false;               // k_rec_params writes every tally record
+  if (on("MIA_HIP_NO_BINNED_TALLY")) ctx->use_binned_tally = 0;                    // plain global-atomic tally
+  if (on("MIA_HIP_NO_LINEAR_TALLY")) ctx->no_linear_tally = true;                // the tally adds the four scores of every base even where counting would do
+  if (on("MIA_HIP_SORT2_UNPACKED")) ctx->sort2_unpacked = true;                  // the second sort's key in a byte array beside the entries, as from 2^24 reads
+  if (on("MIA_HIP_TALLY_INLINE")) ctx->tally_defer = false;    // gapped reads inside k_tally_binned, one per wavefront
+  if (const char* v = alt_env("MIA_HIP_STRAND_SPLIT")) ctx->tally_strand_split = atoi(v) != 0;      // 0: round 4's tally for position-specific matrices
+  if (on("MIA_HIP_NO_TALLY_RUNS")) ctx->tally_runs = false;    // end rows per read, not per run of equal starts
+  if (on("MIA_HIP_NO_TALLY_RALL")) ctx->tally_rall = false;    // round 4's tally for reads of 129 .. 256 bases
+  // Myers
+  if (on("MIA_HIP_MYERS_NO_LANES")) ctx->myers_no_lanes = true;                    // every pair through k_myers
+  if (on("MIA_HIP_MYERS_NO_OND")) ctx->myers_no_ond = true;    // no O(ND) kernel
+  // profiling: results are wrong on purpose
+  if (const char* v = alt_env("MIA_HIP_DEBUG_SKIP")) ctx->dbg = (uint32_t)atoi(v);                  // bits: see the kernels' dbg tests
+  if (const char* v = alt_env("MIA_HIP_BX_DEBUG")) ctx->bx_dbg = (uint32_t)atoi(v);                 // 1 no traceback, 2 one DP row, 4 no values launch, 8 no trace launch, ...
+}
 
 #define HIPCHK(call)                                                                                   \
   do {                                                                                                 \
@@ -341,14 +375,10 @@ extern "C" int mia_hip_create(mia_hip_ctx** out, int device_index) {
   if (device_index < 0 || device_index >= ndev) return MIA_HIP_ERR_ARG;
   mia_hip_ctx* ctx = new mia_hip_ctx();
   ctx->device = device_index;
-  // the events order kernels of this context's streams on this device and nothing else (MIA_HIP_EVENT_DEVICE_SCOPE=1: say so)
-  unsigned evf = hipEventDisableTiming;
-  if (const char* es = alt_env("MIA_HIP_EVENT_DEVICE_SCOPE")) if (atoi(es)) evf |= hipEventReleaseToDevice;
+  const unsigned evf = hipEventDisableTiming;
   if (hipSetDevice(device_index) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_join3, evf) != hipSuccess ||
-      hipStreamCreateWithFlags(&ctx->stream4, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_early, evf) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_snap, evf) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_v1, evf) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_fork, evf) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_join, evf) != hipSuccess) {
     delete ctx;
     return MIA_HIP_ERR_DEVICE;
@@ -360,68 +390,8 @@ extern "C" int mia_hip_create(mia_hip_ctx** out, int device_index) {
     ctx->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
     ctx->grid_wgs = prop.multiProcessorCount * 32;
     ctx->quad_wgs = prop.multiProcessorCount * 16;   // 128 VGPRs -> 4 waves per SIMD
-    const char* nbt = alt_env("MIA_HIP_NO_BINNED_TALLY");
-    if (nbt && atoi(nbt)) ctx->use_binned_tally = 0;
-    const char* nband = alt_env("MIA_HIP_NO_BAND");
-    if (nband && atoi(nband)) ctx->use_band = 0;
-    const char* npl = alt_env("MIA_HIP_NO_PLAIN");
-    if (npl && atoi(npl)) ctx->use_plain = 0;
-    const char* pbb = alt_env("MIA_HIP_PLAIN_BEHIND_BAND");
-    if (pbb && atoi(pbb)) ctx->plain_behind_band = 1;
-    const char* nf = alt_env("MIA_HIP_NO_DIAG_FILTER");
-    if (nf && atoi(nf)) { ctx->use_filter = 0; ctx->use_bx = 0; }      // every shortcut off: the full-window DP kernels only
-    const char* nbd = alt_env("MIA_HIP_NO_BAND_DP");
-    if (nbd && atoi(nbd)) { ctx->use_banddp = 0; ctx->use_bx = 0; }
-    const char* nbx = alt_env("MIA_HIP_NO_BANDX");
-    if (nbx && atoi(nbx)) ctx->use_bx = 0;
-    if (const char* nl2 = alt_env("MIA_HIP_NO_LANES")) if (atoi(nl2)) ctx->use_lanes = 0;
-    if (const char* bd2 = alt_env("MIA_HIP_BX_DEBUG")) ctx->bx_dbg = (uint32_t)atoi(bd2);
-    if (const char* bs2 = alt_env("MIA_HIP_BX_SERIAL")) ctx->bx_serial = atoi(bs2) != 0;
-    if (const char* sb2 = alt_env("MIA_HIP_NO_SIDE_BUCKETS")) ctx->no_side_buckets = atoi(sb2) != 0;
-    if (const char* ns2 = alt_env("MIA_HIP_NO_SPEC")) ctx->no_spec = atoi(ns2) != 0;
-    if (const char* pf2 = alt_env("MIA_HIP_NO_PREP_FUSE")) ctx->no_prep_fuse = atoi(pf2) != 0;
-    if (const char* ps2 = alt_env("MIA_HIP_NO_PLAN_SPLIT")) ctx->plan_split = atoi(ps2) == 0;
-    if (const char* zc = alt_env("MIA_HIP_NO_ZERO_COPY")) ctx->zero_copy = atoi(zc) == 0;
-    if (const char* ef = alt_env("MIA_HIP_NO_EXT_EVENTS")) ctx->ext_events = atoi(ef) ? 0u : 31u;
-    if (const char* cs = alt_env("MIA_HIP_CULL_SCAN")) ctx->cull_scan = atoi(cs) != 0;
-    if (const char* sm = alt_env("MIA_HIP_STAGE_MARKERS")) ctx->stage_markers = atoi(sm) != 0;
-    if (const char* ts = alt_env("MIA_HIP_TAIL_SCANS")) ctx->tail_scans = atoi(ts) != 0;
-    if (const char* dop = alt_env("MIA_HIP_NO_DIRECT_OPEN")) ctx->use_direct_open = atoi(dop) == 0;
-    if (const char* qp = alt_env("MIA_HIP_NO_QUICK_PLAN")) ctx->use_quick = atoi(qp) == 0 ? 1 : 0;
-    if (const char* qp = alt_env("MIA_HIP_QUICK_PLAN")) ctx->use_quick = atoi(qp);      // (2: also where the size rule below says no)
+    read_alt_switches(ctx);
     if (const char* sw = getenv("MIA_HIP_SPIN_WAIT")) ctx->spin_wait = atoi(sw) != 0;
-    if (const char* em = alt_env("MIA_HIP_EXT_EVENTS_MASK")) ctx->ext_events = (uint32_t)atoi(em);
-    if (const char* st2 = alt_env("MIA_HIP_SPEC_TEST")) ctx->spec_force = atoi(st2) != 0;
-    if (const char* ml = alt_env("MIA_HIP_MYERS_NO_LANES")) ctx->myers_no_lanes = atoi(ml) != 0;
-    if (const char* mo = alt_env("MIA_HIP_MYERS_NO_OND")) ctx->myers_no_ond = atoi(mo) != 0;
-    if (const char* fo = alt_env("MIA_HIP_FAKE_EVENT_OVERFLOW")) ctx->fake_event_overflow = atoi(fo) != 0;
-    if (const char* na = alt_env("MIA_HIP_NO_AUTO_PLAIN")) ctx->no_auto_plain = atoi(na) != 0;
-    const char* egs = alt_env("MIA_HIP_EAGER_SCRIPTS");
-    if (egs && atoi(egs)) ctx->lazy_scripts = 0;
-    const char* nwl = alt_env("MIA_HIP_NO_WILD");
-    if (nwl && atoi(nwl)) ctx->use_wild = 0;
-    if (const char* ne = alt_env("MIA_HIP_EARLY_TALLY")) ctx->use_early = atoi(ne) != 0;
-    if (const char* ti = alt_env("MIA_HIP_TALLY_INLINE")) ctx->tally_defer = atoi(ti) == 0;
-    if (const char* ss = alt_env("MIA_HIP_STRAND_SPLIT")) ctx->tally_strand_split = atoi(ss) != 0;
-    if (const char* nr = alt_env("MIA_HIP_NO_TALLY_RUNS")) ctx->tally_runs = atoi(nr) == 0;
-    if (const char* sd = alt_env("MIA_HIP_SPLIT_DP")) ctx->split_dp_mode = atoi(sd) != 0 ? 1 : -1;
-    if (const char* ra = alt_env("MIA_HIP_NO_TALLY_RALL")) ctx->tally_rall = atoi(ra) == 0;
-    if (const char* cr = alt_env("MIA_HIP_NO_CULL_RECORDS")) ctx->cull_with_records = atoi(cr) == 0;
-    if (const char* tc = alt_env("MIA_HIP_TALLY_CHUNK")) { const int c = atoi(tc); if (c == 256 || c == 512 || c == 768) ctx->tally_chunk_linear = c; }
-    if (const char* ew = alt_env("MIA_HIP_EARLY_WGS")) ctx->early_wgs_per_cu = atoi(ew);
-    if (const char* nf = alt_env("MIA_HIP_NO_FINE")) ctx->use_fine = atoi(nf) == 0 ? 1 : 0;
-    if (const char* nf = alt_env("MIA_HIP_FINE")) ctx->use_fine = atoi(nf);
-    if (const char* pb = alt_env("MIA_HIP_PLANNER_BESIDE")) ctx->planner_beside = atoi(pb) != 0;
-    const char* bxf = alt_env("MIA_HIP_BX_FILTER");
-    if (bxf && atoi(bxf)) ctx->bx_filter_first = 1;
-    const char* nq = alt_env("MIA_HIP_NO_QUAD");
-    if (nq && atoi(nq)) ctx->use_quad = 0;
-    const char* qw = alt_env("MIA_HIP_QUAD_WAVES_PER_CU");
-    if (qw && atoi(qw) > 0) ctx->quad_wgs = prop.multiProcessorCount * atoi(qw);
-    const char* dbg = alt_env("MIA_HIP_DEBUG_SKIP");
-    if (dbg) ctx->dbg = (uint32_t)atoi(dbg);
-    const char* g = alt_env("MIA_HIP_GRID_WAVES_PER_CU");
-    if (g && atoi(g) > 0) ctx->grid_wgs = prop.multiProcessorCount * atoi(g);
   }
   if (dev_alloc(ctx, &ctx->d_pssm, 2 * PSSM_WORDS) || dev_alloc(ctx, &ctx->d_ctrl, CTRL_WORDS) ||
       dev_alloc(ctx, &ctx->d_total, 1) || dev_alloc(ctx, &ctx->d_ins_total, 1) ||
@@ -477,13 +447,7 @@ extern "C" void mia_hip_destroy(mia_hip_ctx* ctx) {
   (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
-  if (ctx->stream4) (void)hipStreamDestroy(ctx->stream4);
-  if (ctx->ev_early) (void)hipEventDestroy(ctx->ev_early);
-  if (ctx->ev_snap) (void)hipEventDestroy(ctx->ev_snap);
-  if (ctx->ev_v1) (void)hipEventDestroy(ctx->ev_v1);
-  if (ctx->d_bx_snap) (void)hipFree(ctx->d_bx_snap);
   if (ctx->d_gen_list) (void)hipFree(ctx->d_gen_list);
-  for (void* p : {(void*)ctx->d_early, (void*)ctx->d_trec_early, (void*)ctx->d_order_e, (void*)ctx->d_fix_list, (void*)ctx->d_bucket_e, (void*)ctx->d_tally_slabs_e}) if (p) (void)hipFree(p);
   if (ctx->ev_join3) (void)hipEventDestroy(ctx->ev_join3);
   if (ctx->d_retry2) (void)hipFree(ctx->d_retry2);
   if (ctx->d_cull_sync) (void)hipFree(ctx->d_cull_sync);
@@ -523,7 +487,7 @@ extern "C" int mia_hip_set_pssm(mia_hip_ctx* ctx, const int32_t* fwd, const int3
   {
     int lo = 0, hi = 0;
     for (int k = 0; k < PSSM_WORDS; k++) { lo = std::min(lo, std::min((int)fwd[k], (int)rc[k])); hi = std::max(hi, std::max((int)fwd[k], (int)rc[k])); }
-    ctx->tally_pk_bias = (-lo + hi <= 2047 && !alt_env("MIA_HIP_NO_PACKED_TALLY")) ? -lo : -1;
+    ctx->tally_pk_bias = -lo + hi <= 2047 ? -lo : -1;
   }
   ctx->max_pos = 0;
   for (int i = 0; i < PSSM_WORDS; i++) { if (fwd[i] > ctx->max_pos) ctx->max_pos = fwd[i]; if (rc[i] > ctx->max_pos) ctx->max_pos = rc[i]; }
@@ -541,7 +505,7 @@ extern "C" int mia_hip_set_pssm(mia_hip_ctx* ctx, const int32_t* fwd, const int3
     for (int x = 0; x < 4; x++)
       for (int b = 0; b < 5; b++)
         if (fwd[(d * 5 + x) * 5 + b] != fwd[x * 5 + b] || rc[(d * 5 + x) * 5 + b] != fwd[x * 5 + b]) ctx->tally_linear = false;
-  if (const char* nl = alt_env("MIA_HIP_NO_LINEAR_TALLY")) if (atoi(nl)) ctx->tally_linear = false;
+  if (ctx->no_linear_tally) ctx->tally_linear = false;
   // tables of the band pipeline (bandx_body.h): substitution scores by (strand, depth, read base, reference code), the best
   // score of every row kind, and what a non-identical base costs at least
   {
@@ -722,12 +686,12 @@ static void stage_end(mia_hip_ctx* ctx, Stage st, hipStream_t on = nullptr) {
 
 // One launch of a timed stage whose kernel carries no event for another stream: the event pair rides on the launch itself
 // (start and end of that dispatch, no marker packets in front of and behind the kernel -- on the critical path those cost
-// the step 10-20 us each, and the timed region of bench.py times the dominant stage in every step); MIA_HIP_STAGE_MARKERS=1
-// or an untimed stage: the launch as it is, between stage_begin / stage_end.
+// the step 10-20 us each, and the timed region of bench.py times the dominant stage in every step); an untimed stage: the
+// launch as it is, between stage_begin / stage_end.
 template <typename... KArgs, typename... Args>
 static int stage_launch(mia_hip_ctx* ctx, Stage st, void (*kernel)(KArgs...), dim3 g, dim3 b, size_t shm, hipStream_t s, Args&&... args) {
   static_assert(sizeof...(KArgs) == sizeof...(Args), "every kernel argument, defaults included");
-  if (!((ctx->stage_mask >> st) & 1u) || ctx->stage_markers) {
+  if (!((ctx->stage_mask >> st) & 1u)) {
     if (stage_begin(ctx, st, s)) return -1;
     hipLaunchKernelGGL(kernel, g, b, shm, s, static_cast<KArgs>(args)...);
     stage_end(ctx, st, s);
@@ -879,7 +843,7 @@ static hipError_t launch_window(mia_hip_ctx* ctx, int ci, const int32_t* list, i
     int occ = 0;
     const int cus = ctx->cus;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)k_align_window<CPL>, 64, 0) != hipSuccess || occ < 1) occ = 1;
-    const int per_cu = ctx->grid_wgs / cus;      // the configured ceiling (MIA_HIP_GRID_WAVES_PER_CU)
+    const int per_cu = ctx->grid_wgs / cus;      // the persistent grid's ceiling
     ctx->window_wgs[ci] = cus * (occ < per_cu ? occ : per_cu);
   }
   int grid = (dev_range || count >= ctx->window_wgs[ci]) ? ctx->window_wgs[ci] : count;   // (a count on the device: the whole persistent grid)
@@ -946,7 +910,6 @@ static int bx_join_and_retry(mia_hip_ctx* ctx) {
 }
 
 static int align_all(mia_hip_ctx* ctx);
-static int early_tally_launch(mia_hip_ctx* ctx);
 static bool tally_is_binned(const mia_hip_ctx* ctx);
 static int comm_pre_cull_enqueue(mia_hip_ctx* ctx, const int32_t* d_wide_count);
 static bool comm_pre_cull_collect(mia_hip_ctx* ctx);
@@ -965,7 +928,7 @@ extern "C" int mia_hip_realign(mia_hip_ctx* ctx, const char* new_ref, int32_t re
   ctx->ref_mostly_bases = n_other * 50 <= L;
   ctx->ref_few_n = n_other * 500 <= L;
   ctx->kh_entries = 0;
-  if (n_other && ctx->use_wild) {
+  if (n_other) {
     ctx->kh_entries = kh_wild_entries(codes.data(), wrap, BX_WILD);
     if (ctx->kh_entries > ((int64_t)1 << 24)) ctx->kh_entries = 0;
   }
@@ -1064,7 +1027,6 @@ static int align_all(mia_hip_ctx* ctx) {
   ctx->bx_planner_aside = false;
   ctx->planner_end_signalled = false; ctx->align_end_signalled = false;
   ctx->buckets_queued = 0;                  // (a counting sort queued for an earlier alignment is void)
-  ctx->early_queued = false;
   if (n == 0) { ctx->aligned = true; return MIA_HIP_OK; }
   RefInfo ref{ctx->d_ref, ctx->L, wrap, ctx->explicit_win};
   int32_t* d_count = ctx->d_bins;
@@ -1076,9 +1038,9 @@ static int align_all(mia_hip_ctx* ctx) {
   const int filter_ok = ctx->flat && ctx->use_filter && ctx->ref_mostly_bases;
   // the band pipeline for any matrix (bandx_kernels.h); it needs the 10-mer table and windows free of N
   const bool bx = ctx->bx_ok && ctx->use_bx && (ctx->ref_mostly_bases || ctx->kh_entries > 0) && wrap <= (1 << 22) && !(ctx->dbg & 128u);
-  const bool run_filter = filter_ok && (!bx || ctx->bx_filter_first);
+  const bool run_filter = filter_ok && !bx;
   // mia_hip_iterate with the band pipeline alone: codes, control block, planes, nibbles and 10-mer table in one launch (k_ref_prep)
-  const bool fused_prep = ctx->pend_encode && bx && !run_filter && !ctx->no_prep_fuse;
+  const bool fused_prep = ctx->pend_encode && bx && !ctx->no_prep_fuse;
   if (!fused_prep) {
     encode_now(ctx);
     HIPCHK(hipMemsetAsync(ctx->d_ctrl, 0, (size_t)CTRL_WORDS * 4, ctx->stream));     // every counter of the iteration at once
@@ -1102,7 +1064,7 @@ static int align_all(mia_hip_ctx* ctx) {
     // the 10-mer table of this reference (rule (c) looks long clean stretches up instead of sliding over every diagonal;
     // the band plans are made of its anchors); not for the very long concatenated strings mia_hip_align_windows may be given
     KmerOcc ko{nullptr, nullptr};
-    if (wrap <= (1 << 22) && (run_filter || !bx)) {
+    if (wrap <= (1 << 22) && !bx) {
       if (!ctx->d_kocc_cnt && (dev_alloc(ctx, &ctx->d_kocc_cnt, (size_t)DF_KTAB) || dev_alloc(ctx, &ctx->d_kocc_pos, (size_t)DF_KTAB * DF_KCAP)))
         return MIA_HIP_ERR_NOMEM;
       HIPCHK(hipMemsetAsync(ctx->d_kocc_cnt, 0, (size_t)DF_KTAB * 4, ctx->stream));
@@ -1179,9 +1141,6 @@ static int align_all(mia_hip_ctx* ctx) {
         ctx->bx_values_wgs = ctx->cus * std::min(occ, 4);
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ctx->use_lanes ? (const void*)k_bxl_trace : ALT_KERNEL(k_bx_trace), 256, 0) != hipSuccess || occ < 1) occ = 1;
         ctx->bx_trace_wgs = ctx->cus * std::min(occ, 4);      // (every wavefront of the trace grid owns a slab)
-        // (alt build, percent of the above: how much room the persistent grids leave the planner's chain)
-        if (const char* pv = alt_env("MIA_HIP_BX_VALUES_PCT")) if (atoi(pv) > 0) ctx->bx_values_wgs = std::max(1, ctx->bx_values_wgs * atoi(pv) / 100);
-        if (const char* pt = alt_env("MIA_HIP_BX_TRACE_PCT")) if (atoi(pt) > 0) ctx->bx_trace_wgs = std::max(1, ctx->bx_trace_wgs * atoi(pt) / 100);
       }
       // (the lanes kernels store four rows per word: whole blocks of four rows)
       const int64_t slab_words = ctx->use_lanes ? (int64_t)((ctx->max_len + 3) & ~3) * BXL_SLAB_ROW_WORDS : (int64_t)ctx->max_len * BX_SLAB_ROW_WORDS;
@@ -1191,7 +1150,6 @@ static int align_all(mia_hip_ctx* ctx) {
       }
       BxDev bd;
       bd.tab.sub = ctx->d_bx_sub; bd.tab.mrow = ctx->d_bx_mrow; bd.tab.loss = ctx->d_bx_loss; bd.tab.dl = ctx->d_bx_dl;
-      bd.lazy_scripts = ctx->lazy_scripts;
       bd.dbg = ctx->bx_dbg & (3u | 32u | 64u | 128u | 512u);
       // MIA_HIP_BX_SERIAL=1: round 2's order (band kernels, then the planner over everything they left open)
       // (caller-supplied windows -- mia_hip_align_windows -- can be of any length: the retry list's window kernel is picked by read length)
@@ -1207,7 +1165,7 @@ static int align_all(mia_hip_ctx* ctx) {
       }
       bd.retry = ctx->d_retry2; bd.retry_n = ctx->d_plan_hdr + PH_RETRY2 + 1;
       bd.listed_mark = new_flow ? -5 : 0;
-      if (ctx->lazy_scripts) ctx->diag_scripts_missing = true;
+      ctx->diag_scripts_missing = true;         // (the scripts of reads finished as pure diagonals: k_diag_scripts makes them when asked for)
       bd.tab.min_m = ctx->bx_min_m; bd.tab.max_m = ctx->bx_max_m;
       bd.tab.maxw = ctx->use_lanes ? BX_MAXW : 32;           // (the widest class needs a read spread over eight lanes)
       bd.sub256 = ctx->d_bx_sub + BX_SUB_WORDS;
@@ -1256,16 +1214,16 @@ static int align_all(mia_hip_ctx* ctx) {
       {
         int64_t lr = 0;
         for (int k = 1; k < BXF_KINDS; k++) lr += ctx->bx_last[BXC_FAIL0 + k];
-        const bool many_early = !ctx->no_auto_plain && (!ctx->ref_mostly_bases || lr * 20 > n);
-        planner_head_first = new_flow && ctx->deferred && many_early && !ctx->planner_beside && !(ctx->dbg & 256u);
+        const bool many_early = !ctx->ref_mostly_bases || lr * 20 > n;
+        planner_head_first = new_flow && ctx->deferred && many_early && !(ctx->dbg & 256u);
         // DIRECT OPEN LIST (round 6).  At steady state the plan leaves a few hundred reads per million open.  For their sake the planner
         // counted, scanned and filled over ALL reads (three launches beside the persistent band grids: 13 + 7 + 71 us), a quad kernel took
         // them four to a wavefront (110 us: one quad's latency), three window-class launches and a retry launch followed -- nine launches,
         // 270 us, the longest of the step's three DP chains.  Now the plan appends such a read to a list as it gives up on it and
         // k_align_open takes the list, one read per wavefront (90-115 us beside the band DPs, 35 on an idle chip: off the step's chain either way).  Where the plan gives up on MANY reads (the values-only quad pass is on:
         // every run's first iteration, N-rich references) the planner and the quad kernels stay: four reads per wavefront is what pays there.
-        const bool plain_wanted = ctx->use_plain && (ctx->plain_behind_band || many_early);      // (= use_plain below, the band pipeline being on)
-        direct_open = new_flow && ctx->deferred && ctx->use_direct_open && !plain_wanted && !planner_head_first && !run_filter && !(ctx->dbg & 256u) &&
+        const bool plain_wanted = many_early;      // (= use_plain below, the band pipeline being on)
+        direct_open = new_flow && ctx->deferred && ctx->use_direct_open && !plain_wanted && !planner_head_first && !(ctx->dbg & 256u) &&
                       !(ctx->bx_dbg & (4u | 8u));
       }
       bd.open = nullptr; bd.open_n = ctx->d_bx_ctr + (size_t)BXC_OPEN * BXC_STRIDE;
@@ -1276,44 +1234,17 @@ static int align_all(mia_hip_ctx* ctx) {
         bd.open = ctx->d_open_list;
         ctx->direct_open_steps++;
       }
-      // the early tally (k_rec_early): the plan marks the reads it finishes, their tally runs on stream4 beside the band DPs.  Only in
-      // mia_hip_iterate (the whole step is queued at once), for read sets small enough that the step is a chain of latencies.
-      const bool early = ctx->deferred && new_flow && ctx->use_early && !run_filter && tally_is_binned(ctx) && n <= 4000000;
-      bd.early = nullptr;
-      if (early) {
-        if (n > ctx->early_cap) {
-          if (dev_alloc(ctx, &ctx->d_early, (size_t)n) || dev_alloc(ctx, &ctx->d_trec_early, (size_t)n * 16) || dev_alloc(ctx, &ctx->d_order_e, (size_t)n) ||
-              dev_alloc(ctx, &ctx->d_fix_list, (size_t)n)) return MIA_HIP_ERR_NOMEM;
-          ctx->early_cap = n;
-        }
-        bd.early = ctx->d_early;
-      }
       // ... and where the plan's third launch is off (flat matrix, a million reads, hardly any rejects: the step is a chain of
       // latencies) the widest class is not used at all: those few reads keep going to the full-window kernels on the planner's stream,
       // whose chain is as long with them as without (measured: 0.960 against 0.944 ms per step with the class in use)
       if (!fine && ctx->use_fine < 2) bd.tab.maxw = 32;
-      // THE BAND DPs IN TWO ROUNDS (MIA_HIP_SPLIT_DP=1, alt build).  Where the plan gives up on many reads (every run's
-      // first iteration: a reference full of ambiguity codes) its second and third launch are long -- 0.5 + 1.7 ms of 10 M solexa reads,
-      // behind 3.1 ms of the first -- and the band DPs wait for all three.  Nine lists in ten are complete after the first launch:
-      // k_bx_snap notes their lengths, the DPs of those entries start at once (values DP on stream4, trace DP on stream3) beside the other
-      // two launches, and a second round behind the last launch takes what they appended.  MEASURED, NO GAIN: first iteration of 10 M
-      // solexa reads 17.13 ms with it, 16.90 without; 1 M flat reads 1.90 / 1.83 -- the plan's launches and the DPs are all bound by
-      // vector issue, and what runs side by side only shares the chip.  Kept behind the switch (tests/test_gpu_switches.py runs it).
-      const bool split_dp = new_flow && ctx->deferred && split && last_phase >= 2 && !early && !(ctx->bx_dbg & (4u | 8u)) && ctx->split_dp_mode > 0;
-      bd.snap = nullptr;
-      if (split_dp) {
-        if (!ctx->d_bx_snap && dev_alloc(ctx, &ctx->d_bx_snap, (size_t)(2 * BX_NCLS))) return MIA_HIP_ERR_NOMEM;
-        bd.snap = ctx->d_bx_snap;
-        ctx->split_dp_steps++;
-      }
       // THE QUICK PLAN FIRST (round 6; bandx_body.h: bx_quick, k_bx_plan<NW, 4>): every read on the diagonal it was aligned on before -- nine
       // in ten of a steady-state iteration are finished or listed there for a tenth of the full plan's instructions; the rest goes on a
       // list (the diagonal filter's: d_left_list, d_filter_n[1]) that the launches below take as their in_list.  Not against a reference
-      // that is N all over (every run's first iteration; one with a few N columns: the windows that hold none, want_bits above), not with the
-      // diagonal filter in front, not with the early tally's marks.
+      // that is N all over (every run's first iteration; one with a few N columns: the windows that hold none, want_bits above).
       // (... and with the fine blocks on only from two million reads: the three launches of the full plan stay behind it then, each with a
       // launch's floor of 30-90 us for the few reads it has left -- 1 M ancient reads 1.12 ms without it, 1.15 with; 10 M solexa 6.0 / 5.4)
-      const bool quick = split && new_flow && !run_filter && !early && !split_dp && want_bits && !(ctx->bx_dbg & 32u) && bd.umax != nullptr &&      // (the context's own reads: their U is at hand)
+      const bool quick = split && new_flow && want_bits && !(ctx->bx_dbg & 32u) && bd.umax != nullptr &&      // (the context's own reads: their U is at hand)
                          (!fine || n >= 2000000 || ctx->use_quick > 1);
       bd.qlist = nullptr; bd.qlist_n = ctx->d_filter_n + 1; bd.mark_all = 0; bd.to_late = 0; bd.qch = 4;
       // mia_hip_iterate: the fork is behind the QUICK plan (BxDev::to_late) -- values DP and late trace are on the context's stream there, behind
@@ -1334,7 +1265,7 @@ static int align_all(mia_hip_ctx* ctx) {
       }
       if (stage_begin(ctx, STG_BX_PLAN)) return MIA_HIP_ERR_NOMEM;
       {
-        const int32_t* in_list = (run_filter || quick) ? ctx->d_left_list : nullptr;
+        const int32_t* in_list = quick ? ctx->d_left_list : nullptr;
         const dim3 pb(256);
         const int nwords = (ctx->max_len + 63) >> 6;       // 64-row words of the longest read
         // behind the quick plan the full plan has one read in a hundred left: without fine blocks ONE launch (phase 0: the reads with anchors on
@@ -1374,25 +1305,14 @@ static int align_all(mia_hip_ctx* ctx) {
           }
 #undef MIA_PLAN_NW
 #undef MIA_PLAN
-          if (split_dp && phase == 1) {
-            launch_k(k_bx_snap, dim3(1), dim3(64), 0, ctx->stream, ctx->ev_snap, (const uint32_t*)ctx->d_bx_ctr, ctx->d_bx_snap);
-            HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_snap, 0));
-            HIPCHK(hipStreamWaitEvent(ctx->stream4, ctx->ev_snap, 0));
-            if (stage_begin(ctx, STG_BX_TRACE, ctx->stream3)) return MIA_HIP_ERR_NOMEM;
-            hipLaunchKernelGGL(k_bxl_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream3, ctx->rs, ref, bd, ctx->d_bx_slabs, slab_words, ctx->d_bin_of, (int32_t)BX_PART_HEAD);
-            stage_end(ctx, STG_BX_TRACE, ctx->stream3);
-            if (stage_launch(ctx, STG_BX_VALUES, k_bxl_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, ctx->stream4, ctx->rs, ref, bd, ctx->d_bin_of, (int32_t)BX_PART_HEAD))
-              return MIA_HIP_ERR_NOMEM;
-            HIPCHK(hipEventRecord(ctx->ev_v1, ctx->stream4));
-          }
         }
         bd.to_late = 0;
       }
       stage_end(ctx, STG_BX_PLAN);
       HIPCHK(hipGetLastError());
       if (planner_head_first) {
-        const bool use_plain_h = ctx->use_plain;      // (banded, many rejects: the values-only quad pass is on)
-        hipLaunchKernelGGL(k_plan_count, dim3(gb), dim3(tb), 0, ctx->stream, ctx->rs, ref, ctx->packs, ctx->use_quad, filtered, filtered && use_plain_h, ctx->d_bin_of, d_count, ctx->d_filter_n);
+        // (banded, many rejects: the values-only quad pass is on)
+        hipLaunchKernelGGL(k_plan_count, dim3(gb), dim3(tb), 0, ctx->stream, ctx->rs, ref, ctx->packs, /*use_quad=*/1, filtered, filtered, ctx->d_bin_of, d_count, ctx->d_filter_n);
         hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(512), 0, ctx->stream, d_count, d_off, ctx->d_plan_hdr, 0, ctx->d_list);
         launch_k(k_plan_fill, dim3(gb), dim3(tb), 0, ctx->stream, fork_by_launch ? ctx->ev_fork : nullptr, n, (const int32_t*)ctx->d_bin_of, (const int32_t*)d_off, d_cursor, ctx->d_list);
         HIPCHK(hipGetLastError());
@@ -1419,17 +1339,14 @@ static int align_all(mia_hip_ctx* ctx) {
           if (!fork_by_launch && !fork_at_quick) HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
           HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
           HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_fork, 0));
-          if (early) HIPCHK(hipStreamWaitEvent(ctx->stream4, ctx->ev_fork, 0));
           if (stage_begin(ctx, STG_BX_TRACE, ctx->stream3)) return MIA_HIP_ERR_NOMEM;
           const bool sig3 = (ctx->ext_events & 2u) && new_flow && !(ctx->bx_dbg & 8u);
-          const int32_t part2 = split_dp ? BX_PART_TAIL : BX_PART_ALL;
           if (!(ctx->bx_dbg & 8u))
-            launch_k(k_bxl_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream3, sig3 ? ctx->ev_join3 : nullptr, ctx->rs, ref, bd, ctx->d_bx_slabs, slab_words, ctx->d_bin_of, part2);
+            launch_k(k_bxl_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream3, sig3 ? ctx->ev_join3 : nullptr, ctx->rs, ref, bd, ctx->d_bx_slabs, slab_words, ctx->d_bin_of);
           stage_end(ctx, STG_BX_TRACE, ctx->stream3);
           if (!sig3) HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
           if (!(ctx->bx_dbg & 4u)) {
-            if (stage_launch(ctx, STG_BX_VALUES, k_bxl_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, vs, ctx->rs, ref, bd, ctx->d_bin_of, part2)) return MIA_HIP_ERR_NOMEM;
-            if (split_dp) HIPCHK(hipStreamWaitEvent(vs, ctx->ev_v1, 0));          // (the late lists hold both rounds' left-overs)
+            if (stage_launch(ctx, STG_BX_VALUES, k_bxl_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, vs, ctx->rs, ref, bd, ctx->d_bin_of)) return MIA_HIP_ERR_NOMEM;
             if (stage_launch(ctx, STG_BX_VALUES, k_bxl_trace_late, dim3((unsigned)ctx->bx_late_wgs), dim3(256), 0, vs, ctx->rs, ref, bd, ctx->d_bx_slabs_late, slab_words, ctx->d_bin_of))
               return MIA_HIP_ERR_NOMEM;
           }
@@ -1437,8 +1354,6 @@ static int align_all(mia_hip_ctx* ctx) {
           HIPCHK(hipGetLastError());
           ctx->bx_planner_aside = ctx->deferred;
           ctx->bx_pending_join = true;
-          // (queued behind the band DPs on the host side: the GPU starts it as soon as the plan's last launch is done)
-          if (early) { if (int rce = early_tally_launch(ctx)) return rce; }
         } else {
         // The two band DPs do not depend on each other (a read the values DP cannot finish stays open for the full-window
         // kernels): they run side by side on two streams -- both are persistent grids whose wavefronts leave as soon as the
@@ -1447,7 +1362,7 @@ static int align_all(mia_hip_ctx* ctx) {
         HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
         if (stage_begin(ctx, STG_BX_TRACE, ctx->stream2)) return MIA_HIP_ERR_NOMEM;
         if (ctx->bx_dbg & 8u) {}
-        else if (ctx->use_lanes) hipLaunchKernelGGL(k_bxl_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream2, ctx->rs, ref, bd, ctx->d_bx_slabs, slab_words, ctx->d_bin_of, (int32_t)BX_PART_ALL);
+        else if (ctx->use_lanes) hipLaunchKernelGGL(k_bxl_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream2, ctx->rs, ref, bd, ctx->d_bx_slabs, slab_words, ctx->d_bin_of);
 #ifdef MIA_HIP_ALT_PATHS
         else hipLaunchKernelGGL(k_bx_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream2, ctx->rs, ref, bd, ctx->d_bx_slabs, slab_words, ctx->d_bin_of);
 #endif
@@ -1455,7 +1370,7 @@ static int align_all(mia_hip_ctx* ctx) {
         HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
         if (stage_begin(ctx, STG_BX_VALUES)) return MIA_HIP_ERR_NOMEM;
         if (ctx->bx_dbg & 4u) {}
-        else if (ctx->use_lanes) hipLaunchKernelGGL(k_bxl_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, ctx->stream, ctx->rs, ref, bd, ctx->d_bin_of, (int32_t)BX_PART_ALL);
+        else if (ctx->use_lanes) hipLaunchKernelGGL(k_bxl_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, ctx->stream, ctx->rs, ref, bd, ctx->d_bin_of);
 #ifdef MIA_HIP_ALT_PATHS
         else hipLaunchKernelGGL(k_bx_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, ctx->stream, ctx->rs, ref, bd, ctx->d_bin_of);
 #endif
@@ -1482,8 +1397,6 @@ static int align_all(mia_hip_ctx* ctx) {
     }
   }
   // behind the banded DP the values-only pass has nothing left to prove: what the band could not take nearly always needs a trace
-  // (MIA_HIP_PLAIN_BEHIND_BAND=1: values-only pass over the band pipeline's left-overs all the same -- with a position-specific
-  // matrix most of them are gap-free reads with many substitutions, which it finishes at half the trace kernel's price)
   // ... unless the plan gives up on many reads: against a reference full of ambiguity codes (every run's first iteration
   // against mt311: the N columns alone exhaust the loss budget of one read in twenty, one in five with the ancient matrix),
   // or when it did so in the iteration before.  Most of those reads are gap-free; the values-only pass finishes them at
@@ -1491,11 +1404,11 @@ static int align_all(mia_hip_ctx* ctx) {
   // Either way every read gets the reference's alignment: the choice only moves work between exact kernels.
   int64_t last_rejects = 0;
   for (int k = 1; k < BXF_KINDS; k++) last_rejects += ctx->bx_last[BXC_FAIL0 + k];
-  const bool many_rejects = bx && !ctx->no_auto_plain && (!ctx->ref_mostly_bases || last_rejects * 20 > n);
-  const bool use_plain = ctx->use_plain && (!banded || ctx->plain_behind_band || many_rejects);
+  const bool many_rejects = bx && (!ctx->ref_mostly_bases || last_rejects * 20 > n);
+  const bool use_plain = !banded || many_rejects;
   hipStream_t ps = ctx->bx_planner_aside ? ctx->stream2 : ctx->stream;      // the planner's stream (see the band launches above)
   if (!planner_head_first && !direct_open)
-  hipLaunchKernelGGL(k_plan_count, dim3(gb), dim3(tb), 0, ps, ctx->rs, ref, ctx->packs, ctx->use_quad, filtered, filtered && use_plain, ctx->d_bin_of, d_count, ctx->d_filter_n);
+  hipLaunchKernelGGL(k_plan_count, dim3(gb), dim3(tb), 0, ps, ctx->rs, ref, ctx->packs, /*use_quad=*/1, filtered, filtered && use_plain, ctx->d_bin_of, d_count, ctx->d_filter_n);
   if (ctx->deferred) {
     // ---- mia_hip_iterate: the same plan, but its numbers stay on the device (k_plan_scan) and every DP kernel reads its own
     // range; the host looks at the counters once, when everything has been queued --------------------------------------
@@ -1514,7 +1427,7 @@ static int align_all(mia_hip_ctx* ctx) {
     }
     ck("memsets");
     hipLaunchKernelGGL(k_wide_seed, dim3(1), dim3(256), 0, ps, ctx->d_list, hdr, ctx->d_wide_list, d_wide_count,
-                       (ctx->use_quad && use_plain) ? d_count : (int32_t*)nullptr, d_cursor);      // (cleared for the re-plan below)
+                       use_plain ? d_count : (int32_t*)nullptr, d_cursor);      // (cleared for the re-plan below)
     ck("scan fill seed");
     // every window class reads its own range from the header (the list is rewritten by the re-plan below, so they all go
     // before it; a class without reads costs an empty launch -- a few microseconds -- and three of them in front of the quad
@@ -1529,51 +1442,44 @@ static int align_all(mia_hip_ctx* ctx) {
       ck("window classes");
       return MIA_HIP_OK;
     };
-    bool windows_done = false;
     const size_t quad_lds = (size_t)Q_G * q_sub_bytes(ctx->max_len) + 16;
-    if (ctx->use_quad) {
-      if (use_plain) {
-        if (stage_begin(ctx, STG_PLAIN, ps)) return MIA_HIP_ERR_NOMEM;
-        hipLaunchKernelGGL(k_align_quad_plain, dim3(ctx->quad_wgs), dim3(64), quad_lds, ps, ctx->rs, ref, ctx->d_pssm, ctx->d_list, 0, ctx->d_bin_of,
-                           (const int32_t*)(hdr + PH_QUAD));
-        stage_end(ctx, STG_PLAIN, ps);
-        ck("quad plain");
-        if (int rcw = window_classes()) return rcw;
-        windows_done = true;
-        // what it could not finish (and what the filter's gap hint kept out of it), re-planned into quads
-        // (d_count / d_cursor: cleared by k_wide_seed)
-        hipLaunchKernelGGL(k_plan_recount, dim3(gb), dim3(tb), 0, ps, n, ctx->d_bin_of, d_count);
-        hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(512), 0, ps, d_count, d_off, hdr, 1, ctx->d_list);
-        hipLaunchKernelGGL(k_plan_fill, dim3(gb), dim3(tb), 0, ps, n, ctx->d_bin_of, d_off, d_cursor, ctx->d_list);
-        ck("replan");
-      }
-      const int64_t slab = (int64_t)Q_G * MAX_READ * Q_TRACE_STRIDE;
-      if (!ctx->d_quad_slabs && hipMalloc((void**)&ctx->d_quad_slabs, (size_t)slab * ctx->quad_wgs) != hipSuccess) return MIA_HIP_ERR_NOMEM;
-      const int qgrid = ctx->quad_wgs;
-      if (dbg_steps) {
-        int32_t hh[PH_WORDS];
-        (void)hipMemcpy(hh, hdr, sizeof hh, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[align_all deferred] hdr:");
-        for (int k = 0; k < PH_WORDS; k++) fprintf(stderr, " %d", hh[k]);
-        fprintf(stderr, "  n=%lld max_len=%d quad_lds=%zu\n", (long long)n, ctx->max_len, quad_lds);
-      }
-      if (stage_begin(ctx, STG_TRACE, ps)) return MIA_HIP_ERR_NOMEM;
-      hipLaunchKernelGGL(k_align_quad, dim3(qgrid), dim3(64), quad_lds, ps, ctx->rs, ref, ctx->d_pssm, ctx->packs.p[0], ctx->d_list, 0,
-                         ctx->d_quad_slabs, slab, ctx->d_wide_list, d_wide_count, ctx->d_retry_list, d_retry_cnt, ctx->use_band, ctx->dbg,
+    if (use_plain) {
+      if (stage_begin(ctx, STG_PLAIN, ps)) return MIA_HIP_ERR_NOMEM;
+      hipLaunchKernelGGL(k_align_quad_plain, dim3(ctx->quad_wgs), dim3(64), quad_lds, ps, ctx->rs, ref, ctx->d_pssm, ctx->d_list, 0, ctx->d_bin_of,
                          (const int32_t*)(hdr + PH_QUAD));
-      stage_end(ctx, STG_TRACE, ps);
-      HIPCHK(hipGetLastError());
-      ck("quad trace");
-      if (!windows_done) { if (int rcw = window_classes()) return rcw; windows_done = true; }
-      if (ctx->use_band) {
-        // (the last launch of the planner's chain: on stream2 it signals ev_join itself, see bx_join_and_retry)
-        const bool sig = ctx->bx_planner_aside && ctx->bx_pending_join && (ctx->ext_events & 4u);
-        hipError_t e = launch_window<4>(ctx, 0, ctx->d_retry_list, 0, hdr + PH_RETRY, ps, false, sig ? ctx->ev_join : nullptr);
-        ctx->planner_end_signalled = sig && e == hipSuccess;
-        if (e != hipSuccess) { ctx->err = std::string("k_align_window retry launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
-      }
+      stage_end(ctx, STG_PLAIN, ps);
+      ck("quad plain");
+      if (int rcw = window_classes()) return rcw;
+      // what it could not finish (and what the filter's gap hint kept out of it), re-planned into quads
+      // (d_count / d_cursor: cleared by k_wide_seed)
+      hipLaunchKernelGGL(k_plan_recount, dim3(gb), dim3(tb), 0, ps, n, ctx->d_bin_of, d_count);
+      hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(512), 0, ps, d_count, d_off, hdr, 1, ctx->d_list);
+      hipLaunchKernelGGL(k_plan_fill, dim3(gb), dim3(tb), 0, ps, n, ctx->d_bin_of, d_off, d_cursor, ctx->d_list);
+      ck("replan");
     }
-    if (!windows_done) { if (int rcw = window_classes()) return rcw; }
+    const int64_t slab = (int64_t)Q_G * MAX_READ * Q_TRACE_STRIDE;
+    if (!ctx->d_quad_slabs && hipMalloc((void**)&ctx->d_quad_slabs, (size_t)slab * ctx->quad_wgs) != hipSuccess) return MIA_HIP_ERR_NOMEM;
+    const int qgrid = ctx->quad_wgs;
+    if (dbg_steps) {
+      int32_t hh[PH_WORDS];
+      (void)hipMemcpy(hh, hdr, sizeof hh, hipMemcpyDeviceToHost);
+      fprintf(stderr, "[align_all deferred] hdr:");
+      for (int k = 0; k < PH_WORDS; k++) fprintf(stderr, " %d", hh[k]);
+      fprintf(stderr, "  n=%lld max_len=%d quad_lds=%zu\n", (long long)n, ctx->max_len, quad_lds);
+    }
+    if (stage_begin(ctx, STG_TRACE, ps)) return MIA_HIP_ERR_NOMEM;
+    hipLaunchKernelGGL(k_align_quad, dim3(qgrid), dim3(64), quad_lds, ps, ctx->rs, ref, ctx->d_pssm, ctx->packs.p[0], ctx->d_list, 0,
+                       ctx->d_quad_slabs, slab, ctx->d_wide_list, d_wide_count, ctx->d_retry_list, d_retry_cnt, /*band=*/1, ctx->dbg,
+                       (const int32_t*)(hdr + PH_QUAD));
+    stage_end(ctx, STG_TRACE, ps);
+    HIPCHK(hipGetLastError());
+    ck("quad trace");
+    if (!use_plain) { if (int rcw = window_classes()) return rcw; }
+    // (the last launch of the planner's chain: on stream2 it signals ev_join itself, see bx_join_and_retry)
+    const bool sig = ctx->bx_planner_aside && ctx->bx_pending_join && (ctx->ext_events & 4u);
+    hipError_t e = launch_window<4>(ctx, 0, ctx->d_retry_list, 0, hdr + PH_RETRY, ps, false, sig ? ctx->ev_join : nullptr);
+    ctx->planner_end_signalled = sig && e == hipSuccess;
+    if (e != hipSuccess) { ctx->err = std::string("k_align_window retry launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
     }
     ck("retry");
     if (int rcj = bx_join_and_retry(ctx)) return rcj;
@@ -1595,13 +1501,13 @@ static int align_all(mia_hip_ctx* ctx) {
       // mia_hip_iterate, one context, a cut line that needs no scores on the host: no wait here.  The caller queues cull,
       // tally and consensus behind this copy; their kernels look at the exact-kernel count themselves (abort_if) and
       // iterate_body reads these counters when it waits for the consensus (align_counters_collect).
-      ctx->spec_pending = true; ctx->spec_filtered = filtered != 0; ctx->spec_bx = bx; ctx->spec_plain = use_plain && ctx->use_quad;
+      ctx->spec_pending = true; ctx->spec_filtered = filtered != 0; ctx->spec_bx = bx; ctx->spec_plain = use_plain;
       ctx->abort_if = ctx->spec_force ? ctx->d_one : d_wide_count;      // (MIA_HIP_SPEC_TEST=1: every iteration takes the second round)
       ctx->aligned = true; ctx->culled = false; ctx->tallied = false; ctx->pre_cull_valid = false;
       return MIA_HIP_OK;
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    align_counters_collect(ctx, hb, filtered != 0, bx, use_plain && ctx->use_quad);
+    align_counters_collect(ctx, hb, filtered != 0, bx, use_plain);
     const int32_t n_wide = hb[0];
     if (n_wide > 0) { if (int rcw = run_wide(ctx, ref, n_wide)) return rcw; }
     if (pre_cull && comm_pre_cull_collect(ctx)) {
@@ -1707,22 +1613,20 @@ static int align_all(mia_hip_ctx* ctx) {
     const size_t quad_lds = (size_t)Q_G * q_sub_bytes(ctx->max_len) + 16;
     if (stage_begin(ctx, STG_TRACE)) return MIA_HIP_ERR_NOMEM;
     hipLaunchKernelGGL(k_align_quad, dim3(grid), dim3(64), quad_lds, ctx->stream, ctx->rs, ref, ctx->d_pssm, ctx->packs.p[0], ctx->d_list + quad_begin,
-                       n_quads, ctx->d_quad_slabs, slab, ctx->d_wide_list, d_wide_count, ctx->d_retry_list, d_retry_count, ctx->use_band,
+                       n_quads, ctx->d_quad_slabs, slab, ctx->d_wide_list, d_wide_count, ctx->d_retry_list, d_retry_count, /*band=*/1,
                        ctx->dbg, (const int32_t*)nullptr);
     stage_end(ctx, STG_TRACE);
     HIPCHK(hipGetLastError());
-    if (ctx->use_band) {
-      // reads whose path left the stored trace band: one-read kernel with the full trace (windows <= 208 fit class 0)
-      // (the two counters sit side by side: one copy, one wait; the wide count is final unless the retry kernel runs)
-      HIPCHK(hipMemcpyAsync(&h_misc[2], d_wide_count, 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      const int32_t n_retry = h_misc[3];
-      if (n_retry > 0) {
-        hipError_t e = launch_window<4>(ctx, 0, ctx->d_retry_list, n_retry);
-        if (e != hipSuccess) { ctx->err = std::string("k_align_window retry launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
-      } else {
-        wide_known = true;
-      }
+    // reads whose path left the stored trace band: one-read kernel with the full trace (windows <= 208 fit class 0)
+    // (the two counters sit side by side: one copy, one wait; the wide count is final unless the retry kernel runs)
+    HIPCHK(hipMemcpyAsync(&h_misc[2], d_wide_count, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const int32_t n_retry = h_misc[3];
+    if (n_retry > 0) {
+      hipError_t e = launch_window<4>(ctx, 0, ctx->d_retry_list, n_retry);
+      if (e != hipSuccess) { ctx->err = std::string("k_align_window retry launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
+    } else {
+      wide_known = true;
     }
   }
   if (ctx->bx_pending_join) { if (int rcj = bx_join_and_retry(ctx)) return rcj; wide_known = false; }
@@ -1827,9 +1731,8 @@ static int finish_params(mia_hip_ctx* ctx) {
   hipLaunchKernelGGL(k_rec_params, dim3((int)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rs, ctx->L, ctx->d_slot, ctx->d_slot_dropped,
                      ctx->n_slots, ctx->d_back_slot, ctx->ri, ctx->si, ctx->d_links_all, ctx->d_link_len, ctx->d_link_act, ctx->d_n_links_all,
                      (int32_t)ctx->links_cap_all, ctx->read_base, ctx->d_drop_f, ctx->d_drop_b, ctx->d_cull_flags, ctx->abort_if,
-                     ctx->early_queued ? ctx->d_early : (const uint8_t*)nullptr, ctx->d_fix_list, ctx->d_ctrl + CTRL_FIXN,
                      (ctx->umax_valid && ctx->rs.roff == ctx->d_roff && ctx->d_rplanes && ctx->d_umax) ? ctx->d_umax : (const int32_t*)nullptr,
-                     (ctx->cull_with_records && ctx->d_n_links_all == ctx->lk.n && !ctx->early_queued) ? 1 : 0);
+                     (ctx->cull_with_records && ctx->d_n_links_all == ctx->lk.n) ? 1 : 0);
   HIPCHK(hipGetLastError());
   return MIA_HIP_OK;
 }
@@ -2169,7 +2072,7 @@ static int ensure_tally(mia_hip_ctx* ctx) {
 // part-filled workgroups and got nothing for it: 2.18 against round 4's 1.51 ms per 5 M reads of 150 bases.)
 static bool tally_rall(const mia_hip_ctx* ctx) { return ctx->max_len > 128 && ctx->max_len <= 256 && ctx->tally_runs && ctx->tally_rall; }
 static int tally_split(const mia_hip_ctx* ctx) {
-  return (!ctx->tally_linear && ctx->tally_strand_split && !ctx->early_queued && !ctx->use_early && (ctx->max_len <= 128 || tally_rall(ctx))) ? 1 : 0;
+  return (!ctx->tally_linear && ctx->tally_strand_split && (ctx->max_len <= 128 || tally_rall(ctx))) ? 1 : 0;
 }
 static int tally_nb(const mia_hip_ctx* ctx) { return (ctx->wrap / TALLY_BUCKET + 1) << tally_split(ctx); }
 static bool tally_is_binned(const mia_hip_ctx* ctx) {
@@ -2180,7 +2083,7 @@ static bool tally_is_binned(const mia_hip_ctx* ctx) {
 // alignment starts, so mia_hip_iterate queues it on stream2 BESIDE the cull kernels (it also clears the tally buffers:
 // nothing adds to them before the tally kernel).  tally_launch waits for ev_join if `on` is not the context's stream.
 // reads per workgroup of the binned tally (the linear matrix: one read per lane -- measured, mia_consensus_kernels.h)
-static int tally_chunk(const mia_hip_ctx* ctx) { return ctx->early_queued ? TALLY_CHUNK_LATE : (ctx->tally_linear ? ctx->tally_chunk_linear : TALLY_CHUNK); }
+static int tally_chunk(const mia_hip_ctx* ctx) { return ctx->tally_linear ? TALLY_CHUNK_LINEAR : TALLY_CHUNK; }
 static int bucket_launch(mia_hip_ctx* ctx, hipStream_t on) {
   int rc = ensure_tally(ctx);
   if (rc) return rc;
@@ -2188,8 +2091,6 @@ static int bucket_launch(mia_hip_ctx* ctx, hipStream_t on) {
   const int64_t tally_words = (int64_t)(TALLY_WORDS + 1) * Lp + 256;                               // tally, gaps, the ranks' event counts
   const int64_t n = ctx->rs.n;
   const int nb = tally_nb(ctx), split = tally_split(ctx);
-  // (behind an early tally what is left are the reads with substitutions and gaps -- a fifth of them, and the slow ones: smaller shares
-  // per workgroup, or a few hundred workgroups with 512 slow reads each take longer than the whole tally did)
   const int chunk = tally_chunk(ctx);
   const int grid = (int)(n / chunk) + nb + 1;
   if (4 * (nb + 1) + 4 * grid > ctx->bucket_cap) {
@@ -2202,13 +2103,10 @@ static int bucket_launch(mia_hip_ctx* ctx, hipStream_t on) {
   // the bucket counts are left at zero by k_bucket_scan; only a fresh (or differently laid out) buffer is cleared here
   if (ctx->bucket_clean_nb != nb) { HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)(nb + 1) * 4, on)); ctx->bucket_clean_nb = nb; }
   const int gb = (int)((n + 256 * BUCKET_PER - 1) / (256 * BUCKET_PER));
-  // (with an early tally queued: only the reads it did not take, and the tally buffers are left alone -- its own sort cleared them)
-  const uint8_t* part = ctx->early_queued ? ctx->d_early : nullptr;
-  hipLaunchKernelGGL(k_bucket_count, dim3(gb), dim3(256), (size_t)nb * 4, on, ctx->rs, nb, d_cnt, part ? (int32_t*)nullptr : ctx->tb.tally, part ? (int64_t)0 : tally_words,
-                     ctx->abort_if, part, 0, split);
+  hipLaunchKernelGGL(k_bucket_count, dim3(gb), dim3(256), (size_t)nb * 4, on, ctx->rs, nb, d_cnt, ctx->tb.tally, tally_words, ctx->abort_if, split);
   hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(256), 0, on, d_cnt, nb, d_off, d_wgoff, d_cur, d_wgb, ctx->abort_if, chunk);
   const bool sigb = on != ctx->stream && (ctx->ext_events & 16u);
-  if (!split) launch_k(k_bucket_fill, dim3(gb), dim3(256), (size_t)nb * 8, on, sigb ? ctx->ev_join : nullptr, ctx->rs, nb, d_off, d_cur, ctx->d_order, ctx->abort_if, part, 0, split, (uint8_t*)nullptr, 0);
+  if (!split) launch_k(k_bucket_fill, dim3(gb), dim3(256), (size_t)nb * 8, on, sigb ? ctx->ev_join : nullptr, ctx->rs, nb, d_off, d_cur, ctx->d_order, ctx->abort_if, split, (uint8_t*)nullptr, 0);
   else {
     // ... and every bucket by alignment start (k_sort2_count / k_sort2_fill: the tally's runs of equal starts)
     const int64_t words2 = (int64_t)nb * SORT2_KEYS * 2;
@@ -2217,8 +2115,8 @@ static int bucket_launch(mia_hip_ctx* ctx, hipStream_t on) {
     if (!ctx->d_order2 && dev_alloc(ctx, &ctx->d_order2, (size_t)n)) return MIA_HIP_ERR_NOMEM;
     if (!ctx->d_okey && dev_alloc(ctx, &ctx->d_okey, (size_t)n + 64)) return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipMemsetAsync(ctx->d_sort2, 0, (size_t)words2 * 4, on));
-    const int32_t packed = (n < (1 << 24) && !alt_env("MIA_HIP_SORT2_UNPACKED")) ? 1 : 0;      // (the key in the entry's top byte, or -- 2^24 reads and more -- in a byte array beside it)
-    hipLaunchKernelGGL(k_bucket_fill, dim3(gb), dim3(256), (size_t)nb * 8, on, ctx->rs, nb, (const int32_t*)d_off, d_cur, ctx->d_order, ctx->abort_if, part, 0, split, ctx->d_okey, packed);
+    const int32_t packed = (n < (1 << 24) && !ctx->sort2_unpacked) ? 1 : 0;      // (the key in the entry's top byte, or -- 2^24 reads and more -- in a byte array beside it)
+    hipLaunchKernelGGL(k_bucket_fill, dim3(gb), dim3(256), (size_t)nb * 8, on, ctx->rs, nb, (const int32_t*)d_off, d_cur, ctx->d_order, ctx->abort_if, split, ctx->d_okey, packed);
     hipLaunchKernelGGL(k_sort2_count, dim3(grid), dim3(256), 0, on, nb, (const int32_t*)d_wgoff, (const int32_t*)d_wgb, (const int32_t*)ctx->d_order, (const uint8_t*)ctx->d_okey, packed,
                        ctx->d_sort2, ctx->abort_if);
     launch_k(k_sort2_fill, dim3(grid), dim3(256), 0, on, sigb ? ctx->ev_join : nullptr, nb, (const int32_t*)d_off, (const int32_t*)d_wgoff, (const int32_t*)d_wgb,
@@ -2227,63 +2125,6 @@ static int bucket_launch(mia_hip_ctx* ctx, hipStream_t on) {
   HIPCHK(hipGetLastError());
   if (on != ctx->stream && !sigb) HIPCHK(hipEventRecord(ctx->ev_join, on));
   ctx->buckets_queued = on != ctx->stream ? 2 : 1;
-  return MIA_HIP_OK;
-}
-
-// The early tally: record, counting sort and LDS-window tally of the reads the plan has finished, on stream4 (behind ev_fork);
-// ev_early tells tally_launch when its windows may be summed.  None of its kernels looks at abort_if: the reads it takes do not
-// change if the step's second half is queued again (reads for the exact kernel), and its sort clears the tally buffers once.
-static int early_tally_launch(mia_hip_ctx* ctx) {
-  if (int rc = ensure_tally(ctx)) return rc;
-  hipStream_t on = ctx->stream4;
-  const int Lp = ctx->tb.Lp;
-  const int64_t tally_words = (int64_t)(TALLY_WORDS + 1) * Lp + 256;
-  const int64_t n = ctx->rs.n;
-  const int nb = ctx->wrap / TALLY_BUCKET + 1;
-  const int grid = (int)(n / TALLY_CHUNK) + nb + 1;
-  if (4 * (nb + 1) + 4 * grid > ctx->bucket_e_cap) {
-    if (dev_alloc(ctx, &ctx->d_bucket_e, (size_t)(4 * (nb + 1) + 4 * grid) * 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->bucket_e_cap = (4 * (nb + 1) + 4 * grid) * 2;
-    ctx->bucket_e_clean_nb = -1;
-  }
-  int32_t *d_cnt = ctx->d_bucket_e, *d_off = d_cnt + (nb + 1), *d_wgoff = d_off + (nb + 1), *d_cur = d_wgoff + (nb + 1), *d_wgb = d_cur + (nb + 1);
-  if (ctx->bucket_e_clean_nb != nb) { HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)(nb + 1) * 4, on)); ctx->bucket_e_clean_nb = nb; }
-  const int64_t slab_words = (int64_t)grid * (TALLY_WORDS - 1) * TALLY_WIN;
-  if (slab_words > ctx->tally_slab_e_cap) {
-    if (dev_alloc(ctx, &ctx->d_tally_slabs_e, (size_t)slab_words)) return MIA_HIP_ERR_NOMEM;
-    ctx->tally_slab_e_cap = slab_words;
-  }
-  RefInfo ref{ctx->d_ref, ctx->L, ctx->wrap};
-  hipLaunchKernelGGL(k_rec_early, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, on, ctx->rs, ctx->L, (const uint8_t*)ctx->d_early, ctx->d_trec_early,
-                     (ctx->umax_valid && ctx->rs.roff == ctx->d_roff && ctx->d_rplanes && ctx->d_umax) ? ctx->d_umax : (const int32_t*)nullptr);
-  const int gb = (int)((n + 256 * BUCKET_PER - 1) / (256 * BUCKET_PER));
-  hipLaunchKernelGGL(k_bucket_count, dim3(gb), dim3(256), (size_t)nb * 4, on, ctx->rs, nb, d_cnt, ctx->tb.tally, tally_words, (const int32_t*)nullptr,
-                     (const uint8_t*)ctx->d_early, 1);
-  hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(256), 0, on, d_cnt, nb, d_off, d_wgoff, d_cur, d_wgb, (const int32_t*)nullptr, TALLY_CHUNK);
-  hipLaunchKernelGGL(k_bucket_fill, dim3(gb), dim3(256), (size_t)nb * 8, on, ctx->rs, nb, (const int32_t*)d_off, d_cur, ctx->d_order_e, (const int32_t*)nullptr,
-                     (const uint8_t*)ctx->d_early, 1);
-  const bool planes_ok = ctx->umax_valid && ctx->rs.roff == ctx->d_roff && ctx->d_rplanes && ctx->d_umax;
-  // This launch has the whole band-DP phase to finish in and must not take the DPs' issue slots: extra LDS per workgroup (unused)
-  // keeps it to `early_wgs_per_cu` workgroups per compute unit (MIA_HIP_EARLY_WGS, alt build; 0: no limit)
-  size_t throttle = 0;
-  if (ctx->early_wgs_per_cu > 0) {
-    const size_t lds_static = ctx->tally_linear ? 27 * 1024 : 41 * 1024, want = (size_t)(160 * 1024) / (size_t)ctx->early_wgs_per_cu;
-    if (want > lds_static + 1024) throttle = std::min<size_t>(want - lds_static - 512, (size_t)(64 * 1024) - lds_static - 512);
-  }
-  // (the plan's reads all take the one-read-per-lane route: nothing of this launch goes to k_tally_general)
-  if (ctx->tally_linear
-        ? stage_launch(ctx, STG_TALLY, k_tally_binned<true, false>, dim3(grid), dim3(256), throttle, on, ctx->rs, ref, ctx->d_pssm, ctx->d_drop_f, ctx->d_drop_b,
-                       ctx->tb, nb, d_off, d_wgoff, ctx->d_order_e, ctx->d_trec_early, ctx->ri.actf, ctx->d_tally_slabs_e, ctx->dbg,
-                       planes_ok ? ctx->d_rplanes : nullptr, ctx->rplane_words, planes_ok ? ctx->d_umax : nullptr, d_wgb, -1, (const int32_t*)nullptr, (int32_t)TALLY_CHUNK,
-                       (int32_t*)nullptr, (int32_t*)nullptr, 0)
-        : stage_launch(ctx, STG_TALLY, k_tally_binned<false, false>, dim3(grid), dim3(256), throttle, on, ctx->rs, ref, ctx->d_pssm, ctx->d_drop_f, ctx->d_drop_b,
-                       ctx->tb, nb, d_off, d_wgoff, ctx->d_order_e, ctx->d_trec_early, ctx->ri.actf, ctx->d_tally_slabs_e, ctx->dbg,
-                       (const uint64_t*)nullptr, 0, (const int32_t*)nullptr, d_wgb, ctx->tally_pk_bias, (const int32_t*)nullptr, (int32_t)TALLY_CHUNK,
-                       (int32_t*)nullptr, (int32_t*)nullptr, 0))
-    return MIA_HIP_ERR_NOMEM;
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ctx->ev_early, on));
-  ctx->early_queued = true;
   return MIA_HIP_OK;
 }
 
@@ -2341,15 +2182,6 @@ static int tally_launch(mia_hip_ctx* ctx) {
                     : stage_launch(ctx, STG_TALLY, k_tally_binned<false, false>, MIA_TALLY_ARGS(split ? pl_arg : nullptr, ctx->rplane_words, split ? um_arg : nullptr, ctx->tally_pk_bias));
 #undef MIA_TALLY_ARGS
       if (rct) return MIA_HIP_ERR_NOMEM;
-      if (ctx->early_queued) {
-        // the early tally's corrections (reads whose true record is not the ordinary one it assumed), then its windows join the sum
-        hipLaunchKernelGGL(k_tally_fix, dim3(64), dim3(256), 0, ctx->stream, ctx->rs, ref, ctx->d_pssm, ctx->d_drop_f, ctx->d_drop_b, ctx->tb, ctx->ri.trec,
-                           ctx->d_trec_early, ctx->ri.actf, ctx->d_fix_list, ctx->d_ctrl + CTRL_FIXN, ctx->abort_if);
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_early, 0));
-        int32_t* e_wgoff = ctx->d_bucket_e + 2 * (nb + 1);
-        GenReads none{ctx->rs, ref, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        hipLaunchKernelGGL(k_tally_reduce, dim3((Lp + 255) / 256, TALLY_WORDS - 1), dim3(256), 0, ctx->stream, ctx->tb, nb, e_wgoff, ctx->d_tally_slabs_e, ctx->abort_if, none);
-      }
       GenReads gen{ctx->rs, ref, ctx->d_pssm, ctx->d_drop_f, ctx->d_drop_b, ctx->ri.trec, ctx->ri.actf, defer ? ctx->d_gen_list : nullptr, n_gen};
       hipLaunchKernelGGL(k_tally_reduce, dim3((Lp + 255) / 256 + (defer ? TALLY_GEN_BLOCKS : 0), TALLY_WORDS - 1, TALLY_REDUCE_SHARES), dim3(256), 0, ctx->stream, ctx->tb, nb, d_wgoff,
                          ctx->d_tally_slabs, ctx->abort_if, gen, split);

@@ -192,7 +192,7 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
   ctx->ref_mostly_bases = n_other * 50 <= L;
   ctx->ref_few_n = n_other * 500 <= L;
   ctx->kh_entries = 0;
-  if (n_other && ctx->use_wild) {            // (kh_wild_entries over the wrapped string, without making the codes here)
+  if (n_other) {            // (kh_wild_entries over the wrapped string, without making the codes here)
     int64_t e = 0;
     int k = 0;
     auto other = [&](int j) { return base_code(new_ref[j < L ? j : j - L]) > 3 ? 1 : 0; };

@@ -387,7 +387,6 @@ extern "C" int mia_hip_pass1(mia_hip_ctx* ctx, const char* ref, int32_t ref_len,
   if (waves_cu < 1) { ctx->err = "pass-1 kernel does not fit a compute unit"; return MIA_HIP_ERR_RANGE; }
   // whole waves per SIMD only: an uneven remainder (13 = 4+3+3+3) measured slower than 12, the extra workgroups start late
   if (waves_cu > 4) waves_cu &= ~3;
-  if (const char* ev = alt_env("MIA_HIP_P1_WAVES_PER_CU")) { const int wv = atoi(ev); if (wv > 0 && wv < waves_cu) waves_cu = wv; }
   if (timing) fprintf(stderr, "[mia_hip_pass1] cpl %d plain %d waves/CU %d lds %d\n", cpl, plain, waves_cu, lds);
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, ctx->device));
@@ -409,18 +408,18 @@ extern "C" int mia_hip_pass1(mia_hip_ctx* ctx, const char* ref, int32_t ref_len,
   const bool fast_ok = ctx->flat && ctx->use_filter && kmer_len <= 0 && len1 >= max_len;
   // any other matrix the band pipeline has tables for: the anchored windows in losses (mia_pass1_kernels.h, GEN); the
   // diagonal filter stays the flat matrix's
-  const bool gen_ok = !ctx->flat && ctx->bx_ok && ctx->use_bx && ctx->use_filter && kmer_len <= 0 && len1 >= max_len && !alt_env("MIA_HIP_NO_ANCHOR_GEN");
+  const bool gen_ok = !ctx->flat && ctx->bx_ok && ctx->use_bx && ctx->use_filter && kmer_len <= 0 && len1 >= max_len;
   const bool filtered = fast_ok && p1_other * 50 <= L;
   // the anchored stage behind it (or in its place: a reference full of ambiguity codes, mt311 itself, leaves the filter
   // nothing to decide): the windows' 10-mer tables list the N columns under every spelling (bandx_body.h, N COLUMNS)
   int64_t wild_entries = 0;
-  if ((fast_ok || gen_ok) && p1_other && ctx->use_wild && len1 <= (1 << 22)) {
+  if ((fast_ok || gen_ok) && p1_other && len1 <= (1 << 22)) {
     std::vector<uint8_t> both(cf.begin(), cf.begin() + len1);
     both.insert(both.end(), cr.begin(), cr.begin() + len1);
     wild_entries = kh_wild_entries(both.data(), (int64_t)both.size(), BX_WILD);
     if (wild_entries > ((int64_t)1 << 24)) wild_entries = 0;
   }
-  const bool anchored_ok = (fast_ok || gen_ok) && (p1_other == 0 || wild_entries > 0) && len1 <= (1 << 22) && !alt_env("MIA_HIP_NO_ANCHOR");
+  const bool anchored_ok = (fast_ok || gen_ok) && (p1_other == 0 || wild_entries > 0) && len1 <= (1 << 22);
   int64_t n_dp = n;
   ctx->pass1_filtered = 0;
   ctx->pass1_anchored = 0;

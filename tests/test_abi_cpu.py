@@ -2,6 +2,7 @@
 include/mia_hip.h declares, refuses to run without a GPU (no CPU fallback), and its
 host-only helper (score-cut regression) follows the reference arithmetic."""
 import ctypes as C
+import glob
 import math
 import os
 import re
@@ -43,6 +44,20 @@ def test_release_library_reads_five_environment_variables(mia):
     assert os.path.exists(mia.ALT_LIB_PATH)
     alt = names(mia.ALT_LIB_PATH)
     assert {"MIA_HIP_DEBUG_SKIP", "MIA_HIP_NO_LANES", "MIA_HIP_NO_DIAG_FILTER", "MIA_HIP_NO_FINE"} <= alt
+    # every switch a test or a tool sets is one the alt library reads: a misspelt or retired name would compare the default with itself
+    not_switches = {"MIA_HIP_SPIN_WAIT", "MIA_HIP_LOOPBACK_TIMEOUT", "MIA_HIP_THREADS", "MIA_HIP_TIMING", "MIA_HIP_LIB", "MIA_HIP_ALT_PATHS",
+                    "MIA_HIP_OK", "MIA_HIP_X"}          # (release variables, the binding's own, the build's macro, a status code, tools/ab_bench.sh's placeholder)
+    used = set()
+    for path in glob.glob(os.path.join(ROOT, "tests", "*.py")) + glob.glob(os.path.join(ROOT, "tools", "*")):
+        if os.path.isfile(path):
+            used |= names(path)
+    used = {n for n in used if n not in not_switches and not n.startswith(("MIA_HIP_OP_", "MIA_HIP_ERR_"))}
+    assert used <= alt, sorted(used - alt)
+    # ... and the names retired with their code are gone from it (spelt without the prefix here, so that this file does not name them)
+    retired = {"MIA_HIP_" + s for s in ("EARLY_TALLY EARLY_WGS SPLIT_DP NO_BAND NO_PLAIN PLAIN_BEHIND_BAND NO_AUTO_PLAIN NO_QUAD QUAD_WAVES_PER_CU "
+                                        "GRID_WAVES_PER_CU NO_WILD EAGER_SCRIPTS BX_FILTER PLANNER_BESIDE STAGE_MARKERS EXT_EVENTS_MASK TALLY_CHUNK "
+                                        "NO_PACKED_TALLY NO_ANCHOR NO_ANCHOR_GEN P1_WAVES_PER_CU EVENT_DEVICE_SCOPE BX_VALUES_PCT BX_TRACE_PCT").split()}
+    assert not (retired & alt), sorted(retired & alt)
     hdr = open(os.path.join(ROOT, "include", "mia_hip.h")).read()
     declared = sorted(set(re.findall(r"\b(mia_hip_[a-z_0-9]+)\s*\(", hdr)))
     lib = mia.alt_lib()

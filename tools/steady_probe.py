@@ -20,7 +20,7 @@ cur = w["ref"]
 for _ in range(6):
     cur = pipe.step(cur)
 hip.close()
-for env in ({}, {"MIA_HIP_BX_SERIAL": "1"}, {"MIA_HIP_NO_LANES": "1"}, {"MIA_HIP_NO_AUTO_PLAIN": "1"}):
+for env in ({}, {"MIA_HIP_BX_SERIAL": "1"}, {"MIA_HIP_NO_LANES": "1"}):
     os.environ.update(env)
     hip = mia_amd.MiaHip(0)
     for k in env:
