@@ -303,6 +303,18 @@ int mia_hip_ma_tally(mia_hip_ctx *ctx, int32_t ref_len, const int32_t *gaps, int
  * (bases = records with a base in that column; cov = T_SPAN word of the column, gaps = cov - bases). */
 int mia_hip_get_ins_tally(mia_hip_ctx *ctx, int32_t *ins_off, int32_t *ins_tally, int64_t cap_slots, int64_t *n_slots);
 
+/* The record lines of print_region (src/map_align.c:660-750; ma -f 6 / -f 61) for the records of the last
+ * mia_hip_ma_tally, which stay on the device.  first .. last: 0-based inclusive reference columns, already clamped
+ * to the reference; first > last is legal and gives width 0.  Reference column p owns gaps[p] insert columns in
+ * front of it, p == 0 and p == first included, so  width = sum over first..last of gaps[p] + 1.
+ * Selected are the records with start <= last && end >= first (alnseq_ol_reg, src/map_align.c:44-46), in record
+ * order.  A record's row: gaps[p] + 1 dots for a column it does not cover; on its own first column dots for the
+ * insert columns; on a later column its inserted bases, then '-' up to gaps[p]; then its seq character. */
+int mia_hip_ma_region(mia_hip_ctx *ctx, int32_t first, int32_t last, int64_t *n_rows, int64_t *width);
+/* rows[n_rows] = the selected records, text[n_rows * width] = their rows (no terminators); cap_rows = rows the
+ * buffers hold (>= n_rows).  Either pointer may be NULL. */
+int mia_hip_get_ma_region(mia_hip_ctx *ctx, int64_t *rows, char *text, int64_t cap_rows);
+
 /* ---- Myers edit distance -------------------------------------------------- */
 
 /* unsigned myers_diff(const char *seq_a, enum myers_align_mode mode, const char* seq_b, int maxd,
@@ -381,7 +393,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

@@ -24,13 +24,15 @@
 #include "mia_trim_kernels.h"
 #include "mia_peak_kernels.h"
 #include "mia_iter_kernels.h"
+#include "mia_ma_region_kernels.h"
 
 using namespace mia;
 
 // timed stages (HIP events on the context's stream around the kernel launches of that kind)
-enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_COUNT };
+enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_COUNT };
 static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan",
-                                                   "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1"};
+                                                   "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select",
+                                                   "k_ma_region_render"};
 
 // One device block for every small counter of an iteration (planner bins and header, filter / band-pipeline counters, link
 // count, cull and tally flags, insert-event count): one memset at the start of the alignment clears them all, and one copy
@@ -239,6 +241,14 @@ struct mia_hip_ctx {
   double pass1_ms = 0; int64_t pass1_filtered = 0, pass1_anchored = 0;   // reads of the last pass-1 call that the diagonal filter decided
   double myers_kernel_ms = 0; bool myers_no_lanes = false, myers_no_ond = false;   // the kernels of the last mia_hip_myers call (HIP events)
   int64_t trim_escapes = 0;   // reads of the last mia_hip_trim call that took the exact scalar path
+  // the records of the last mia_hip_ma_tally stay on the device for mia_hip_ma_region: start, col_off, seq, the INS_POS pairs (and
+  // which pairs each record owns), ref->gaps; the region's column map, selected records and text
+  bool ma_resident = false; int64_t ma_n = 0; int32_t ma_L = 0;
+  int32_t *d_ma_start = nullptr, *d_ma_gaps = nullptr, *d_ma_ipos = nullptr, *d_ma_rec_ins = nullptr, *d_ma_ins_list = nullptr;
+  int64_t *d_ma_coff = nullptr, *d_ma_ioff = nullptr, *d_ma_colmap = nullptr, *d_ma_rows = nullptr;
+  char *d_ma_seq = nullptr, *d_ma_ib = nullptr, *d_ma_text = nullptr; int64_t ma_text_cap = 0;
+  unsigned long long* d_ma_ctl = nullptr;
+  int32_t ma_first = 0, ma_last = -1; int64_t ma_rows = 0, ma_width = 0; bool ma_region_done = false;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------
@@ -461,6 +471,9 @@ extern "C" void mia_hip_destroy(mia_hip_ctx* ctx) {
   if (ctx->d_slabs_open) (void)hipFree(ctx->d_slabs_open);
   if (ctx->d_open_list) (void)hipFree(ctx->d_open_list);
   if (ctx->d_kbits) (void)hipFree(ctx->d_kbits);
+  for (void* p : {(void*)ctx->d_ma_start, (void*)ctx->d_ma_gaps, (void*)ctx->d_ma_ipos, (void*)ctx->d_ma_rec_ins, (void*)ctx->d_ma_ins_list, (void*)ctx->d_ma_coff,
+                  (void*)ctx->d_ma_ioff, (void*)ctx->d_ma_colmap, (void*)ctx->d_ma_rows, (void*)ctx->d_ma_seq, (void*)ctx->d_ma_ib, (void*)ctx->d_ma_text, (void*)ctx->d_ma_ctl})
+    if (p) (void)hipFree(p);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   delete ctx;

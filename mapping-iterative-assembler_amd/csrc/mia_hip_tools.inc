@@ -120,18 +120,35 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   if (rc) return rc;
   const int Lp = ctx->tb.Lp;
   const int64_t chars = n ? col_off[n] : 0;
-  int32_t *d_start = nullptr, *d_irec = nullptr, *d_ipos = nullptr;
+  // the INS_POS pairs by record (mia_hip_ma_region fetches a record's own range): a stable counting sort of the pair numbers
+  if (n > INT32_MAX - 1 || n_ins > INT32_MAX - 1) { ctx->err = "ma_tally: more than 2^31 records or INS_POS pairs"; return MIA_HIP_ERR_ARG; }
+  std::vector<int32_t> rec_ins((size_t)n + 1, 0), ins_list((size_t)n_ins);
+  for (int64_t e = 0; e < n_ins; e++) rec_ins[(size_t)ins_record[e] + 1]++;
+  for (int64_t r = 0; r < n; r++) rec_ins[(size_t)r + 1] += rec_ins[(size_t)r];
+  {
+    std::vector<int32_t> cursor(rec_ins.begin(), rec_ins.end() - 1);
+    for (int64_t e = 0; e < n_ins; e++) ins_list[(size_t)cursor[(size_t)ins_record[e]]++] = (int32_t)e;
+  }
+  // The records stay on the device behind this call (mia_hip_ma_region reads them): buffers of the context, made here, before anything
+  // is queued.  Strand, depth codes and the pairs' record numbers are needed by the tally alone.
+  ctx->ma_resident = false;
+  ctx->ma_region_done = false;
+  int32_t* d_irec = nullptr;
   uint8_t* d_rev = nullptr;
-  int64_t *d_coff = nullptr, *d_ioff = nullptr;
-  char *d_seq = nullptr, *d_smp = nullptr, *d_ib = nullptr;
+  char* d_smp = nullptr;
   ScopeFree guard;   // every temporary is released on any return
-  for (void** pp : {(void**)&d_start, (void**)&d_rev, (void**)&d_coff, (void**)&d_seq, (void**)&d_smp, (void**)&d_irec, (void**)&d_ipos,
-                    (void**)&d_ioff, (void**)&d_ib})
-    guard.watch(pp);
-  int rcx = dev_alloc(ctx, &d_start, (size_t)n + 1) | dev_alloc(ctx, &d_rev, (size_t)n + 1) | dev_alloc(ctx, &d_coff, (size_t)n + 1) |
-            dev_alloc(ctx, &d_seq, (size_t)chars + 1) | dev_alloc(ctx, &d_smp, (size_t)chars + 1) | dev_alloc(ctx, &d_irec, (size_t)n_ins + 1) |
-            dev_alloc(ctx, &d_ipos, (size_t)n_ins + 1) | dev_alloc(ctx, &d_ioff, (size_t)n_ins + 1) | dev_alloc(ctx, &d_ib, (size_t)ins_chars + 1);
+  for (void** pp : {(void**)&d_rev, (void**)&d_smp, (void**)&d_irec}) guard.watch(pp);
+  int rcx = dev_alloc(ctx, &ctx->d_ma_start, (size_t)n + 1) | dev_alloc(ctx, &d_rev, (size_t)n + 1) | dev_alloc(ctx, &ctx->d_ma_coff, (size_t)n + 1) |
+            dev_alloc(ctx, &ctx->d_ma_seq, (size_t)chars + 1) | dev_alloc(ctx, &d_smp, (size_t)chars + 1) | dev_alloc(ctx, &d_irec, (size_t)n_ins + 1) |
+            dev_alloc(ctx, &ctx->d_ma_ipos, (size_t)n_ins + 1) | dev_alloc(ctx, &ctx->d_ma_ioff, (size_t)n_ins + 1) |
+            dev_alloc(ctx, &ctx->d_ma_ib, (size_t)ins_chars + 1) | dev_alloc(ctx, &ctx->d_ma_gaps, (size_t)ref_len) |
+            dev_alloc(ctx, &ctx->d_ma_rec_ins, (size_t)n + 1) | dev_alloc(ctx, &ctx->d_ma_ins_list, (size_t)n_ins + 1) |
+            dev_alloc(ctx, &ctx->d_ma_colmap, (size_t)ref_len + 1) | dev_alloc(ctx, &ctx->d_ma_rows, (size_t)n + 1) |
+            dev_alloc(ctx, &ctx->d_ma_ctl, (size_t)MAR_STATE + (size_t)(n / MAR_PER_WG) + 2);
   if (rcx) return MIA_HIP_ERR_NOMEM;
+  int32_t* const d_start = ctx->d_ma_start; int32_t* const d_ipos = ctx->d_ma_ipos;
+  int64_t* const d_coff = ctx->d_ma_coff; int64_t* const d_ioff = ctx->d_ma_ioff;
+  char* const d_seq = ctx->d_ma_seq; char* const d_ib = ctx->d_ma_ib;
   hipError_t e = hipSuccess;
   auto up = [&](void* d, const void* h, size_t b) { if (e == hipSuccess && b) e = hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream); };
   auto zero = [&](void* d, size_t b) { if (e == hipSuccess) e = hipMemsetAsync(d, 0, b, ctx->stream); };
@@ -143,6 +160,9 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   up(d_start, start, (size_t)n * 4); up(d_rev, revcom, (size_t)n); up(d_coff, col_off, (size_t)(n + 1) * 8);
   up(d_seq, seq, (size_t)chars); up(d_smp, smp, (size_t)chars);
   if (n_ins) { up(d_irec, ins_record, (size_t)n_ins * 4); up(d_ipos, ins_pos, (size_t)n_ins * 4); up(d_ioff, ins_off, (size_t)(n_ins + 1) * 8); up(d_ib, ins_bases, (size_t)ins_chars); }
+  up(ctx->d_ma_gaps, gaps, (size_t)ref_len * 4);
+  up(ctx->d_ma_rec_ins, rec_ins.data(), (size_t)(n + 1) * 4);
+  up(ctx->d_ma_ins_list, ins_list.data(), (size_t)n_ins * 4);
   if (e == hipSuccess && n > 0) {
     MaRecords mr{n, d_start, d_rev, d_coff, d_seq, d_smp};
     hipLaunchKernelGGL(k_ma_tally, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, mr, ctx->d_pssm, ctx->tb);
@@ -161,6 +181,62 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   if (ctx->n_events_host > ctx->tb.cap_events) ctx->n_events_host = ctx->tb.cap_events;
   ctx->tallied = true;
   ctx->consensus_done = false;
+  ctx->ma_resident = true;
+  ctx->ma_n = n;
+  ctx->ma_L = ref_len;
+  return MIA_HIP_OK;
+}
+
+// print_region's rows (src/map_align.c:660-750) for the records of the last mia_hip_ma_tally: see mia_ma_region_kernels.h
+extern "C" int mia_hip_ma_region(mia_hip_ctx* ctx, int32_t first, int32_t last, int64_t* n_rows, int64_t* width) {
+  if (!ctx || !n_rows || !width) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_region"; return MIA_HIP_ERR_STATE; }
+  if (first <= last && (first < 0 || last >= ctx->ma_L)) { ctx->err = "ma_region: the region reaches outside the reference"; return MIA_HIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->ma_region_done = false;
+  const int64_t n = ctx->ma_n;
+  const int32_t n_wgs = (int32_t)((n + MAR_PER_WG - 1) / MAR_PER_WG);
+  MaRegionView v{n, ctx->d_ma_start, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos, ctx->d_ma_ioff, ctx->d_ma_ib,
+                 ctx->d_ma_gaps, first, last, ctx->d_ma_colmap};
+  HIPCHK(hipMemsetAsync(ctx->d_ma_ctl, 0, ((size_t)MAR_STATE + (size_t)n_wgs) * 8, ctx->stream));
+  if (stage_launch(ctx, STG_MA_SELECT, k_ma_region_select, dim3((unsigned)n_wgs + 1), dim3(MAR_THREADS), 0, ctx->stream, v, n_wgs, ctx->d_ma_ctl,
+                   ctx->d_ma_colmap, ctx->d_ma_rows))
+    return MIA_HIP_ERR_NOMEM;
+  HIPCHK(hipGetLastError());
+  unsigned long long hdr[MAR_STATE] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(hdr, ctx->d_ma_ctl, sizeof hdr, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const int64_t rows = (int64_t)hdr[MAR_ROWS], w = (int64_t)hdr[MAR_WIDTH];
+  if (rows < 0 || rows > n || w < 0) { ctx->err = "ma_region: the selection came back inconsistent"; return MIA_HIP_ERR_DEVICE; }
+  if (rows > 0 && w > 0) {
+    if (w > INT64_MAX / rows) { ctx->err = "ma_region: the text does not fit"; return MIA_HIP_ERR_NOMEM; }
+    if (ctx->ma_text_cap < rows * w) {
+      ctx->ma_text_cap = 0;
+      if (dev_alloc(ctx, &ctx->d_ma_text, (size_t)(rows * w))) return MIA_HIP_ERR_NOMEM;
+      ctx->ma_text_cap = rows * w;
+    }
+    if (stage_launch(ctx, STG_MA_RENDER, k_ma_region_render, dim3((unsigned)((rows + MAR_THREADS / 64 - 1) / (MAR_THREADS / 64))), dim3(MAR_THREADS), 0,
+                     ctx->stream, v, ctx->d_ma_rows, rows, w, ctx->d_ma_text))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  ctx->ma_first = first; ctx->ma_last = last; ctx->ma_rows = rows; ctx->ma_width = w;
+  ctx->ma_region_done = true;
+  *n_rows = rows;
+  *width = w;
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_region(mia_hip_ctx* ctx, int64_t* rows, char* text, int64_t cap_rows) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident || !ctx->ma_region_done) { ctx->err = "ma_region first"; return MIA_HIP_ERR_STATE; }
+  if (cap_rows < ctx->ma_rows) { ctx->err = "get_ma_region: buffers too small"; return MIA_HIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (rows && ctx->ma_rows > 0) HIPCHK(hipMemcpyAsync(rows, ctx->d_ma_rows, (size_t)ctx->ma_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (text && ctx->ma_rows > 0 && ctx->ma_width > 0)
+    HIPCHK(hipMemcpyAsync(text, ctx->d_ma_text, (size_t)(ctx->ma_rows * ctx->ma_width), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }
 

@@ -1,9 +1,9 @@
-// ma_hip -- the reference's `ma` report tool (/root/reference/src/map_assembler.c) for the formats that
-// are computed from the column tallies: -f 5 (assembled sequence as FASTA), -f 41 and -f 4 (per-column
-// table).  The .maln text is parsed here exactly as read_ma does (src/map_alignment.c:384-607); the
-// add_base loops of show_consensus / find_ins_cons run on the GPU (mia_hip_ma_tally, every record counts,
-// dropped or not); calling, phred score and printing follow src/map_alignment.c:107-220,
-// src/map_align.c:152-227,294-391 and src/io.c:929-951.  No CPU fallback.
+// ma_hip -- the reference's `ma` report tool (/root/reference/src/map_assembler.c): -f 1 (clustalw, the default), -f 2 (line
+// format), -f 5 (assembled sequence as FASTA), -f 41 and -f 4 (per-column table), -f 6 and -f 61 (the fragments of a region,
+// -R).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
+// find_ins_cons run on the GPU (mia_hip_ma_tally, every record counts, dropped or not), and so do the selection and the
+// rows of the region view (mia_hip_ma_region); calling, phred score and printing follow src/map_alignment.c:107-220,
+// src/map_align.c:152-227,294-391,543-759 and src/io.c:929-1085.  Formats 3 and 7 and -m stay outside.  No CPU fallback.
 #include <ctype.h>
 #include <float.h>
 #include <getopt.h>
@@ -22,112 +22,21 @@
 
 namespace {
 
-constexpr int PSSM_DEPTH = 15, FASTA_LINE_WIDTH = 60;   // src/params.h:20-21
+constexpr int FASTA_LINE_WIDTH = 60, CLUSTALW_LINE_WIDTH = 60;   // src/params.h:19-20
 using namespace maln_text;
+typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 5, 41 or 4>\n   -I <ID to assign to assembly sequence>\n"
-         "ma_hip reports the assembled sequence (-f 5) or the per-column table (-f 41 all positions, -f 4 positions that\n"
-         "differ from the reference) of a .maln file written by mia, as the reference's ma does; the tallies are\n"
-         "computed on the MI355X.  The other ma formats are outside the accelerated path.\n");
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6 or 61>\n   -R <REGION_START:REGION_END>\n"
+         "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n"
+         "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
+         "(-f 1 clustalw, the default; -f 2 one line each plus coverage), the per-column table (-f 41 all positions, -f 4\n"
+         "positions that differ from the reference), the assembled sequence (-f 5), and the reference, the consensus and every\n"
+         "fragment of a region (-f 6, as multi-FASTA -f 61; -R, default 90:109).  Tallies, the selection of the fragments and\n"
+         "their rows are computed on the MI355X.  Formats 3 and 7 and -m are outside the accelerated path.\n");
 }
 
-struct Maln {
-  std::string ref_id, ref_seq;
-  int L = 0;
-  std::vector<int32_t> gaps;
-  int32_t fpsm[31][5][5], rpsm[31][5][5];
-  std::vector<int32_t> start, ins_record, ins_pos;
-  std::vector<uint8_t> revcom;
-  std::vector<int64_t> col_off, ins_off;
-  std::string seq, smp, ins_bases;
-};
-
-void bad(const char* what, const char* fn) { fprintf(stderr, what, fn); exit(1); }
-
-void read_ma(const char* fn, Maln* m) {
-  std::string buf;
-  if (!slurp(fn, &buf)) { fprintf(stderr, "Cannot open %s\n", fn); exit(1); }
-  Cursor c{buf.data(), buf.data() + buf.size()};
-  std::string line, tok;
-  c.line(&line);
-  if (line.find("/* map_alignment") == std::string::npos) bad("%s does not look like a map_alignment input file\n", fn);
-  int nas = 0, tmp = 0;
-  c.line(&line); field_int(line, "MALN_NAS", &nas);
-  c.line(&line);                       // MALN_SIZ: only sizes an array
-  c.line(&line);                       // MALN_COC: overridden by -c (src/map_assembler.c:191)
-  c.line(&line);
-  if (line.find("__REFERENCE__") == std::string::npos) bad("Do not see reference sequence header in %s\n", fn);
-  c.line(&line); field(line, "ID", &m->ref_id);
-  c.line(&line);                       // DESC
-  c.line(&line); field_int(line, "LEN", &m->L);
-  c.line(&line);                       // SIZE
-  c.line(&line); field(line, "SEQ", &m->ref_seq);
-  if ((int)m->ref_seq.size() != m->L) {
-    fprintf(stderr, "Reported length of reference sequence %d is not observed length %d\n", m->L, (int)m->ref_seq.size());
-    exit(1);
-  }
-  c.literal("GAPS");
-  m->gaps.assign((size_t)m->L, 0);
-  for (int i = 0; i < m->L; i++) { long v = 0; if (c.integer(&v)) m->gaps[(size_t)i] = (int32_t)v; }
-  while (c.p < c.end && *c.p != '\n') c.p++;
-  if (c.p < c.end) c.p++;
-  c.line(&line);
-  if (line.find("__PSSM__") == std::string::npos) { fprintf(stderr, "Do not see __PSSM__ line in %s\n", fn); exit(2); }
-  int depth = PSSM_DEPTH;
-  c.line(&line); field_int(line, "DEPTH", &depth);
-  c.line(&line);
-  if (line.find("FPSM:") == std::string::npos) { fprintf(stderr, "Do not see the FPSM: in %s\n", fn); exit(2); }
-  memset(m->fpsm, 0, sizeof m->fpsm);
-  memset(m->rpsm, 0, sizeof m->rpsm);
-  read_matrices(c, depth, m->fpsm);
-  c.line(&line);
-  if (line.find("RPSM:") == std::string::npos) { fprintf(stderr, "Do not see the RPSM: in %s\n", fn); exit(2); }
-  read_matrices(c, depth, m->rpsm);
-  c.line(&line);
-  if (line.find("__ALNSEQS__") == std::string::npos) bad("Do not see __ALNSEQS__ line in %s\n", fn);
-  m->col_off.push_back(0);
-  m->ins_off.push_back(0);
-  for (int r = 0; r < nas; r++) {
-    int start = 0, end = 0, rc = 0;
-    std::string seq, smp;
-    c.line(&line);                                  // ID
-    c.line(&line);                                  // DESC
-    c.line(&line);                                  // SCORE
-    c.line(&line);                                  // NUM_INPUTS, if there
-    if (field_int(line, "NUM_INPUTS", &tmp)) c.line(&line);
-    field_int(line, "START", &start);
-    c.line(&line); field_int(line, "END", &end);
-    c.line(&line); field_int(line, "RC", &rc);
-    c.line(&line);                                  // TR
-    c.line(&line);                                  // DR, if there
-    if (field_int(line, "DR", &tmp)) c.line(&line);
-    // SEG
-    c.line(&line); field(line, "SEQ", &seq);
-    c.line(&line); field(line, "SMP", &smp);
-    const int ncols = end - start + 1;
-    if (ncols < 0 || (int)seq.size() < ncols || (int)smp.size() < ncols || start < 0) {
-      fprintf(stderr, "record %d of %s: SEQ/SMP shorter than START..END\n", r, fn);
-      exit(1);
-    }
-    m->start.push_back(start);
-    m->revcom.push_back(rc ? 1 : 0);
-    m->seq.append(seq, 0, (size_t)ncols);
-    m->smp.append(smp, 0, (size_t)ncols);
-    m->col_off.push_back((int64_t)m->seq.size());
-    c.literal("INS_POS");
-    for (;;) {
-      const char* save = c.p;
-      long pos = 0;
-      if (!c.integer(&pos)) break;                   // (white space already consumed, as fscanf does)
-      if (!c.token(&tok)) { c.p = save; break; }
-      m->ins_record.push_back(r);
-      m->ins_pos.push_back((int32_t)pos);
-      m->ins_bases += tok;
-      m->ins_off.push_back((int64_t)m->ins_bases.size());
-    }
-  }
-}
+void read_ma(const char* fn, Maln* m) { read_maln_file(fn, m); }
 
 // find_phred_qscore, src/map_align.c:152-205
 int phred(int sA, int sC, int sG, int sT) {
@@ -165,6 +74,49 @@ void show_single_pos(int ref_pos, char ref_base, char cons_base, const Counts& b
          b.sG, b.sT, phred(b.sA, b.sC, b.sG, b.sT), frac);
 }
 
+// fasta_aln_print, src/io.c:953-973
+void fasta_aln_print(const char* seq, size_t len, const std::string& id) {
+  printf(">%s\n", id.c_str());
+  size_t i = 0;
+  for (; i + FASTA_LINE_WIDTH <= len; i += FASTA_LINE_WIDTH) {
+    for (size_t k = 0; k < (size_t)FASTA_LINE_WIDTH; k++) fputc(seq[i + k] == ' ' ? 'X' : seq[i + k], stdout);
+    fputc('\n', stdout);
+  }
+  for (; i < len; i++) fputc(seq[i] == ' ' ? 'X' : seq[i], stdout);
+  fputc('\n', stdout);
+}
+
+// clustalw_print_cons, src/io.c:976-1029
+void clustalw_print_cons(const std::string& cons, const std::string& aln_ref, const std::string& ref_id) {
+  std::string ref_start = ref_id.substr(0, 15);
+  ref_start.resize(17, ' ');
+  printf("CLUSTAL W (1.8) multiple sequence alignment\n");
+  for (size_t at = 0; at < cons.size(); at += CLUSTALW_LINE_WIDTH) {
+    const std::string r = aln_ref.substr(at, CLUSTALW_LINE_WIDTH);
+    std::string c = cons.substr(at, CLUSTALW_LINE_WIDTH);
+    for (char& ch : c) if (ch == ' ') ch = 'X';
+    printf("%s%s\nConsensus        %s\n                 ", ref_start.c_str(), r.c_str(), c.c_str());
+    for (size_t i = 0; i < c.size(); i++) fputc(i < r.size() && r[i] == c[i] ? '*' : ' ', stdout);
+    printf("\n\n\n");
+  }
+}
+
+// color_print, src/io.c:1044-1085
+void color_print(const char* s, size_t len) {
+  for (size_t i = 0; i < len; i++) {
+    switch (s[i]) {
+      case 'a': case 'A': printf("\33[37;42m"); break;
+      case 'c': case 'C': printf("\33[37;44m"); break;
+      case 'g': case 'G': printf("\33[37;40m"); break;
+      case 't': case 'T': printf("\33[37;41m"); break;
+      case '-': printf("\33[47;30m"); break;
+      default: printf("\33[0m");
+    }
+    fputc(s[i], stdout);
+  }
+  printf("\33[0m\n");
+}
+
 void die(mia_hip_ctx* g, const char* what) {
   fprintf(stderr, "%s: %s\n", what, g ? mia_hip_last_error(g) : "no context");
   exit(1);
@@ -175,7 +127,8 @@ void die(mia_hip_ctx* g, const char* what) {
 int main(int argc, char* argv[]) {
   std::string ma_in_fn, assign_id;
   bool id_assigned = false, in_ma = false, any_arg = false;
-  int cons_scheme = 1, out_format = 1, gpu = 0;
+  int cons_scheme = 1, out_format = 1, gpu = 0, reg_start = 90, reg_end = 109;
+  bool in_color = false;
   double score_int = -1.0, score_slo = -1.0;
   int ich;
   // the reference's option string (src/map_assembler.c:113) plus -g <gpu>
@@ -185,10 +138,10 @@ int main(int argc, char* argv[]) {
       case 'c': cons_scheme = atoi(optarg); any_arg = true; break;
       case 'i': any_arg = true; break;                 // parsed and never used by the reference either
       case 'f': out_format = atoi(optarg); any_arg = true; break;
-      case 'R': any_arg = true; break;
+      case 'R': parse_region(optarg, &reg_start, &reg_end); any_arg = true; break;
       case 's': score_slo = atof(optarg); any_arg = true; break;
       case 'b': score_int = atof(optarg); any_arg = true; break;
-      case 'C': break;
+      case 'C': in_color = true; break;
       case 'm': fprintf(stderr, "option -m (rewrite the .maln) is outside the MI355X-accelerated path and is not supported by ma_hip\n"); exit(1);
       case 'M': ma_in_fn = optarg; in_ma = true; any_arg = true; break;
       case 'd': any_arg = true; break;
@@ -197,8 +150,8 @@ int main(int argc, char* argv[]) {
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 5 && out_format != 4 && out_format != 41) {
-    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 5, 41 and 4 are); use the reference's ma\n", out_format);
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61) {
+    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6 and 61 are); use the reference's ma\n", out_format);
     exit(1);
   }
   Maln m;
@@ -228,7 +181,7 @@ int main(int argc, char* argv[]) {
     mia_hip_destroy(g);
     return 0;
   }
-  // formats 4 / 41: BaseCounts of every column from the device, calls and the double-valued columns here
+  // the other formats: BaseCounts of every column from the device, calls and the double-valued columns here
   std::vector<int32_t> tally((size_t)MIA_HIP_TALLY_WORDS * (size_t)(L + 1)), dgaps((size_t)L + 1), ins_off((size_t)L + 1);
   {
     std::string scratch((size_t)L * 2 + (1 << 20), '\0');
@@ -242,6 +195,72 @@ int main(int argc, char* argv[]) {
   if (slots > 0 && mia_hip_get_ins_tally(g, nullptr, ins_tally.data(), slots, nullptr) != MIA_HIP_OK) die(g, "get_ins_tally");
   const size_t Lp = (size_t)L + 1;
   auto word = [&](int w, int p) { return tally[(size_t)w * Lp + (size_t)p]; };
+  if (out_format != 4 && out_format != 41) {
+    // consensus, gapped reference and coverage of columns first .. last as show_consensus (formats 1, 2: the whole reference, no
+    // insert columns in front of column 0) and print_region (formats 6, 61: those too) build them
+    const bool region = out_format == 6 || out_format == 61;
+    int first = 0, last = L - 1;
+    if (region) clamp_region(reg_start, reg_end, L, &first, &last);
+    std::string cons, aln_ref;
+    std::vector<int> cov;
+    for (int p = first; p <= last; p++) {
+      const int gp = m.gaps[(size_t)p] > 0 ? m.gaps[(size_t)p] : 0;
+      if (gp > 0 && (p > 0 || region)) {              // find_ins_cons (src/map_align.c:444-510); no record spans column 0
+        const int span = p > 0 ? word(10 /* T_SPAN */, p) : 0;
+        for (int j = 0; j < gp; j++) {
+          static const int32_t none[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+          const int32_t* t = p > 0 ? &ins_tally[(size_t)(ins_off[(size_t)p] + j) * 9] : none;
+          Counts b{t[0], t[1], t[2], t[3], span - t[4], span, t[5], t[6], t[7], t[8]};
+          double frac = 0.0;
+          cons += find_consensus(b, cons_scheme, &frac);
+          aln_ref += '-';
+          cov.push_back(span);
+        }
+      }
+      Counts b{word(0, p), word(1, p), word(2, p), word(3, p), word(4, p), word(5, p), word(6, p), word(7, p), word(8, p), word(9, p)};
+      double frac = 0.0;
+      cons += find_consensus(b, cons_scheme, &frac);
+      aln_ref += m.ref_seq[(size_t)p];
+      cov.push_back(b.cov);
+    }
+    if (out_format == 1) clustalw_print_cons(cons, aln_ref, m.ref_id);
+    else if (out_format == 2) {                       // line_print_cons, src/io.c:1032-1042
+      printf("Consensus, %s, coverage:\n%s\n%s\n", m.ref_id.c_str(), cons.c_str(), aln_ref.c_str());
+      for (int c : cov) printf("%d ", c);
+      printf("\n");
+    } else {
+      // print_region, src/map_align.c:635-750: the rows of the overlapping records come from the device
+      int64_t n_rows = 0, width = 0;
+      if (mia_hip_ma_region(g, first, last, &n_rows, &width) != MIA_HIP_OK) die(g, "ma_region");
+      if (width != (int64_t)aln_ref.size()) { fprintf(stderr, "ma_hip: the region's rows are %lld wide, its reference line %zu\n", (long long)width, aln_ref.size()); exit(1); }
+      std::vector<int64_t> rows((size_t)n_rows + 1);
+      std::string text((size_t)(n_rows * width) + 1, '\0');
+      if (mia_hip_get_ma_region(g, rows.data(), &text[0], n_rows) != MIA_HIP_OK) die(g, "get_ma_region");
+      if (out_format == 61) {
+        fasta_aln_print(aln_ref.data(), aln_ref.size(), m.ref_id);
+        fasta_aln_print(cons.data(), cons.size(), "Consensus");
+      } else if (in_color) {
+        printf("%-20.20s ", m.ref_id.c_str());
+        color_print(aln_ref.data(), aln_ref.size());
+        printf("%-20.20s ", "Consensus");
+        color_print(cons.data(), cons.size());
+      } else {
+        printf("%-20.20s %s\n%-20s %s\n", m.ref_id.c_str(), aln_ref.c_str(), "Consensus", cons.c_str());
+      }
+      for (int64_t i = 0; i < n_rows; i++) {
+        const std::string label = region_label(m.rec[(size_t)rows[(size_t)i]]);
+        const char* row = text.data() + (size_t)(i * width);
+        if (out_format == 61) fasta_aln_print(row, (size_t)width, label);
+        else {
+          printf("%-20.20s ", label.c_str());
+          if (in_color) color_print(row, (size_t)width);
+          else { fwrite(row, 1, (size_t)width, stdout); fputc('\n', stdout); }
+        }
+      }
+    }
+    mia_hip_destroy(g);
+    return 0;
+  }
   for (int p = 0; p < L; p++) {
     if (m.gaps[(size_t)p] > 0 && p > 0) {           // find_ins_cons (src/map_align.c:444-510)
       const int span = word(10 /* T_SPAN */, p);

@@ -1,6 +1,7 @@
 // maln_text.h -- reading the text of a .maln file the way the reference's read_ma does (src/map_alignment.c:384-607:
 // fgets with MAX_LINE_LEN, sscanf "KEY %s" / "KEY %d", fscanf " %d %s" for the insert list).  Shared by ma_hip and
-// ccheck_hip; each keeps its own record layout.
+// ccheck_hip; ccheck_hip keeps its own record layout, ma_hip's (MalnFile, read_maln_file) is here so that a host-only caller can
+// read a .maln the same way.
 #pragma once
 #include <ctype.h>
 #include <stdint.h>
@@ -8,7 +9,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
+#include <vector>
 
 namespace maln_text {
 
@@ -97,6 +100,167 @@ inline bool slurp(const char* fn, std::string* buf) {
   while ((n = fread(chunk, 1, sizeof chunk, f)) > 0) buf->append(chunk, n);
   fclose(f);
   return true;
+}
+
+// ---- a whole .maln as ma reads it (read_ma, src/map_alignment.c:384-607) -------------------------------------------------
+constexpr int PSSM_DEPTH = 15;   // src/params.h:21
+
+struct MalnRecord {
+  std::string id;
+  int start = 0, end = 0, rc = 0, trimmed = 0, num_inputs = 1;
+  char segment = 'n';
+  std::string seq, smp;                       // columns start .. end
+  std::vector<int32_t> ins_pos;               // INS_POS pairs, in file order
+  std::vector<std::string> ins_seq;
+};
+
+// The records flattened the way mia_hip_ma_tally takes them, in the order of `rec`.
+struct MalnFile {
+  std::string ref_id, ref_seq;
+  int L = 0;
+  std::vector<int32_t> gaps;
+  int32_t fpsm[31][5][5], rpsm[31][5][5];
+  std::vector<MalnRecord> rec;
+  std::vector<int32_t> start, ins_record, ins_pos;
+  std::vector<uint8_t> revcom;
+  std::vector<int64_t> col_off, ins_off;
+  std::string seq, smp, ins_bases;
+};
+
+inline void maln_bad(const char* what, const char* fn) { fprintf(stderr, what, fn); exit(1); }
+
+// sort_aln_frags (src/map_alignment.c:630-633, alnSeqCmp src/map_align.c:393-414): by start, then end.  glibc's qsort is a merge
+// sort at these sizes, so records that compare equal keep their order.
+inline void sort_records(MalnFile* m) {
+  std::stable_sort(m->rec.begin(), m->rec.end(), [](const MalnRecord& a, const MalnRecord& b) { return a.start != b.start ? a.start < b.start : a.end < b.end; });
+}
+
+inline void flatten_records(MalnFile* m) {
+  m->start.clear(); m->revcom.clear(); m->seq.clear(); m->smp.clear(); m->ins_record.clear(); m->ins_pos.clear(); m->ins_bases.clear();
+  m->col_off.assign(1, 0);
+  m->ins_off.assign(1, 0);
+  for (size_t r = 0; r < m->rec.size(); r++) {
+    const MalnRecord& a = m->rec[r];
+    m->start.push_back(a.start);
+    m->revcom.push_back(a.rc ? 1 : 0);
+    m->seq += a.seq;
+    m->smp += a.smp;
+    m->col_off.push_back((int64_t)m->seq.size());
+    for (size_t k = 0; k < a.ins_pos.size(); k++) {
+      m->ins_record.push_back((int32_t)r);
+      m->ins_pos.push_back(a.ins_pos[k]);
+      m->ins_bases += a.ins_seq[k];
+      m->ins_off.push_back((int64_t)m->ins_bases.size());
+    }
+  }
+}
+
+inline void read_maln_file(const char* fn, MalnFile* m) {
+  std::string buf;
+  if (!slurp(fn, &buf)) { fprintf(stderr, "Cannot open %s\n", fn); exit(1); }
+  Cursor c{buf.data(), buf.data() + buf.size()};
+  std::string line, tok;
+  c.line(&line);
+  if (line.find("/* map_alignment") == std::string::npos) maln_bad("%s does not look like a map_alignment input file\n", fn);
+  int nas = 0, tmp = 0;
+  c.line(&line); field_int(line, "MALN_NAS", &nas);
+  c.line(&line);                       // MALN_SIZ: only sizes an array
+  c.line(&line);                       // MALN_COC: overridden by -c (src/map_assembler.c:191)
+  c.line(&line);
+  if (line.find("__REFERENCE__") == std::string::npos) maln_bad("Do not see reference sequence header in %s\n", fn);
+  c.line(&line); field(line, "ID", &m->ref_id);
+  c.line(&line);                       // DESC
+  c.line(&line); field_int(line, "LEN", &m->L);
+  c.line(&line);                       // SIZE
+  c.line(&line); field(line, "SEQ", &m->ref_seq);
+  if ((int)m->ref_seq.size() != m->L) {
+    fprintf(stderr, "Reported length of reference sequence %d is not observed length %d\n", m->L, (int)m->ref_seq.size());
+    exit(1);
+  }
+  c.literal("GAPS");
+  m->gaps.assign((size_t)m->L, 0);
+  for (int i = 0; i < m->L; i++) { long v = 0; if (c.integer(&v)) m->gaps[(size_t)i] = (int32_t)v; }
+  while (c.p < c.end && *c.p != '\n') c.p++;
+  if (c.p < c.end) c.p++;
+  c.line(&line);
+  if (line.find("__PSSM__") == std::string::npos) { fprintf(stderr, "Do not see __PSSM__ line in %s\n", fn); exit(2); }
+  int depth = PSSM_DEPTH;
+  c.line(&line); field_int(line, "DEPTH", &depth);
+  c.line(&line);
+  if (line.find("FPSM:") == std::string::npos) { fprintf(stderr, "Do not see the FPSM: in %s\n", fn); exit(2); }
+  memset(m->fpsm, 0, sizeof m->fpsm);
+  memset(m->rpsm, 0, sizeof m->rpsm);
+  read_matrices(c, depth, m->fpsm);
+  c.line(&line);
+  if (line.find("RPSM:") == std::string::npos) { fprintf(stderr, "Do not see the RPSM: in %s\n", fn); exit(2); }
+  read_matrices(c, depth, m->rpsm);
+  c.line(&line);
+  if (line.find("__ALNSEQS__") == std::string::npos) maln_bad("Do not see __ALNSEQS__ line in %s\n", fn);
+  m->rec.clear();
+  m->rec.reserve((size_t)(nas > 0 ? nas : 0));
+  for (int r = 0; r < nas; r++) {
+    MalnRecord a;
+    std::string seq, smp;
+    c.line(&line); field(line, "ID", &a.id);
+    c.line(&line);                                  // DESC
+    c.line(&line);                                  // SCORE
+    c.line(&line);                                  // NUM_INPUTS, if there (else 1)
+    if (field_int(line, "NUM_INPUTS", &a.num_inputs)) c.line(&line);
+    field_int(line, "START", &a.start);
+    c.line(&line); field_int(line, "END", &a.end);
+    c.line(&line); field_int(line, "RC", &a.rc);
+    c.line(&line); field_int(line, "TR", &a.trimmed);
+    c.line(&line);                                  // DR, if there
+    if (field_int(line, "DR", &tmp)) c.line(&line);
+    if (field(line, "SEG", &tok)) a.segment = tok[0];
+    c.line(&line); field(line, "SEQ", &seq);
+    c.line(&line); field(line, "SMP", &smp);
+    const int ncols = a.end - a.start + 1;
+    if (ncols < 0 || (int)seq.size() < ncols || (int)smp.size() < ncols || a.start < 0) {
+      fprintf(stderr, "record %d of %s: SEQ/SMP shorter than START..END\n", r, fn);
+      exit(1);
+    }
+    a.seq.assign(seq, 0, (size_t)ncols);
+    a.smp.assign(smp, 0, (size_t)ncols);
+    c.literal("INS_POS");
+    for (;;) {
+      const char* save = c.p;
+      long pos = 0;
+      if (!c.integer(&pos)) break;                   // (white space already consumed, as fscanf does)
+      if (!c.token(&tok)) { c.p = save; break; }
+      a.ins_pos.push_back((int32_t)pos);
+      a.ins_seq.push_back(tok);
+    }
+    m->rec.push_back(std::move(a));
+  }
+  sort_records(m);
+  flatten_records(m);
+}
+
+// ---- ma -R (parse_region, src/map_assembler.c:73-82) and print_region's clamp (src/map_align.c:561-567) --------------------
+// sscanf "%d:%d": what does not parse keeps its default; the reference's swap assigns the smaller value to both ends.
+inline void parse_region(const char* s, int* reg_start, int* reg_end) {
+  sscanf(s, "%d:%d", reg_start, reg_end);
+  if (*reg_start > *reg_end) { *reg_start = *reg_end; *reg_end = *reg_start; }
+}
+// 1-based inclusive region -> 0-based inclusive columns first .. last inside a reference of L columns (first > last: empty)
+inline void clamp_region(int reg_start, int reg_end, int L, int* first, int* last) {
+  if (reg_start < 1) reg_start = 1;
+  if (reg_end > L) reg_end = L;
+  *first = reg_start - 1;
+  *last = reg_end - 1;
+}
+
+// the id print_region shows for a record: ID, then t|_ (trimmed), r|_ (reverse complement) and %02d of num_inputs -- of which
+// read_id[4] = '\0' keeps two characters (src/map_align.c:664-681)
+inline std::string region_label(const MalnRecord& a) {
+  char num[16];
+  snprintf(num, sizeof num, "%02d", a.num_inputs);
+  std::string id = a.id;
+  id += a.trimmed ? 't' : '_';
+  id += a.rc ? 'r' : '_';
+  id.append(num, 0, 2);
+  return id;
 }
 
 }  // namespace maln_text
