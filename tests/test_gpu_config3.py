@@ -11,6 +11,8 @@ cannot hold this many (5.4 KB of host memory per AlnSeq), hence samples and size
   host threads joined by the library's loopback transport, mia_hip_iterate's own sharded path (pre-cull all-gather,
   all-reduce of tallies and gaps, event exchange): every rank returns the single context's consensus in both iterations,
   the concatenated per-read results and the reduced tallies are identical;
+* at the full size, EVERY read after both iterations and both consensus strings digest to what the reference's own loop
+  computed for the same reads (tests/golden/bench_certificates_ref.json, tools/make_ref_certificates.py);
 * the consensus is a fixed point after a few more rounds.
 MIA_CONFIG3_READS overrides the read count."""
 import os
@@ -85,6 +87,18 @@ def test_sample_against_oracle(full, oracle):
             bad = np.nonzero(al[k][pick] != o[k])[0]
             assert len(bad) == 0, (it, k, len(bad), pick[bad[:5]].tolist())
     po.close()
+
+
+def test_all_reads_against_reference(full, oracle):
+    f = full
+    if N == 10_000_000:
+        import ref_certificates as rcert
+        ref = rcert.load()["cfg3"]
+        rcert.check_consensus(f.cons1, ref["consensus_sha256"], ref["consensus_len"], "cfg3 iteration 1")
+        rcert.check_consensus(f.cons2, ref["consensus_sha256"], ref["consensus_len"], "cfg3 iteration 2")
+        refs = [f.ref, f.cons1]
+        for it, al in ((1, f.al1), (2, f.al2)):
+            rcert.check_alignments(al, ref, it, "cfg3", rcert.oracle_rerun(oracle, refs[:it], True, SPEC, f.stored, f.rc, f.as0, f.ae0))
 
 
 def test_shortcuts_change_nothing_on_a_slice(full):

@@ -2,6 +2,11 @@
 """GPU box: the digests bench.py prints for its four workloads (bench.certificate: sha256 of the converged consensus and of every
 read's (score, as, ae)), written to gpurun_out/bench_certificates.json -- copy to tests/golden/ once the tests that check samples
 of the SAME workloads against the oracle are green (tests/test_gpu_bench_workloads.py, test_gpu_config3.py, test_gpu_config4_full.py).
+These digests are HIP-made: they say what bench.py's line must show, not what is right.  The reference-made side is
+tests/golden/bench_certificates_ref.json (tools/make_ref_certificates.py: the reference's own loop on every read of cfg1, cfg2, cfg3,
+both iterations); tests/test_bench_certificates_cpu.py holds the two files against each other, so regenerate this one only after the
+GPU tests match the reference-made file.  cfg4 and the whole-batch consensus of the 1 M / 10 M runs have no reference-made digest
+(cost: DESIGN section 6); they remain oracle-sampled.
 usage: python3 tools/make_bench_certificates.py [cfg ...]"""
 import json
 import os
