@@ -969,14 +969,19 @@ static int bx_diag[8];       // (tests / tools only: what the last bx_finish saw
 #endif
 // B0 (the loss of one valid path) and what follows from it
 // PATHS: 0 = whatever the anchors say, 1 = the caller knows d_first == d_last, 2 = the caller knows they differ
-template <int NW, int PATHS = 0>
-MIA_HD inline void bx_finish(DiagScan<NW>& sc, const RefPlanes& rp, const BxAnchors& an, int s, int len1, int len2, int st, const BxTab& T, BxPlan* out) {
+// LEAN (the quick plan's two forms): the caller has looked at d_first already -- sc SITS on s + d_first and m1_held are its loss rows
+// (no second seek) --, has proven that the window holds no N column (cok covers every row on every diagonal of the window: bx_window_nmin
+// is 0, the credit loop finds no column and leaves on its first pass -- neither is compiled) and uses no fine blocks (an.fine == 0).
+// The band it proves is the one the plain form proves for the same anchors.
+template <int NW, int PATHS = 0, bool LEAN = false>
+MIA_HD inline void bx_finish(DiagScan<NW>& sc, const RefPlanes& rp, const BxAnchors& an, int s, int len1, int len2, int st, const BxTab& T, BxPlan* out,
+                             const uint64_t* m1_held = nullptr) {
   out->mode = BX_NONE;
   const int R = len2 - 1, d_first = an.d_first, d_last = PATHS == 1 ? an.d_first : an.d_last;
   uint64_t m1[NW];
-  sc.seek(rp, (int64_t)s + d_first);
+  if (!LEAN) sc.seek(rp, (int64_t)s + d_first);
 #pragma unroll
-  for (int j = 0; j < NW; j++) m1[j] = bx_loss_rows<NW>(sc, j);
+  for (int j = 0; j < NW; j++) m1[j] = LEAN ? m1_held[j] : bx_loss_rows<NW>(sc, j);
   int b0 = 0, nfail = 0;
   if (PATHS == 1 || (PATHS == 0 && d_first == d_last)) {
     b0 = bx_rows_loss<NW>(sc, m1, 0, len2, len2, st, T, 0, &nfail);
@@ -1012,7 +1017,7 @@ MIA_HD inline void bx_finish(DiagScan<NW>& sc, const RefPlanes& rp, const BxAnch
   // is mostly N columns (ten of them under a 100-base read, 210 each) -- but so is every other path's loss: the window-wide
   // credit (bx_make_tables, bx_window_nmin) is worked out only for the reads the plain sum turns away
   int ncredit = 0;
-  if (b0x > an.budget || (an.l_out >= 0 && an.l_out <= b0x)) {
+  if (!LEAN && (b0x > an.budget || (an.l_out >= 0 && an.l_out <= b0x))) {
     if (T.loss[BX_LOSS_NCRED + st * BX_NCRED_K + 1] > 0) {
       const int nm = bx_window_nmin(rp, s, len1, len2, an.fine != 0);
       const int16_t* cum = T.loss + BX_LOSS_NCRED + st * BX_NCRED_K;
@@ -1032,7 +1037,7 @@ MIA_HD inline void bx_finish(DiagScan<NW>& sc, const RefPlanes& rp, const BxAnch
   // hold one or more, none holds three).  Every other block is broken -- by a row that is no match (fdl_b) or by an event, which
   // pays for the blocks it touches (the netting of the stray tables).
   int l_out = an.l_out;
-  if (an.fine && l_out >= 0 && an.fc2 >= 0) {
+  if (!LEAN && an.fine && l_out >= 0 && an.fc2 >= 0) {
     const int m = b0x / (GOP + GEP) + 1;
     const int two = m < an.fc2 ? m : an.fc2, rest = m - two, ones = an.fc1 - an.fc2;
     const int t = 2 * two + (rest < ones ? rest : ones);
@@ -1049,8 +1054,8 @@ MIA_HD inline void bx_finish(DiagScan<NW>& sc, const RefPlanes& rp, const BxAnch
   if (g_dn > 0) {
     const int x = b0x - an.s_un;
     if (x < 0) { out->b0 = BXF_PATH; return; }         // (cannot happen: every path pays for the blocks that occur nowhere)
-    const int16_t* dn = T.dl + (an.fine ? bx_stray_off_fine(st, 0) : bx_stray_off(st, len2, 0));
-    const int16_t* up = T.dl + (an.fine ? bx_stray_off_fine(st, 1) : bx_stray_off(st, len2, 1));
+    const int16_t* dn = T.dl + (!LEAN && an.fine ? bx_stray_off_fine(st, 0) : bx_stray_off(st, len2, 0));
+    const int16_t* up = T.dl + (!LEAN && an.fine ? bx_stray_off_fine(st, 1) : bx_stray_off(st, len2, 1));
     if (g_dn > BX_GMAX) g_dn = g_up = BX_GMAX + 1;     // (beyond the tables: the band is too wide anyway)
     else {
       // either side can be reached either way: below the anchors by skipped rows behind them or by a column gap in front
@@ -1075,7 +1080,7 @@ MIA_HD inline void bx_finish(DiagScan<NW>& sc, const RefPlanes& rp, const BxAnch
   // The band this gives is proven in turn, so the argument can be repeated with it (more columns count, y shrinks).
   // (Against mt311, every tenth column an ambiguity code, B0 is mostly such columns: without the credit the band would
   // be 20-30 diagonals wide.)  sc sits on d_first: bit q of its planes is window column d_first + q.
-  if (g_dn + g_up > 0) {
+  if (!LEAN && g_dn + g_up > 0) {
     int G = b0x < GOP + GEP ? 0 : (b0x - GOP) / GEP;
     const int gt = g_dn > g_up ? g_dn : g_up;
     if (gt <= BX_GMAX && gt < G) G = gt;
@@ -1173,6 +1178,29 @@ struct alignas(8) KbPair { uint32_t present, repeated; };
 struct KmerBits { const KbPair* w; int32_t ref_len; };      // ref_len = L (the places the bitmaps count); w == nullptr: none
 constexpr int64_t KB_WORDS = (int64_t)1 << (2 * DF_K - 5);      // pairs (32 10-mers each)
 constexpr int BX_QUICK_MAX = 8;        // more rows with a loss on d than this: an indel, or a read that belongs elsewhere -- not worth the look-ups
+// the first rows of the read's blocks (bx_block_row, whose 64-bit division is a subroutine of a hundred instructions on the device: the
+// products stay below 2^12, the same quotients in 32 bits, worked out once per read)
+template <int NB>
+MIA_HD inline void bx_block_rows(int len2, int nb_cut, int* orow) {
+#pragma unroll
+  for (int b = 0; b < NB; b++) orow[b] = b < nb_cut ? b * (len2 - DF_K) / (nb_cut - 1) : 0;
+}
+// bit q: rows q .. q + DF_K - 1 are all free of loss (m = the rows that lose anything, bx_loss_rows; rows behind word NW - 1 count as
+// lost: no block reaches them).  Four shifted ANDs per diagonal, then one bit per block -- bx_count's two variable 64-bit shifts and a
+// population count per block and word were most of the one-indel form's seven diagonals.
+template <int NW>
+MIA_HD inline void bx_clean_runs(const uint64_t* m, uint64_t* r) {
+  static_assert(DF_K == 10, "bx_clean_runs folds 2, 4, 8 and two more rows");
+  uint64_t a[NW], b[NW], c[NW];
+#pragma unroll
+  for (int j = 0; j < NW; j++) a[j] = ~m[j] & ((~m[j] >> 1) | (j + 1 < NW ? ~m[j + 1] << 63 : 0ull));          // rows q, q + 1
+#pragma unroll
+  for (int j = 0; j < NW; j++) b[j] = a[j] & ((a[j] >> 2) | (j + 1 < NW ? a[j + 1] << 62 : 0ull));                // q .. q + 3
+#pragma unroll
+  for (int j = 0; j < NW; j++) c[j] = b[j] & ((b[j] >> 4) | (j + 1 < NW ? b[j + 1] << 60 : 0ull));                // q .. q + 7
+#pragma unroll
+  for (int j = 0; j < NW; j++) r[j] = c[j] & ((a[j] >> 8) | (j + 1 < NW ? a[j + 1] << 56 : 0ull));                // q .. q + 9
+}
 template <int NW>
 MIA_HD inline bool bx_quick(DiagScan<NW>& sc, const RefPlanes& rp, const KmerHash& kh, const KmerBits& kb, int s, int len1, int len2, int st, int d, const BxTab& T,
                             BxPlan* out) {
@@ -1190,37 +1218,42 @@ MIA_HD inline bool bx_quick(DiagScan<NW>& sc, const RefPlanes& rp, const KmerHas
   const int16_t* dl = T.dl + (st * (MAX_READ + 1) + len2) * BX_BLOCKS;
   uint32_t kidx[NB], w1[NB], w2[NB];
   int32_t dlv[NB];
+  int orow[NB];
+  bx_block_rows<NB>(len2, nb_cut, orow);
 #pragma unroll
   for (int b = 0; b < NB; b++) {
     kidx[b] = 0; dlv[b] = 0; w1[b] = 0; w2[b] = 0;
     if (b < nb_cut) {
-      kidx[b] = bx_kmer_planes<NW>(sc, bx_block_row(b, len2, nb_cut));
+      kidx[b] = bx_kmer_planes<NW>(sc, orow[b]);
       const KbPair pr = kb.w[kidx[b] >> 5];
       w1[b] = pr.present; w2[b] = pr.repeated;
       dlv[b] = dl[b];
     }
   }
   BX_LOADS_ISSUED();
-  int budget = -1, nbv = 0, s_un = 0, b_lo = -1, b_hi = -1;
+  uint64_t run[NW];
+  bx_clean_runs<NW>(m1, run);
+  int budget = -1, nbv = 0, s_un = 0, b_lo = -1, b_hi = -1, r_head = 0, r_tail = 0;
 #pragma unroll
   for (int b = 0; b < NB; b++) {
     if (b >= nb_cut) continue;
-    const int o = bx_block_row(b, len2, nb_cut);
-    const bool clean = bx_count<NW>(m1, o, o + DF_K) == 0;
+    const bool clean = bx_bit<NW>(run, orow[b]) != 0;
     const bool present = ((w1[b] >> (kidx[b] & 31u)) & 1u) != 0u, repeated = ((w2[b] >> (kidx[b] & 31u)) & 1u) != 0u;
     if (!present) {                           // occurs nowhere: every path breaks this block
       budget += dlv[b]; s_un += dlv[b]; nbv++;
     } else if (clean && !repeated) {          // the reference's own 10-mer of this place, and its only one: anchored on d
       budget += dlv[b]; nbv++;
-      if (b_lo < 0) b_lo = b;
-      b_hi = b;
+      if (b_lo < 0) { b_lo = b; r_head = orow[b]; }
+      b_hi = b; r_tail = orow[b] + DF_K;
     }
   }
   if (nbv < BX_MIN_BLOCKS || b_lo < 0) return false;
   BxAnchors an;
   an.fail = 0; an.a_lo = d; an.a_hi = d; an.d_first = d; an.d_last = d; an.budget = budget; an.t_lo = 1; an.t_hi = R; an.l_out = -1; an.s_un = s_un;
-  an.r_head = bx_block_row(b_lo, len2, nb_cut); an.r_tail = bx_block_row(b_hi, len2, nb_cut) + DF_K; an.rescue = 0; an.fine = 0; an.fc1 = 0; an.fc2 = 0; an.fmax = 0;
-  bx_finish<NW, 1>(sc, rp, an, s, len1, len2, st, T, out);
+  an.r_head = r_head; an.r_tail = r_tail; an.rescue = 0; an.fine = 0; an.fc1 = 0; an.fc2 = 0; an.fmax = 0;
+  (void)b_hi;
+  // (sc sits on s + d, m1 are its loss rows, the window holds no N column: the lean form)
+  bx_finish<NW, 1, true>(sc, rp, an, s, len1, len2, st, T, out, m1);
   if (out->mode == BX_NONE) { out->b0 = 0; return false; }
   return true;
 }
@@ -1234,6 +1267,9 @@ MIA_HD inline bool bx_quick(DiagScan<NW>& sc, const RefPlanes& rp, const KmerHas
 // band [min - g, max + g] exactly as for anchors that bx_anchors found in the table.  Every shift is tried, the one with the most blocks
 // behind the indel is taken (a wrong choice costs a wider band or the budget test, never a wrong answer: the anchors are true places).
 constexpr int BX_QUICK_SHIFT = 3;
+// (Not done: handing the bitmaps' answers on from the one-diagonal form.  That form asks them only of a read with at most BX_QUICK_MAX
+// lost rows on d, and a read with ten clean rows on another diagonal behind an indel loses three rows in four of them on d: of the 476
+// reads this form planned in tests/test_emul_quick_lean.py's three runs, 5 had been looked up before.)
 template <int NW>
 MIA_HD inline bool bx_quick2(DiagScan<NW>& sc, const RefPlanes& rp, const KmerHash& kh, const KmerBits& kb, int s, int len1, int len2, int st, int d, const BxTab& T,
                              BxPlan* out) {
@@ -1245,11 +1281,13 @@ MIA_HD inline bool bx_quick2(DiagScan<NW>& sc, const RefPlanes& rp, const KmerHa
   const int16_t* dl = T.dl + (st * (MAX_READ + 1) + len2) * BX_BLOCKS;
   uint32_t kidx[NB], w1[NB], w2[NB];
   int32_t dlv[NB];
+  int orow[NB];
+  bx_block_rows<NB>(len2, nb_cut, orow);
 #pragma unroll
   for (int b = 0; b < NB; b++) {
     kidx[b] = 0; dlv[b] = 0; w1[b] = 0; w2[b] = 0;
     if (b < nb_cut) {
-      kidx[b] = bx_kmer_planes<NW>(sc, bx_block_row(b, len2, nb_cut));
+      kidx[b] = bx_kmer_planes<NW>(sc, orow[b]);
       const KbPair pr = kb.w[kidx[b] >> 5];
       w1[b] = pr.present; w2[b] = pr.repeated;
       dlv[b] = dl[b];
@@ -1264,20 +1302,28 @@ MIA_HD inline bool bx_quick2(DiagScan<NW>& sc, const RefPlanes& rp, const KmerHa
     if (!present) absent |= 1u << b; else if (!repeated) uniq |= 1u << b;
   }
   // the unique blocks that are clean on diagonal x (bit b), for x = d - SHIFT .. d + SHIFT: one seek, then a column at a time
+  // (the scan and the loss rows of d itself are kept for bx_finish: it seeks to d2 alone)
   uint32_t on[2 * BX_QUICK_SHIFT + 1];
+  DiagScan<NW> sd;
+  uint64_t md[NW];
   sc.seek(rp, (int64_t)s + d - BX_QUICK_SHIFT);
 #pragma unroll
   for (int k = 0; k <= 2 * BX_QUICK_SHIFT; k++) {
     if (k) sc.advance(rp, (int64_t)s + d - BX_QUICK_SHIFT + k);
-    uint64_t m[NW];
+    uint64_t m[NW], run[NW];
 #pragma unroll
     for (int j = 0; j < NW; j++) m[j] = bx_loss_rows<NW>(sc, j);
+    if (k == BX_QUICK_SHIFT) {
+      sd = sc;
+#pragma unroll
+      for (int j = 0; j < NW; j++) md[j] = m[j];
+    }
+    bx_clean_runs<NW>(m, run);
     uint32_t c = 0;
 #pragma unroll
     for (int b = 0; b < NB; b++) {
       if (b >= nb_cut) continue;
-      const int o = bx_block_row(b, len2, nb_cut);
-      if (bx_count<NW>(m, o, o + DF_K) == 0) c |= 1u << b;
+      if (bx_bit<NW>(run, orow[b])) c |= 1u << b;
     }
     const int x = d - BX_QUICK_SHIFT + k;
     on[k] = (x >= 0 && x <= len1 - len2) ? (c & uniq) : 0u;       // (the written-down path must stay inside the window: bx_anchors' BXF_PATH)
@@ -1309,11 +1355,14 @@ MIA_HD inline bool bx_quick2(DiagScan<NW>& sc, const RefPlanes& rp, const KmerHa
   const int b_lo = df_ctz32(cd), b_last = df_ctz32(c2), b_hi = 31 - df_clz32(c2);
   BxAnchors an;
   an.fail = 0; an.a_lo = d < d2 ? d : d2; an.a_hi = d < d2 ? d2 : d; an.d_first = d; an.d_last = d2; an.budget = budget; an.l_out = -1; an.s_un = s_un;
-  an.t_lo = bx_block_row(b_first, len2, nb_cut) + DF_K; an.t_hi = bx_block_row(b_last, len2, nb_cut);
+  // (b_first, b_last, b_lo, b_hi < nb_cut: bits of masks that hold the read's blocks alone)
+  const int dk = len2 - DF_K, dv = nb_cut - 1;
+  an.t_lo = b_first * dk / dv + DF_K; an.t_hi = b_last * dk / dv;
   if (an.t_lo < 1) an.t_lo = 1;
-  an.r_head = bx_block_row(b_lo, len2, nb_cut); an.r_tail = bx_block_row(b_hi, len2, nb_cut) + DF_K; an.rescue = 0; an.fine = 0; an.fc1 = 0; an.fc2 = 0; an.fmax = 0;
+  an.r_head = b_lo * dk / dv; an.r_tail = b_hi * dk / dv + DF_K; an.rescue = 0; an.fine = 0; an.fc1 = 0; an.fc2 = 0; an.fmax = 0;
   (void)R;
-  bx_finish<NW, 2>(sc, rp, an, s, len1, len2, st, T, out);
+  // (sd sits on s + d, md are its loss rows, the window holds no N column: the lean form; it seeks to d2 itself)
+  bx_finish<NW, 2, true>(sd, rp, an, s, len1, len2, st, T, out, md);
   if (out->mode == BX_NONE) { out->b0 = 0; return false; }
   return true;
 }

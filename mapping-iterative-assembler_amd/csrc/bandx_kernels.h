@@ -260,9 +260,10 @@ __device__ unsigned long long g_plan_clk[64 * 16];
 __host__ __device__ constexpr int bx_quick_lds_words(int qch) { return (256 * qch * 5 + 7) / 8; }
 constexpr int BX_QCH = 8;          // stretches of 256 reads a workgroup of the quick plan (phase 4) takes AT MOST (BxDev::qch: four up to four million reads, eight beyond)
 // (the second launch for reads of 193 .. 256 bases is held to three wavefronts per SIMD, 170 VGPRs: left to itself the allocator takes 176 and
-// the compute unit holds two workgroups instead of three; no other instance changes with the bound, and this one's scratch stays at 80 bytes)
+// the compute unit holds two workgroups instead of three; no other instance changes with the bound, and this one's scratch stays at 80 bytes;
+// the quick plan with the planes in LDS for such reads, <4,5>, likewise: the lean forms keep the scan of d beside the sweep's, 181 VGPRs unbound)
 template <int NW, int PH>
-__global__ __launch_bounds__(256, (NW == 4 && PH == 2) ? 3 : 1) void k_bx_plan(ReadSet rs, RefInfo ref, RefPlanes rp, KmerHash ko, int64_t n_ref, BxDev bx, const int32_t* in_list,
+__global__ __launch_bounds__(256, (NW == 4 && (PH == 2 || PH == 5)) ? 3 : 1) void k_bx_plan(ReadSet rs, RefInfo ref, RefPlanes rp, KmerHash ko, int64_t n_ref, BxDev bx, const int32_t* in_list,
                                                   const uint32_t* n_in_p, int64_t n_all, int32_t* bin_of) {
   // PH: 0 everything in one launch; 1 / 2 / 3 the three launches of the full plan; 4 the quick plan, 5 the same with the reference's planes in
   // LDS; 6 = phase 0 over a list that may be LONGER than the grid (the quick plan's undecided reads, taken beside the band DPs by a grid
