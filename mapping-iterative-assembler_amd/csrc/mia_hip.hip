@@ -19,6 +19,7 @@
 #include "mia_consensus_kernels.h"
 #include "mia_kernels.h"
 #include "bandx_kernels.h"
+#include "align_route.h"
 #include "mia_pass1_kernels.h"
 #include "mia_myers_kernels.h"
 #include "mia_trim_kernels.h"
@@ -77,7 +78,7 @@ struct mia_hip_ctx {
   hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the trace DP of the plan's own lists runs beside the values DP
   hipStream_t stream3 = nullptr; hipEvent_t ev_join3 = nullptr;                      // ... and both beside the planner and the full-window kernels of the reads the plan gave up on
   // the launches other streams wait for signal their events themselves (launch_k) instead of a marker behind them: a bit per launch, all or none
-  uint32_t ext_events = 31u; bool planner_end_signalled = false, align_end_signalled = false;
+  uint32_t ext_events = 31u; bool align_end_signalled = false;      // (the alignment's last launch on the context's stream has signalled ev_fork: bx_join_and_retry)
   bool spin_wait = true;                   // mia_hip_iterate's one wait asks (hipStreamQuery) instead of sleeping on an interrupt; MIA_HIP_SPIN_WAIT=0: hipStreamSynchronize
   // HIP-event timers of the kernels bench.py reports, one per stage (mia_hip_stage_stats); pairs are recycled through ev_free
   uint32_t stage_mask = ~0u;               // timed stages (mia_hip_set_stage_mask): an event pair costs the stream a few microseconds
@@ -125,10 +126,9 @@ struct mia_hip_ctx {
   bool wide_to_caller = false;             // run_wide marks its reads ST_ESCAPE instead of aligning them (the anchored pass 1)
   // wide scratch
   int32_t* d_scratch = nullptr; int64_t scratch_cap = 0; int64_t* d_scratch_off = nullptr; int64_t scratch_off_cap = 0;
-  // round 6: the band plan lists the reads it leaves open itself and k_align_open takes them one per wavefront (align_all: direct_open):
+  // round 6: the band plan lists the reads it leaves open itself and k_align_open takes them one per wavefront (align_route.h: direct_open):
   // the plan's own open list (n entries), k_align_open's trace slabs (one per workgroup of its grid)
   int32_t* d_open_list = nullptr; int64_t open_cap = 0; unsigned char* d_slabs_open = nullptr; bool use_direct_open = true; int64_t direct_open_steps = 0;
-  bool direct_open_now = false;        // this alignment's open reads are on d_open_list (set by align_all, read by bx_join_and_retry)
 
   // ---- band pipeline, round 1: the diagonal filter (diag_filter.h) and its banded DP (band_body.h), flat matrix only -----------
   int use_filter = 1;
@@ -157,10 +157,8 @@ struct mia_hip_ctx {
   uint32_t* d_bx_slabs = nullptr; int64_t bx_slab_cap = 0;
   int bx_values_wgs = 0, bx_trace_wgs = 0;
   uint32_t* d_bx_slabs_late = nullptr; int64_t bx_slab_late_cap = 0; int bx_late_wgs = 0;
-  uint32_t* d_bx_slabs_late2 = nullptr; bool dp_aside = false;      // the second late trace's slabs; this alignment's values DP and late trace are on stream2 (align_all: fork_at_quick)
+  uint32_t* d_bx_slabs_late2 = nullptr;      // the second late trace's slabs (align_route.h: fork_at_quick)
   int32_t* d_retry2 = nullptr; int64_t retry2_cap = 0;                              // reads no band kernel could finish
-  bool bx_planner_aside = false;            // this call: the planner and the full-window kernels run on stream2, the band DPs on the context's stream
-  bool bx_pending_join = false;             // band kernels are still running on stream2 / stream3
   bool diag_scripts_missing = false;       // the last alignment left the scripts of its ST_DIAG reads unwritten (k_diag_scripts)
   int64_t bx_seen = 0, bx_done[3] = {0, 0, 0};   // reads planned on; finished by the plan / the values DP / the trace DP
   int64_t bx_launches = 0;
@@ -262,7 +260,8 @@ struct mia_hip_ctx {
   int32_t* d_scores_all = nullptr; int64_t scores_all_cap = 0;
 };
 
-// The alternative routes and diagnostics of libmia_hip_alt.so (alt_env reads nothing in the release build), one line each.  The rest
+// The alternative routes and diagnostics of libmia_hip_alt.so (alt_env reads nothing in the release build), one line each.  What the
+// alignment's switches do to the route is decided in ONE place, align_route.h (align_route); these lines only set the fields.  The rest
 // are read where they apply: MIA_HIP_ITER_DEBUG and MIA_HIP_EV_PAD (mia_hip_iterate), MIA_HIP_P1_TIMING / _CPL / _PLAIN
 // (mia_hip_pass1), MIA_HIP_PEAK_DEBUG (mia_hip_peak).
 static void read_alt_switches(mia_hip_ctx* ctx) {
@@ -879,47 +878,12 @@ static hipError_t launch_window(mia_hip_ctx* ctx, int ci, const int32_t* list, i
   return hipGetLastError();
 }
 
-// The band kernels of the three-stream order (align_all) are still running beside the context's stream: wait for them
-// there, then let a window kernel take what they put on the retry list (its length stays on the device).
-static int bx_join_and_retry(mia_hip_ctx* ctx) {
-  if (!ctx->bx_pending_join) return MIA_HIP_OK;
-  ctx->bx_pending_join = false;
-  const int32_t* range = ctx->d_plan_hdr + PH_RETRY2;
-  const int cols = ctx->max_len + 2 * REALIGN_BUFFER + 2;
-  const bool aside = ctx->bx_planner_aside;
-  // mia_hip_iterate: the retry list is the band kernels' alone, so its window kernel only waits for THEM (the trace DP on
-  // stream3; values and late trace are ahead of it on this stream) and runs beside the tail of the planner's chain on
-  // stream2, with trace slabs of its own; the planner is waited for behind it
-  if (!aside || ctx->dp_aside) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));      // (dp_aside: values DP and late trace on stream2)
-  HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join3, 0));
-  // (this launch is the last of the alignment on the context's stream: with ext_events it signals ev_fork, which
-  // mia_hip_iterate's counting sort on stream2 waits for -- see queue_cull)
-  hipEvent_t stop = (aside && (ctx->ext_events & 8u)) ? ctx->ev_fork : nullptr;
-  ctx->align_end_signalled = stop != nullptr;
-  hipError_t e;
-  if (ctx->direct_open_now) {
-    // the plan's own open list and the band DPs' retry list in ONE launch, a read of either per wavefront (k_align_open): the planner's
-    // stream has had nothing to do in this alignment -- no kernel beside the DPs for the open reads, no wait for that stream here
-    RefInfo ref{ctx->d_ref, ctx->L, ctx->wrap, ctx->explicit_win};
-    if (stage_begin(ctx, STG_TRACE)) return MIA_HIP_ERR_NOMEM;
-    launch_k(k_align_open, dim3(OPEN_WGS), dim3(64), 0, ctx->stream, stop, ctx->rs, ref, (const int32_t*)ctx->d_pssm, ctx->packs, (const int32_t*)ctx->d_open_list,
-             (const uint32_t*)(ctx->d_bx_ctr + (size_t)BXC_OPEN * BXC_STRIDE), ctx->d_slabs_open, (int64_t)OPEN_SLAB_BYTES, ctx->d_wide_list, ctx->d_bins + 3 * N_BINS, ctx->dbg,
-             (const int32_t*)ctx->d_retry2, (const uint32_t*)(range + 1));
-    stage_end(ctx, STG_TRACE);
-    e = hipGetLastError();
-    if (e != hipSuccess) { ctx->err = std::string("k_align_open launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
-    return MIA_HIP_OK;
-  }
-  e = cols <= 64 * 4 ? launch_window<4>(ctx, 0, ctx->d_retry2, 0, range, nullptr, aside, stop)
-    : cols <= 64 * 8 ? launch_window<8>(ctx, 1, ctx->d_retry2, 0, range, nullptr, aside, stop)
-                     : launch_window<12>(ctx, 2, ctx->d_retry2, 0, range, nullptr, aside, stop);
-  if (e != hipSuccess) { ctx->err = std::string("k_align_window (band retry list) launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
-  if (aside) {
-    if (!ctx->planner_end_signalled) HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));      // (the planner's chain ends here)
-    ctx->planner_end_signalled = false;
-    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-  }
-  return MIA_HIP_OK;
+// the window kernel of class ci: 64 * {4, 8, 12} columns
+static hipError_t launch_window_class(mia_hip_ctx* ctx, int ci, const int32_t* list, int count, const int32_t* dev_range = nullptr, hipStream_t on = nullptr,
+                                      bool own_slabs = false, hipEvent_t stop = nullptr) {
+  return ci == 0 ? launch_window<4>(ctx, ci, list, count, dev_range, on, own_slabs, stop)
+       : ci == 1 ? launch_window<8>(ctx, ci, list, count, dev_range, on, own_slabs, stop)
+                 : launch_window<12>(ctx, ci, list, count, dev_range, on, own_slabs, stop);
 }
 
 static int align_all(mia_hip_ctx* ctx);
@@ -1029,634 +993,663 @@ static void align_counters_collect(mia_hip_ctx* ctx, const int32_t* hb, bool fil
   if (plain) ctx->plain_retried += h_hdr[PH_RETRIED_PLAIN];
 }
 
-// every strand_known read against its window of ctx->d_ref: plan, values-only pass, trace kernels, exact kernel
-static int align_all(mia_hip_ctx* ctx) {
+// ---- align_all: the route is decided in ONE place (align_route.h: align_route), the stages below follow it --------------------------
+static_assert(ROUTE_QCH == BX_QCH && ROUTE_MAXW == BX_MAXW, "align_route.h carries copies of the two");
+
+// What the stages of one alignment hand each other.  Nothing of it outlives the call: the context keeps align_end_signalled and spec_*.
+struct AlignCall {
+  AlignRoute r;
+  RefInfo ref; RefPlanes rp{nullptr, nullptr, nullptr}; KmerOcc ko{nullptr, nullptr}; KmerHash kh{};
+  uint32_t kslots = 0; int64_t nib_words = 0;
+  BxDev bd; int64_t slab_words = 0;        // the band DPs' tables and lists; words of one trace slab (band pipeline, or round 1's k_band_align)
+  int gb = 0;                              // the planner's grid: 256 threads, PLAN_PER reads each
+  int32_t *d_count, *d_off, *d_cursor, *d_wide_count;
+  hipStream_t ps = nullptr;                // the planner's stream: stream2 beside the band DPs of a deferred call, else the context's
+  bool pending_join = false;               // band kernels are still running on stream2 / stream3
+  bool planner_end_signalled = false;      // the planner chain's last launch has signalled ev_join itself
+  bool dbg_steps = false;                  // MIA_HIP_ITER_DEBUG: wait and report after every stage of the deferred chain
+};
+
+static AlignRouteIn align_route_in(const mia_hip_ctx* ctx) {
+  AlignRouteIn in;
+  in.n = ctx->rs.n; in.max_len = ctx->max_len; in.wrap = ctx->wrap; in.L = ctx->L; in.kh_entries = ctx->kh_entries;
+  in.plane_words = plane_words((int64_t)ctx->wrap + 64);
+  in.flat = ctx->flat; in.ref_mostly_bases = ctx->ref_mostly_bases; in.ref_few_n = ctx->ref_few_n; in.bx_ok = ctx->bx_ok;
+  in.explicit_win = ctx->explicit_win != 0; in.deferred = ctx->deferred; in.pend_encode = ctx->pend_encode;
+  in.own_umax = ctx->umax_valid && ctx->rs.roff == ctx->d_roff;
+  for (int k = 1; k < BXF_KINDS; k++) in.rejects += ctx->bx_last[BXC_FAIL0 + k];
+  in.use_filter = ctx->use_filter; in.use_banddp = ctx->use_banddp; in.use_bx = ctx->use_bx; in.use_lanes = ctx->use_lanes;
+  in.use_fine = ctx->use_fine; in.use_quick = ctx->use_quick; in.bx_serial = ctx->bx_serial; in.plan_split = ctx->plan_split;
+  in.use_direct_open = ctx->use_direct_open; in.no_prep_fuse = ctx->no_prep_fuse;
+  in.ext_events = ctx->ext_events; in.dbg = ctx->dbg; in.bx_dbg = ctx->bx_dbg;
+  return in;
+}
+
+static void align_ck(mia_hip_ctx* ctx, const AlignCall& c, const char* what) {
+  if (!c.dbg_steps) return;
+  hipError_t e = hipStreamSynchronize(c.ps);
+  fprintf(stderr, "[align_all deferred] %s: %s\n", what, hipGetErrorString(e)); fflush(stderr);
+}
+
+template <class T>
+static int grow(mia_hip_ctx* ctx, T** p, int64_t* cap, int64_t want, size_t elems) {
+  if (want <= *cap) return MIA_HIP_OK;
+  if (dev_alloc(ctx, p, elems)) return MIA_HIP_ERR_NOMEM;
+  *cap = want;
+  return MIA_HIP_OK;
+}
+
+// BUFFERS: everything the route's kernels write to, grown to this alignment's sizes (the full-window kernels' trace slabs are made
+// where those are launched: launch_window)
+static int align_ensure_buffers(mia_hip_ctx* ctx, AlignCall& c) {
+  const AlignRoute& r = c.r;
   const int64_t n = ctx->rs.n;
   const int wrap = ctx->wrap;
-  ctx->bx_pending_join = false;
-  ctx->direct_open_now = false;
-  ctx->dp_aside = false;
-  if (!ctx->spec_ok) { ctx->spec_pending = false; ctx->abort_if = nullptr; }
-  ctx->bx_planner_aside = false;
-  ctx->planner_end_signalled = false; ctx->align_end_signalled = false;
-  ctx->buckets_queued = 0;                  // (a counting sort queued for an earlier alignment is void)
-  if (n == 0) { ctx->aligned = true; return MIA_HIP_OK; }
-  RefInfo ref{ctx->d_ref, ctx->L, wrap, ctx->explicit_win};
-  int32_t* d_count = ctx->d_bins;
-  int32_t* d_off = ctx->d_bins + N_BINS;
-  int32_t* d_cursor = ctx->d_bins + 2 * N_BINS;
-  int32_t* d_wide_count = ctx->d_bins + 3 * N_BINS;
-  int32_t* d_retry_count = ctx->d_bins + 3 * N_BINS + 1;
-  const int tb = 256, gb = (int)((n + (int64_t)tb * PLAN_PER - 1) / ((int64_t)tb * PLAN_PER));
-  const int filter_ok = ctx->flat && ctx->use_filter && ctx->ref_mostly_bases;
-  // the band pipeline for any matrix (bandx_kernels.h); it needs the 10-mer table and windows free of N
-  const bool bx = ctx->bx_ok && ctx->use_bx && (ctx->ref_mostly_bases || ctx->kh_entries > 0) && wrap <= (1 << 22) && !(ctx->dbg & 128u);
-  const bool run_filter = filter_ok && !bx;
-  // mia_hip_iterate with the band pipeline alone: codes, control block, planes, nibbles and 10-mer table in one launch (k_ref_prep)
-  const bool fused_prep = ctx->pend_encode && bx && !ctx->no_prep_fuse;
-  if (!fused_prep) {
+  if (!r.filtered) return MIA_HIP_OK;
+  if (grow(ctx, &ctx->d_planes, &ctx->plane_cap, r.plane_words, (size_t)r.plane_words * 3)) return MIA_HIP_ERR_NOMEM;
+  if (r.kocc && !ctx->d_kocc_cnt && (dev_alloc(ctx, &ctx->d_kocc_cnt, (size_t)DF_KTAB) || dev_alloc(ctx, &ctx->d_kocc_pos, (size_t)DF_KTAB * DF_KCAP)))
+    return MIA_HIP_ERR_NOMEM;
+  if (((r.run_filter && r.banded) || r.quick) && grow(ctx, &ctx->d_left_list, &ctx->left_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+  if (!r.bx) {
+    // round 1's banded DP: a persistent grid of wavefronts (three per SIMD), each with its own trace slab
+    c.slab_words = (int64_t)ctx->max_len * BAND_ROW_WORDS;
+    const int64_t words = c.slab_words * std::min<int64_t>((n + 63) / 64, 3072);
+    return r.banded ? grow(ctx, &ctx->d_band_slabs, &ctx->band_slab_cap, words, (size_t)words) : MIA_HIP_OK;
+  }
+  // the reference as 4-bit codes, the lists, one slab per wavefront of the trace kernel's persistent grid
+  c.nib_words = bx_nib_words((int64_t)wrap + 64);
+  if (c.nib_words > ctx->refnib_cap) {
+    if (dev_alloc(ctx, &ctx->d_refnib, (size_t)c.nib_words * 2)) return MIA_HIP_ERR_NOMEM;
+    ctx->refnib_cap = c.nib_words * 2;
+  }
+  c.kslots = kh_slots_for_entries(wrap, ctx->kh_entries);
+  if (c.kslots > ctx->khash_cap) {
+    if (dev_alloc(ctx, &ctx->d_khash, (size_t)c.kslots * 4) || dev_alloc(ctx, &ctx->d_khash_ovf, (size_t)c.kslots * 2)) return MIA_HIP_ERR_NOMEM;
+    ctx->khash_cap = c.kslots;
+  }
+  if (r.want_bits && !ctx->d_kbits && dev_alloc(ctx, &ctx->d_kbits, (size_t)KB_WORDS)) return MIA_HIP_ERR_NOMEM;
+  if (n > ctx->bx_cap) {
+    if (dev_alloc(ctx, &ctx->d_bx_plan, (size_t)n) || dev_alloc(ctx, &ctx->d_bx_expect, (size_t)n) || dev_alloc(ctx, &ctx->d_bx_lists, (size_t)n * 4 * BX_NCLS))
+      return MIA_HIP_ERR_NOMEM;
+    ctx->bx_cap = n;
+  }
+  if (!ctx->bx_values_wgs) {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ctx->use_lanes ? (const void*)k_bxl_values : ALT_KERNEL(k_bx_values), 256, 0) != hipSuccess || occ < 1) occ = 1;
+    ctx->bx_values_wgs = ctx->cus * std::min(occ, 4);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ctx->use_lanes ? (const void*)k_bxl_trace : ALT_KERNEL(k_bx_trace), 256, 0) != hipSuccess || occ < 1) occ = 1;
+    ctx->bx_trace_wgs = ctx->cus * std::min(occ, 4);      // (every wavefront of the trace grid owns a slab)
+  }
+  // (the lanes kernels store four rows per word: whole blocks of four rows)
+  c.slab_words = ctx->use_lanes ? (int64_t)((ctx->max_len + 3) & ~3) * BXL_SLAB_ROW_WORDS : (int64_t)ctx->max_len * BX_SLAB_ROW_WORDS;
+  const int64_t trace_words = c.slab_words * ctx->bx_trace_wgs * 4;
+  if (grow(ctx, &ctx->d_bx_slabs, &ctx->bx_slab_cap, trace_words, (size_t)trace_words)) return MIA_HIP_ERR_NOMEM;
+  if (r.new_flow) {
+    if (grow(ctx, &ctx->d_retry2, &ctx->retry2_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+    if (!ctx->bx_late_wgs) ctx->bx_late_wgs = ctx->cus;        // the values DP's left-overs are few: one workgroup per CU
+    const int64_t late_words = (int64_t)((ctx->max_len + 3) & ~3) * BXL_SLAB_ROW_WORDS * ctx->bx_late_wgs * 4;
+    if (late_words > ctx->bx_slab_late_cap) {
+      if (dev_alloc(ctx, &ctx->d_bx_slabs_late, (size_t)late_words) || dev_alloc(ctx, &ctx->d_bx_slabs_late2, (size_t)late_words)) return MIA_HIP_ERR_NOMEM;
+      ctx->bx_slab_late_cap = late_words;
+    }
+  }
+  if (r.split && grow(ctx, &ctx->d_bx_cand, &ctx->cand_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+  // (the third launch's list only where that launch runs: a record is 72 bytes -- 0.7 GB at 10 M reads)
+  if (r.fine && grow(ctx, &ctx->d_bx_cand2, &ctx->cand2_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+  if (r.direct_open) {
+    if (grow(ctx, &ctx->d_open_list, &ctx->open_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+    if (!ctx->d_slabs_open && hipMalloc((void**)&ctx->d_slabs_open, (size_t)OPEN_SLAB_BYTES * OPEN_WGS) != hipSuccess) return MIA_HIP_ERR_NOMEM;
+  }
+  return MIA_HIP_OK;
+}
+
+// REFERENCE PREPARATION: codes, control block, bit planes, and the table of the route -- round 1's 10-mer occurrences, or nibbles, hash
+// table and bitmaps of the band pipeline; mia_hip_iterate with the band pipeline: all of it in ONE launch (k_ref_prep)
+static int align_ref_prep(mia_hip_ctx* ctx, AlignCall& c) {
+  const AlignRoute& r = c.r;
+  const int wrap = ctx->wrap;
+  const int64_t words = r.plane_words;
+  if (!r.fused_prep) {
     encode_now(ctx);
     HIPCHK(hipMemsetAsync(ctx->d_ctrl, 0, (size_t)CTRL_WORDS * 4, ctx->stream));     // every counter of the iteration at once
   }
-  const int filtered = run_filter || bx;            // bin_of carries marks for the planner
-  uint32_t h_filter_n = 0;
-  bool banded = false;
-  bool planner_head_first = false;      // count / scan / fill of the planner queued in front of the band DPs (see the band launches)
-  bool direct_open = false;             // the plan lists its open reads itself, k_align_open takes them (no planner, no quad kernels: see below)
-  if (filtered) {
-    // reads whose alignment is provably one gap-free diagonal never reach the DP kernels (diag_filter.h)
-    const int64_t words = plane_words((int64_t)wrap + 64);
-    if (words > ctx->plane_cap) {
-      if (dev_alloc(ctx, &ctx->d_planes, (size_t)words * 3)) return MIA_HIP_ERR_NOMEM;
-      ctx->plane_cap = words;
-    }
-    RefPlanes rp{ctx->d_planes, ctx->d_planes + ctx->plane_cap, ctx->d_planes + 2 * ctx->plane_cap};
-    if (!fused_prep)
+  if (!r.filtered) return MIA_HIP_OK;
+  c.rp = RefPlanes{ctx->d_planes, ctx->d_planes + ctx->plane_cap, ctx->d_planes + 2 * ctx->plane_cap};
+  if (!r.fused_prep)
     hipLaunchKernelGGL(k_ref_planes, dim3((unsigned)((words + 3) / 4 < 4096 ? (words + 3) / 4 : 4096)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap + 64, words,
                        ctx->d_planes, ctx->d_planes + ctx->plane_cap, ctx->d_planes + 2 * ctx->plane_cap);
-    // the 10-mer table of this reference (rule (c) looks long clean stretches up instead of sliding over every diagonal;
-    // the band plans are made of its anchors); not for the very long concatenated strings mia_hip_align_windows may be given
-    KmerOcc ko{nullptr, nullptr};
-    if (wrap <= (1 << 22) && !bx) {
-      if (!ctx->d_kocc_cnt && (dev_alloc(ctx, &ctx->d_kocc_cnt, (size_t)DF_KTAB) || dev_alloc(ctx, &ctx->d_kocc_pos, (size_t)DF_KTAB * DF_KCAP)))
-        return MIA_HIP_ERR_NOMEM;
-      HIPCHK(hipMemsetAsync(ctx->d_kocc_cnt, 0, (size_t)DF_KTAB * 4, ctx->stream));
-      hipLaunchKernelGGL(k_kmer_occ, dim3((unsigned)((wrap + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap, ctx->d_kocc_cnt, ctx->d_kocc_pos, 0);
-      ko.cnt = ctx->d_kocc_cnt; ko.pos = ctx->d_kocc_pos;
-    }
-    // what the filter leaves over goes through a banded DP first (bandx_kernels.h, or round 1's band_body.h); both need the table
-    banded = bx || (ctx->use_banddp && ko.cnt && !(ctx->dbg & 128u));
-    if (run_filter) {
-      if (banded && n > ctx->left_cap) {
-        if (dev_alloc(ctx, &ctx->d_left_list, (size_t)n)) return MIA_HIP_ERR_NOMEM;
-        ctx->left_cap = n;
-      }
-      if (stage_begin(ctx, STG_FILTER)) return MIA_HIP_ERR_NOMEM;
-      hipLaunchKernelGGL(k_diag_filter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rs, ref, rp, ko, (int64_t)wrap, ctx->d_bin_of, ctx->dbg,
-                         banded ? ctx->d_left_list : nullptr, ctx->d_filter_n + 1);
-      stage_end(ctx, STG_FILTER);
-      HIPCHK(hipGetLastError());
-    }
-    if (bx) {
-      // the reference as 4-bit codes, the lists, one slab per wavefront of the trace kernel's persistent grid
-      const int64_t nw = bx_nib_words((int64_t)wrap + 64);
-      if (nw > ctx->refnib_cap) {
-        if (dev_alloc(ctx, &ctx->d_refnib, (size_t)nw * 2)) return MIA_HIP_ERR_NOMEM;
-        ctx->refnib_cap = nw * 2;
-      }
-      if (!fused_prep)
-      hipLaunchKernelGGL(k_ref_nibbles, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap, nw, ctx->d_refnib);
-      const uint32_t kslots = kh_slots_for_entries(wrap, ctx->kh_entries);
-      if (kslots > ctx->khash_cap) {
-        if (dev_alloc(ctx, &ctx->d_khash, (size_t)kslots * 4) || dev_alloc(ctx, &ctx->d_khash_ovf, (size_t)kslots * 2)) return MIA_HIP_ERR_NOMEM;
-        ctx->khash_cap = kslots;
-      }
-      const KmerHash kh{ctx->d_khash, ctx->d_khash_ovf, kslots - 1, kh_shift_for(kslots), ctx->kh_entries > 0 ? BX_WILD : 0};
-      // (the quick plan's bitmaps: made wherever the table is made, unless the reference is N all over -- hardly a window without one then)
-      const bool want_bits = ctx->use_quick && (kh.wild == 0 || ctx->ref_few_n);
-      if (want_bits && !ctx->d_kbits && dev_alloc(ctx, &ctx->d_kbits, (size_t)KB_WORDS)) return MIA_HIP_ERR_NOMEM;
-      if (fused_prep) {
-        RefPrep rp2;
-        rp2.ascii = ctx->ascii_src; rp2.L = ctx->pend_L; rp2.wl = ctx->pend_wl; rp2.total = ctx->pend_total; rp2.codes = ctx->d_ref;
-        rp2.ctrl = ctx->d_ctrl; rp2.ctrl_words = CTRL_WORDS;
-        rp2.kslot = ctx->d_khash; rp2.kovf = ctx->d_khash_ovf; rp2.kslots = kslots; rp2.kmask = kh.mask; rp2.kshift = kh.shift; rp2.kwild = kh.wild;
-        rp2.plane_words = words; rp2.plo = ctx->d_planes; rp2.phi = ctx->d_planes + ctx->plane_cap; rp2.pok = ctx->d_planes + 2 * ctx->plane_cap;
-        rp2.nib_words = nw; rp2.nib = ctx->d_refnib;
-        const int64_t want = ((int64_t)wrap + (kh.wild > 0 ? 63 : 255)) / (kh.wild > 0 ? 64 : 256);       // (N columns spelled out: 64 positions per workgroup, see kmer_hash_insert_block)
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, ctx->cus));      // one workgroup per compute unit at most: all resident
-        // the grid barrier's target: what the counter reaches when this launch's workgroups have all arrived.  The host's count only
-        // moves once the launch is known to be queued (a refused launch adds nothing on the device either), the wait inside the
-        // kernel is bounded, and a barrier given up on is reported through a pinned word the step's one wait looks at.
-        rp2.bar = ctx->d_prep_bar; rp2.bar_target = ctx->prep_bar_count + grid;
-        rp2.stuck = ctx->h_pin ? reinterpret_cast<uint32_t*>(ctx->h_pin + (62 << 10)) : nullptr;
-        rp2.kbits = want_bits ? ctx->d_kbits : nullptr;
-        hipLaunchKernelGGL(k_ref_prep, dim3(grid), dim3(256), 0, ctx->stream, rp2);
-        HIPCHK(hipGetLastError());
-        ctx->prep_bar_count += grid;
-        ctx->pend_encode = false;
-      } else {
-      HIPCHK(hipMemsetAsync(ctx->d_khash, 0xFF, (size_t)kslots * 16, ctx->stream));
-      hipLaunchKernelGGL(k_kmer_hash, dim3((unsigned)((wrap + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap, ctx->d_khash, ctx->d_khash_ovf,
-                         kh.mask, kh.shift, kh.wild);
-      if (want_bits) {
-        HIPCHK(hipMemsetAsync(ctx->d_kbits, 0, (size_t)KB_WORDS * sizeof(KbPair), ctx->stream));
-        hipLaunchKernelGGL(k_kmer_bits, dim3((unsigned)((ctx->L + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap, (int64_t)ctx->L, ctx->d_kbits);
-      }
-      }
-      if (n > ctx->bx_cap) {
-        if (dev_alloc(ctx, &ctx->d_bx_plan, (size_t)n) || dev_alloc(ctx, &ctx->d_bx_expect, (size_t)n) || dev_alloc(ctx, &ctx->d_bx_lists, (size_t)n * 4 * BX_NCLS))
-          return MIA_HIP_ERR_NOMEM;
-        ctx->bx_cap = n;
-      }
-      if (!ctx->bx_values_wgs) {
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ctx->use_lanes ? (const void*)k_bxl_values : ALT_KERNEL(k_bx_values), 256, 0) != hipSuccess || occ < 1) occ = 1;
-        ctx->bx_values_wgs = ctx->cus * std::min(occ, 4);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ctx->use_lanes ? (const void*)k_bxl_trace : ALT_KERNEL(k_bx_trace), 256, 0) != hipSuccess || occ < 1) occ = 1;
-        ctx->bx_trace_wgs = ctx->cus * std::min(occ, 4);      // (every wavefront of the trace grid owns a slab)
-      }
-      // (the lanes kernels store four rows per word: whole blocks of four rows)
-      const int64_t slab_words = ctx->use_lanes ? (int64_t)((ctx->max_len + 3) & ~3) * BXL_SLAB_ROW_WORDS : (int64_t)ctx->max_len * BX_SLAB_ROW_WORDS;
-      if (slab_words * ctx->bx_trace_wgs * 4 > ctx->bx_slab_cap) {
-        if (dev_alloc(ctx, &ctx->d_bx_slabs, (size_t)(slab_words * ctx->bx_trace_wgs * 4))) return MIA_HIP_ERR_NOMEM;
-        ctx->bx_slab_cap = slab_words * ctx->bx_trace_wgs * 4;
-      }
-      BxDev bd;
-      bd.tab.sub = ctx->d_bx_sub; bd.tab.mrow = ctx->d_bx_mrow; bd.tab.loss = ctx->d_bx_loss; bd.tab.dl = ctx->d_bx_dl;
-      bd.dbg = ctx->bx_dbg & (3u | 32u | 64u | 128u | 512u);
-      // MIA_HIP_BX_SERIAL=1: round 2's order (band kernels, then the planner over everything they left open)
-      // (caller-supplied windows -- mia_hip_align_windows -- can be of any length: the retry list's window kernel is picked by read length)
-      const bool new_flow = ctx->use_lanes && !ctx->bx_serial && !(ctx->dbg & 256u) && !ctx->explicit_win;
-      if (new_flow) {
-        if (n > ctx->retry2_cap) { if (dev_alloc(ctx, &ctx->d_retry2, (size_t)n)) return MIA_HIP_ERR_NOMEM; ctx->retry2_cap = n; }
-        if (!ctx->bx_late_wgs) ctx->bx_late_wgs = ctx->cus;        // the values DP's left-overs are few: one workgroup per CU
-        const int64_t late_words = (int64_t)((ctx->max_len + 3) & ~3) * BXL_SLAB_ROW_WORDS * ctx->bx_late_wgs * 4;
-        if (late_words > ctx->bx_slab_late_cap) {
-          if (dev_alloc(ctx, &ctx->d_bx_slabs_late, (size_t)late_words) || dev_alloc(ctx, &ctx->d_bx_slabs_late2, (size_t)late_words)) return MIA_HIP_ERR_NOMEM;
-          ctx->bx_slab_late_cap = late_words;
-        }
-      }
-      bd.retry = ctx->d_retry2; bd.retry_n = ctx->d_plan_hdr + PH_RETRY2 + 1;
-      bd.listed_mark = new_flow ? -5 : 0;
-      ctx->diag_scripts_missing = true;         // (the scripts of reads finished as pure diagonals: k_diag_scripts makes them when asked for)
-      bd.tab.min_m = ctx->bx_min_m; bd.tab.max_m = ctx->bx_max_m;
-      bd.tab.maxw = ctx->use_lanes ? BX_MAXW : 32;           // (the widest class needs a read spread over eight lanes)
-      bd.sub256 = ctx->d_bx_sub + BX_SUB_WORDS;
-      bd.refnib = ctx->d_refnib;
-      bd.umax = (ctx->umax_valid && ctx->rs.roff == ctx->d_roff) ? ctx->d_umax : nullptr;    // (a borrowed read set has none)
-      bd.rplanes = bd.umax ? ctx->d_rplanes : nullptr;
-      bd.rplane_words = ctx->rplane_words;
-      bd.plan = ctx->d_bx_plan; bd.expect = ctx->d_bx_expect; bd.lists = ctx->d_bx_lists; bd.list_stride = ctx->bx_cap; bd.ctr = ctx->d_bx_ctr;
-      // the plan in two launches (bandx_kernels.h, phase): the reads with anchors on two diagonals are finished by a second launch
-      // with every lane at work (MIA_HIP_NO_PLAN_SPLIT=1: by the first threads of their blocks, one launch)
-      const bool split = ctx->plan_split;
-      const bool fork_by_launch = (ctx->ext_events & 1u) && new_flow && !(ctx->dbg & 256u);
-      bd.cand = nullptr; bd.cand_n = ctx->d_bx_ctr + (size_t)BXC_CAND * BXC_STRIDE;
-      bd.cand2 = nullptr; bd.cand2_n = ctx->d_bx_ctr + (size_t)BXC_CAND2 * BXC_STRIDE;
-      // a third launch for the reads whose loss exceeds what the 10-mers vouch for (bx_fine_anchors; MIA_HIP_NO_FINE=1: given up as before)
-      // ... with a position-specific matrix (two reads in a hundred exceed the 10-mers' budget in every iteration, and the full-window
-      // kernels they went to were the largest consumer of vector instructions at 10 M reads: configs[3] 8.47 -> 7.44 ms, configs[2]
-      // 1.41 -> 1.35 ms), with many reads (the launch costs next to nothing where the step is bound by throughput), and whenever
-      // the plan gives up on many reads: against a reference full of ambiguity codes (every run's first iteration), or when it did so
-      // in the iteration before.  With the flat matrix and a million reads the launch would sit on the step's critical path (~55 us)
-      // for the sake of a few thousand reads whose full-window kernels run beside the band DPs anyway.
-      int64_t rejects_before = 0;
-      for (int k = 1; k < BXF_KINDS; k++) rejects_before += ctx->bx_last[BXC_FAIL0 + k];
-      const bool fine = split && ctx->use_fine && (ctx->use_fine > 1 || !ctx->flat || n >= 4000000 || !ctx->ref_mostly_bases || rejects_before * 20 > n);
-      if (split) {
-        if (n > ctx->cand_cap) {
-          if (dev_alloc(ctx, &ctx->d_bx_cand, (size_t)n)) return MIA_HIP_ERR_NOMEM;
-          ctx->cand_cap = n;
-        }
-        // (the third launch's list only where that launch runs: a record is 72 bytes -- 0.7 GB at 10 M reads)
-        if (fine && n > ctx->cand2_cap) {
-          if (dev_alloc(ctx, &ctx->d_bx_cand2, (size_t)n)) return MIA_HIP_ERR_NOMEM;
-          ctx->cand2_cap = n;
-        }
-        bd.cand = ctx->d_bx_cand;
-        if (fine) bd.cand2 = ctx->d_bx_cand2;
-      }
-      const int last_phase = split ? (fine ? 3 : 2) : 0;
-      // PLANNER FIRST.  Where the plan gives up on many reads (against a reference full of ambiguity codes -- every run's first
-      // iteration --, or when it did so in the iteration before) the planner's chain on stream2 -- count, scan, fill, the values-only
-      // quad kernel, the re-plan, the trace quad kernel -- is the longest of the three, and its three small head kernels, launched
-      // beside the persistent band grids, wait for wave slots: k_plan_scan's single workgroup 70 us, the other two 65-80 us each
-      // instead of 10 (first iteration of 1 M flat reads; at 10 M reads 1 ms and 0.8 ms).  They go in front of the fork then: ~35 us
-      // later for the band DPs, ~190 us earlier for the chain that the step waits for.  (Not at steady state, where the
-      // planner's chain has slack and the band DPs' start is the step's critical path.)
-      {
-        int64_t lr = 0;
-        for (int k = 1; k < BXF_KINDS; k++) lr += ctx->bx_last[BXC_FAIL0 + k];
-        const bool many_early = !ctx->ref_mostly_bases || lr * 20 > n;
-        planner_head_first = new_flow && ctx->deferred && many_early && !(ctx->dbg & 256u);
-        // DIRECT OPEN LIST (round 6).  At steady state the plan leaves a few hundred reads per million open.  For their sake the planner
-        // counted, scanned and filled over ALL reads (three launches beside the persistent band grids: 13 + 7 + 71 us), a quad kernel took
-        // them four to a wavefront (110 us: one quad's latency), three window-class launches and a retry launch followed -- nine launches,
-        // 270 us, the longest of the step's three DP chains.  Now the plan appends such a read to a list as it gives up on it and
-        // k_align_open takes the list, one read per wavefront (90-115 us beside the band DPs, 35 on an idle chip: off the step's chain either way).  Where the plan gives up on MANY reads (the values-only quad pass is on:
-        // every run's first iteration, N-rich references) the planner and the quad kernels stay: four reads per wavefront is what pays there.
-        const bool plain_wanted = many_early;      // (= use_plain below, the band pipeline being on)
-        direct_open = new_flow && ctx->deferred && ctx->use_direct_open && !plain_wanted && !planner_head_first && !(ctx->dbg & 256u) &&
-                      !(ctx->bx_dbg & (4u | 8u));
-      }
-      bd.open = nullptr; bd.open_n = ctx->d_bx_ctr + (size_t)BXC_OPEN * BXC_STRIDE;
-      ctx->direct_open_now = direct_open;
-      if (direct_open) {
-        if (n > ctx->open_cap) { if (dev_alloc(ctx, &ctx->d_open_list, (size_t)n)) return MIA_HIP_ERR_NOMEM; ctx->open_cap = n; }
-        if (!ctx->d_slabs_open && hipMalloc((void**)&ctx->d_slabs_open, (size_t)OPEN_SLAB_BYTES * OPEN_WGS) != hipSuccess) return MIA_HIP_ERR_NOMEM;
-        bd.open = ctx->d_open_list;
-        ctx->direct_open_steps++;
-      }
-      // ... and where the plan's third launch is off (flat matrix, a million reads, hardly any rejects: the step is a chain of
-      // latencies) the widest class is not used at all: those few reads keep going to the full-window kernels on the planner's stream,
-      // whose chain is as long with them as without (measured: 0.960 against 0.944 ms per step with the class in use)
-      if (!fine && ctx->use_fine < 2) bd.tab.maxw = 32;
-      // THE QUICK PLAN FIRST (round 6; bandx_body.h: bx_quick, k_bx_plan<NW, 4>): every read on the diagonal it was aligned on before -- nine
-      // in ten of a steady-state iteration are finished or listed there for a tenth of the full plan's instructions; the rest goes on a
-      // list (the diagonal filter's: d_left_list, d_filter_n[1]) that the launches below take as their in_list.  Not against a reference
-      // that is N all over (every run's first iteration; one with a few N columns: the windows that hold none, want_bits above).
-      // (... and with the fine blocks on only from two million reads: the three launches of the full plan stay behind it then, each with a
-      // launch's floor of 30-90 us for the few reads it has left -- 1 M ancient reads 1.12 ms without it, 1.15 with; 10 M solexa 6.0 / 5.4)
-      const bool quick = split && new_flow && want_bits && !(ctx->bx_dbg & 32u) && bd.umax != nullptr &&      // (the context's own reads: their U is at hand)
-                         (!fine || n >= 2000000 || ctx->use_quick > 1);
-      bd.qlist = nullptr; bd.qlist_n = ctx->d_filter_n + 1; bd.mark_all = 0; bd.to_late = 0; bd.qch = 4;
-      // mia_hip_iterate: the fork is behind the QUICK plan (BxDev::to_late) -- values DP and late trace are on the context's stream there, behind
-      // the full plan's launch, so no wait between streams is added; mia_hip_realign keeps every launch of the plan in front of the fork
-      // (... and only where the plan lists its open reads itself: the planner's kernels on stream2 would want every read's mark at the fork)
-      bool plan_launched = false;
-      // (... and not with the fine blocks: the three launches of the full plan are then a chain of their own, longer beside the DPs than
-      // both DPs together -- configs[2]: 45 + 174 + 114 us and 211 for their lists' trace against 280 for the DPs; in front of the fork)
-      const bool fork_at_quick = quick && ctx->deferred && direct_open && !fine && !planner_head_first && !(ctx->bx_dbg & (4u | 8u));
-      bd.kb = KmerBits{quick ? ctx->d_kbits : nullptr, ctx->L};
-      // (the reference's planes in LDS for the quick plan while they are small: 38 KB holds a hundred thousand columns)
-      const bool quick_lds = quick && words * 24 <= 38 * 1024;
-      bd.plane_words = (int32_t)(quick_lds ? words : 0);
-      if (quick) {
-        if (n > ctx->left_cap) { if (dev_alloc(ctx, &ctx->d_left_list, (size_t)n)) return MIA_HIP_ERR_NOMEM; ctx->left_cap = n; }
-        bd.qlist = ctx->d_left_list;
-        ctx->quick_steps++;
-      }
-      if (stage_begin(ctx, STG_BX_PLAN)) return MIA_HIP_ERR_NOMEM;
-      {
-        const int32_t* in_list = quick ? ctx->d_left_list : nullptr;
-        const dim3 pb(256);
-        const int nwords = (ctx->max_len + 63) >> 6;       // 64-row words of the longest read
-        // behind the quick plan the full plan has one read in a hundred left: without fine blocks ONE launch (phase 0: the reads with anchors on
-        // two diagonals by the block's first threads -- a second launch would be a second chain through the table, 40 us, for fifty workgroups)
-        const bool one_launch = quick && !fine;
-        if (quick) {
-          // (eight stretches per workgroup where the lists' counters are the wait -- many reads -- and the planes in LDS are small: with a
-          // 100 kb reference's 37 KB of planes the larger per-read arrays cost the third workgroup per compute unit, configs[4] 7.85 -> 8.05 ms)
-          bd.qch = (n >= 4000000 && words * 24 <= 16 * 1024) ? BX_QCH : 4;
-          const dim3 pg((unsigned)((n + 256 * bd.qch - 1) / (256 * bd.qch)));
-          hipEvent_t done = (fork_at_quick && fork_by_launch) ? ctx->ev_fork : nullptr;
-          const int32_t* in_list = nullptr;               // (this launch walks all n reads)
-#define MIA_PLAN(NWV, PHV) launch_k(k_bx_plan<NWV, PHV>, pg, pb, (size_t)(bx_quick_lds_words(bd.qch) * 8 + (PHV == 5 ? words * 24 : 0)), ctx->stream, done, ctx->rs, ref, rp, kh, (int64_t)wrap, bd, in_list, (const uint32_t*)(ctx->d_filter_n + 1), n, ctx->d_bin_of)
-          if (quick_lds) { switch (nwords) { case 1: MIA_PLAN(1, 5); break; case 2: MIA_PLAN(2, 5); break; case 3: MIA_PLAN(3, 5); break; default: MIA_PLAN(4, 5); break; } }
-          else { switch (nwords) { case 1: MIA_PLAN(1, 4); break; case 2: MIA_PLAN(2, 4); break; case 3: MIA_PLAN(3, 4); break; default: MIA_PLAN(4, 4); break; } }
-#undef MIA_PLAN
-          bd.mark_all = 1;
-          if (fork_at_quick) {
-            if (!fork_by_launch) HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-            bd.to_late = 1;
-          }
-        }
-        const int phase_first = (split && !one_launch) ? 1 : 0, phase_last = one_launch ? 0 : last_phase;
-        plan_launched = true;
-        for (int phase = phase_first; phase <= phase_last; phase++) {
-          // (one_launch: a grid the chip holds at once, looping over the list -- see PH 6 in bandx_kernels.h)
-          const dim3 pg(phase >= 2 ? (unsigned)std::min<int64_t>((n + 255) / 256, 1024) : (unsigned)(one_launch ? std::min<int64_t>((n + 255) / 256, 256) : (n + 255) / 256));
-          // (the fork event rides on the last launch's own completion signal: no marker between the plan and the values DP)
-          hipEvent_t done = (fork_by_launch && phase == phase_last && !planner_head_first && !fork_at_quick) ? ctx->ev_fork : nullptr;
-#define MIA_PLAN(NWV, PHV) launch_k(k_bx_plan<NWV, PHV>, pg, pb, 0, ctx->stream, done, ctx->rs, ref, rp, kh, (int64_t)wrap, bd, in_list, (const uint32_t*)(ctx->d_filter_n + 1), n, ctx->d_bin_of)
-#define MIA_PLAN_NW(PHV) switch (nwords) { case 1: MIA_PLAN(1, PHV); break; case 2: MIA_PLAN(2, PHV); break; case 3: MIA_PLAN(3, PHV); break; default: MIA_PLAN(4, PHV); break; }
-          switch (phase) {
-            case 0: if (one_launch) { MIA_PLAN_NW(6) } else { MIA_PLAN_NW(0) } break;
-            case 1: MIA_PLAN_NW(1) break;
-            case 2: MIA_PLAN_NW(2) break;
-            default: MIA_PLAN_NW(3) break;
-          }
-#undef MIA_PLAN_NW
-#undef MIA_PLAN
-        }
-        bd.to_late = 0;
-      }
-      stage_end(ctx, STG_BX_PLAN);
-      HIPCHK(hipGetLastError());
-      if (planner_head_first) {
-        // (banded, many rejects: the values-only quad pass is on)
-        hipLaunchKernelGGL(k_plan_count, dim3(gb), dim3(tb), 0, ctx->stream, ctx->rs, ref, ctx->packs, /*use_quad=*/1, filtered, filtered, ctx->d_bin_of, d_count, ctx->d_filter_n);
-        hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(512), 0, ctx->stream, d_count, d_off, ctx->d_plan_hdr, 0, ctx->d_list);
-        launch_k(k_plan_fill, dim3(gb), dim3(tb), 0, ctx->stream, fork_by_launch ? ctx->ev_fork : nullptr, n, (const int32_t*)ctx->d_bin_of, (const int32_t*)d_off, d_cursor, ctx->d_list);
-        HIPCHK(hipGetLastError());
-      }
-      if (!(ctx->dbg & 256u)) {
-        if (new_flow) {
-          // Three things that do not depend on each other run side by side: the trace DP of the plan's own lists (stream3),
-          // the values DP with one more trace launch behind it for what it could not finish (stream2), and -- on the
-          // context's stream, below -- the planner and the full-window kernels for the reads the plan gave up on.  The
-          // step pays the longest of the three instead of their sum; what no band kernel can finish (the reference's
-          // index-0 quirk: next to nothing) goes on a retry list that a window kernel reads behind the join.
-          // mia_hip_iterate (deferred): the values DP and the trace launch behind it ARE the step's critical path, so they
-          // stay on the context's stream, right behind the plan -- a cross-stream wait costs 20-30 us each way, and it is the
-          // planner with the full-window kernels (short, done long before) that moves to stream2.
-          // fork_at_quick (round 6): the context's stream holds the full plan's launch for the reads the quick plan left and the trace launch
-          // of what THAT lists (the second late lists); values DP and late trace run beside them on stream2, the trace DP on stream3 -- three
-          // chains of about the same length instead of plan -> values DP -> late trace one after the other, and the join waits for all
-          hipStream_t vs = (ctx->deferred && !fork_at_quick) ? ctx->stream : ctx->stream2;
-          ctx->dp_aside = fork_at_quick;
-          if (fork_at_quick && plan_launched) {
-            if (stage_launch(ctx, STG_BX_VALUES, k_bxl_trace_late2, dim3((unsigned)ctx->bx_late_wgs), dim3(256), 0, ctx->stream, ctx->rs, ref, bd, ctx->d_bx_slabs_late2, slab_words, ctx->d_bin_of))
-              return MIA_HIP_ERR_NOMEM;
-          }
-          if (!fork_by_launch && !fork_at_quick) HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-          HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-          HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_fork, 0));
-          if (stage_begin(ctx, STG_BX_TRACE, ctx->stream3)) return MIA_HIP_ERR_NOMEM;
-          const bool sig3 = (ctx->ext_events & 2u) && new_flow && !(ctx->bx_dbg & 8u);
-          if (!(ctx->bx_dbg & 8u))
-            launch_k(k_bxl_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream3, sig3 ? ctx->ev_join3 : nullptr, ctx->rs, ref, bd, ctx->d_bx_slabs, slab_words, ctx->d_bin_of);
-          stage_end(ctx, STG_BX_TRACE, ctx->stream3);
-          if (!sig3) HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
-          if (!(ctx->bx_dbg & 4u)) {
-            if (stage_launch(ctx, STG_BX_VALUES, k_bxl_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, vs, ctx->rs, ref, bd, ctx->d_bin_of)) return MIA_HIP_ERR_NOMEM;
-            if (stage_launch(ctx, STG_BX_VALUES, k_bxl_trace_late, dim3((unsigned)ctx->bx_late_wgs), dim3(256), 0, vs, ctx->rs, ref, bd, ctx->d_bx_slabs_late, slab_words, ctx->d_bin_of))
-              return MIA_HIP_ERR_NOMEM;
-          }
-          if (!ctx->deferred || fork_at_quick) HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
-          HIPCHK(hipGetLastError());
-          ctx->bx_planner_aside = ctx->deferred;
-          ctx->bx_pending_join = true;
-        } else {
-        // The two band DPs do not depend on each other (a read the values DP cannot finish stays open for the full-window
-        // kernels): they run side by side on two streams -- both are persistent grids whose wavefronts leave as soon as the
-        // chunks run out, so each fills what the other leaves idle, and the step pays the longer of the two tails, not both.
-        HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-        HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        if (stage_begin(ctx, STG_BX_TRACE, ctx->stream2)) return MIA_HIP_ERR_NOMEM;
-        if (ctx->bx_dbg & 8u) {}
-        else if (ctx->use_lanes) hipLaunchKernelGGL(k_bxl_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream2, ctx->rs, ref, bd, ctx->d_bx_slabs, slab_words, ctx->d_bin_of);
-#ifdef MIA_HIP_ALT_PATHS
-        else hipLaunchKernelGGL(k_bx_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream2, ctx->rs, ref, bd, ctx->d_bx_slabs, slab_words, ctx->d_bin_of);
-#endif
-        stage_end(ctx, STG_BX_TRACE, ctx->stream2);
-        HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
-        if (stage_begin(ctx, STG_BX_VALUES)) return MIA_HIP_ERR_NOMEM;
-        if (ctx->bx_dbg & 4u) {}
-        else if (ctx->use_lanes) hipLaunchKernelGGL(k_bxl_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, ctx->stream, ctx->rs, ref, bd, ctx->d_bin_of);
-#ifdef MIA_HIP_ALT_PATHS
-        else hipLaunchKernelGGL(k_bx_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, ctx->stream, ctx->rs, ref, bd, ctx->d_bin_of);
-#endif
-        stage_end(ctx, STG_BX_VALUES);
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        HIPCHK(hipGetLastError());
-        }
-      }
-      ctx->bx_launches++;
-    } else if (banded) {
-      // a persistent grid of wavefronts, each with its own trace slab (the number of left-over reads stays on the device)
-      const int64_t chunks = (n + 63) / 64;
-      const int grid = (int)(chunks < 3072 ? chunks : 3072);          // three wavefronts per SIMD
-      const int64_t slab_words = (int64_t)ctx->max_len * BAND_ROW_WORDS;
-      if (slab_words * grid > ctx->band_slab_cap) {
-        if (dev_alloc(ctx, &ctx->d_band_slabs, (size_t)(slab_words * grid))) return MIA_HIP_ERR_NOMEM;
-        ctx->band_slab_cap = slab_words * grid;
-      }
-      if (stage_begin(ctx, STG_BAND)) return MIA_HIP_ERR_NOMEM;
-      hipLaunchKernelGGL(k_band_align, dim3(grid), dim3(64), 0, ctx->stream, ctx->rs, ref, rp, ko, (int64_t)wrap, ctx->d_left_list, ctx->d_filter_n + 1,
-                         ctx->d_band_slabs, slab_words, ctx->d_bin_of, ctx->d_filter_n + 2, ctx->d_filter_n + 3, ctx->dbg);
-      stage_end(ctx, STG_BAND);
-      HIPCHK(hipGetLastError());
-    }
+  if (r.kocc) {
+    HIPCHK(hipMemsetAsync(ctx->d_kocc_cnt, 0, (size_t)DF_KTAB * 4, ctx->stream));
+    hipLaunchKernelGGL(k_kmer_occ, dim3((unsigned)((wrap + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap, ctx->d_kocc_cnt, ctx->d_kocc_pos, 0);
+    c.ko.cnt = ctx->d_kocc_cnt; c.ko.pos = ctx->d_kocc_pos;
   }
-  // behind the banded DP the values-only pass has nothing left to prove: what the band could not take nearly always needs a trace
-  // ... unless the plan gives up on many reads: against a reference full of ambiguity codes (every run's first iteration
-  // against mt311: the N columns alone exhaust the loss budget of one read in twenty, one in five with the ancient matrix),
-  // or when it did so in the iteration before.  Most of those reads are gap-free; the values-only pass finishes them at
-  // half the trace kernel's price (first iteration 2.84 -> 2.59 ms flat, 5.35 -> 4.08 ms ancient, per 1 M reads).
-  // Either way every read gets the reference's alignment: the choice only moves work between exact kernels.
-  int64_t last_rejects = 0;
-  for (int k = 1; k < BXF_KINDS; k++) last_rejects += ctx->bx_last[BXC_FAIL0 + k];
-  const bool many_rejects = bx && (!ctx->ref_mostly_bases || last_rejects * 20 > n);
-  const bool use_plain = !banded || many_rejects;
-  hipStream_t ps = ctx->bx_planner_aside ? ctx->stream2 : ctx->stream;      // the planner's stream (see the band launches above)
-  if (!planner_head_first && !direct_open)
-  hipLaunchKernelGGL(k_plan_count, dim3(gb), dim3(tb), 0, ps, ctx->rs, ref, ctx->packs, /*use_quad=*/1, filtered, filtered && use_plain, ctx->d_bin_of, d_count, ctx->d_filter_n);
-  if (ctx->deferred) {
-    // ---- mia_hip_iterate: the same plan, but its numbers stay on the device (k_plan_scan) and every DP kernel reads its own
-    // range; the host looks at the counters once, when everything has been queued --------------------------------------
-    int32_t* hdr = ctx->d_plan_hdr;
-    const bool dbg_steps = alt_env("MIA_HIP_ITER_DEBUG") != nullptr;
-    auto ck = [&](const char* what) { if (dbg_steps) { hipError_t e = hipStreamSynchronize(ps); fprintf(stderr, "[align_all deferred] %s: %s\n", what, hipGetErrorString(e)); fflush(stderr); } };
-    ck("plan_count");
-    int32_t* d_retry_cnt = hdr + PH_RETRY + 1;
-    if (direct_open) {
-      // (the plan's open list is taken by the alignment's LAST launch, together with the band DPs' retry list: bx_join_and_retry)
-      ctx->planner_end_signalled = false;
-    } else {
-    if (!planner_head_first) {
-    hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(512), 0, ps, d_count, d_off, hdr, 0, ctx->d_list);      // (writes the quad bins' padding itself: -1 = empty slot)
-    hipLaunchKernelGGL(k_plan_fill, dim3(gb), dim3(tb), 0, ps, n, ctx->d_bin_of, d_off, d_cursor, ctx->d_list);
+  if (!r.bx) return MIA_HIP_OK;
+  const int64_t nw = c.nib_words;
+  const uint32_t kslots = c.kslots;
+  if (!r.fused_prep)
+    hipLaunchKernelGGL(k_ref_nibbles, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap, nw, ctx->d_refnib);
+  c.kh = KmerHash{ctx->d_khash, ctx->d_khash_ovf, kslots - 1, kh_shift_for(kslots), ctx->kh_entries > 0 ? BX_WILD : 0};
+  const KmerHash& kh = c.kh;
+  if (!r.fused_prep) {
+    HIPCHK(hipMemsetAsync(ctx->d_khash, 0xFF, (size_t)kslots * 16, ctx->stream));
+    hipLaunchKernelGGL(k_kmer_hash, dim3((unsigned)((wrap + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap, ctx->d_khash, ctx->d_khash_ovf,
+                       kh.mask, kh.shift, kh.wild);
+    if (r.want_bits) {
+      HIPCHK(hipMemsetAsync(ctx->d_kbits, 0, (size_t)KB_WORDS * sizeof(KbPair), ctx->stream));
+      hipLaunchKernelGGL(k_kmer_bits, dim3((unsigned)((ctx->L + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap, (int64_t)ctx->L, ctx->d_kbits);
     }
-    ck("memsets");
-    hipLaunchKernelGGL(k_wide_seed, dim3(1), dim3(256), 0, ps, ctx->d_list, hdr, ctx->d_wide_list, d_wide_count,
-                       use_plain ? d_count : (int32_t*)nullptr, d_cursor);      // (cleared for the re-plan below)
-    ck("scan fill seed");
-    // every window class reads its own range from the header (the list is rewritten by the re-plan below, so they all go
-    // before it; a class without reads costs an empty launch -- a few microseconds -- and three of them in front of the quad
-    // kernel delayed it by ~50 us of launch gaps on a chain that ends about when the band DPs' does: they go behind its first launch)
-    auto window_classes = [&]() -> int {
-      for (int ci = 0; ci < N_CPL; ci++) {
-        hipError_t e = ci == 0 ? launch_window<4>(ctx, ci, ctx->d_list, 0, hdr + PH_WIN + 2 * ci, ps)
-                     : ci == 1 ? launch_window<8>(ctx, ci, ctx->d_list, 0, hdr + PH_WIN + 2 * ci, ps)
-                               : launch_window<12>(ctx, ci, ctx->d_list, 0, hdr + PH_WIN + 2 * ci, ps);
-        if (e != hipSuccess) { ctx->err = std::string("k_align_window launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
-      }
-      ck("window classes");
-      return MIA_HIP_OK;
-    };
-    const size_t quad_lds = (size_t)Q_G * q_sub_bytes(ctx->max_len) + 16;
-    if (use_plain) {
-      if (stage_begin(ctx, STG_PLAIN, ps)) return MIA_HIP_ERR_NOMEM;
-      hipLaunchKernelGGL(k_align_quad_plain, dim3(ctx->quad_wgs), dim3(64), quad_lds, ps, ctx->rs, ref, ctx->d_pssm, ctx->d_list, 0, ctx->d_bin_of,
-                         (const int32_t*)(hdr + PH_QUAD));
-      stage_end(ctx, STG_PLAIN, ps);
-      ck("quad plain");
-      if (int rcw = window_classes()) return rcw;
-      // what it could not finish (and what the filter's gap hint kept out of it), re-planned into quads
-      // (d_count / d_cursor: cleared by k_wide_seed)
-      hipLaunchKernelGGL(k_plan_recount, dim3(gb), dim3(tb), 0, ps, n, ctx->d_bin_of, d_count);
-      hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(512), 0, ps, d_count, d_off, hdr, 1, ctx->d_list);
-      hipLaunchKernelGGL(k_plan_fill, dim3(gb), dim3(tb), 0, ps, n, ctx->d_bin_of, d_off, d_cursor, ctx->d_list);
-      ck("replan");
-    }
-    const int64_t slab = (int64_t)Q_G * MAX_READ * Q_TRACE_STRIDE;
-    if (!ctx->d_quad_slabs && hipMalloc((void**)&ctx->d_quad_slabs, (size_t)slab * ctx->quad_wgs) != hipSuccess) return MIA_HIP_ERR_NOMEM;
-    const int qgrid = ctx->quad_wgs;
-    if (dbg_steps) {
-      int32_t hh[PH_WORDS];
-      (void)hipMemcpy(hh, hdr, sizeof hh, hipMemcpyDeviceToHost);
-      fprintf(stderr, "[align_all deferred] hdr:");
-      for (int k = 0; k < PH_WORDS; k++) fprintf(stderr, " %d", hh[k]);
-      fprintf(stderr, "  n=%lld max_len=%d quad_lds=%zu\n", (long long)n, ctx->max_len, quad_lds);
-    }
-    if (stage_begin(ctx, STG_TRACE, ps)) return MIA_HIP_ERR_NOMEM;
-    hipLaunchKernelGGL(k_align_quad, dim3(qgrid), dim3(64), quad_lds, ps, ctx->rs, ref, ctx->d_pssm, ctx->packs.p[0], ctx->d_list, 0,
-                       ctx->d_quad_slabs, slab, ctx->d_wide_list, d_wide_count, ctx->d_retry_list, d_retry_cnt, /*band=*/1, ctx->dbg,
-                       (const int32_t*)(hdr + PH_QUAD));
-    stage_end(ctx, STG_TRACE, ps);
-    HIPCHK(hipGetLastError());
-    ck("quad trace");
-    if (!use_plain) { if (int rcw = window_classes()) return rcw; }
-    // (the last launch of the planner's chain: on stream2 it signals ev_join itself, see bx_join_and_retry)
-    const bool sig = ctx->bx_planner_aside && ctx->bx_pending_join && (ctx->ext_events & 4u);
-    hipError_t e = launch_window<4>(ctx, 0, ctx->d_retry_list, 0, hdr + PH_RETRY, ps, false, sig ? ctx->ev_join : nullptr);
-    ctx->planner_end_signalled = sig && e == hipSuccess;
-    if (e != hipSuccess) { ctx->err = std::string("k_align_window retry launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
-    }
-    ck("retry");
-    if (int rcj = bx_join_and_retry(ctx)) return rcj;
-    ck("band join");
-    // the one look at the counters: wide / retry counts, the planner's header, filter and band-pipeline counters lie side by
-    // side in the control block
-    constexpr int C0 = CTRL_C0, CN = CTRL_CN;
-    std::vector<int32_t> pageable;
-    int32_t* hb;
-    if (ctx->h_pin) hb = reinterpret_cast<int32_t*>(ctx->h_pin);
-    else { pageable.resize(CN); hb = pageable.data(); }
-    const bool pre_cull = ctx->in_iterate && ctx->comm;
-    if (pre_cull) { if (int rcp = comm_pre_cull_enqueue(ctx, d_wide_count)) return rcp; }
-    const bool spec = ctx->spec_ok && ctx->h_pin && !pre_cull && !dbg_steps;
-    // (a copy in the middle of the step holds the stream up for 20 us: with zero_copy the step's last kernel, k_cons_scatter,
-    // writes these words into h_pin itself, whether or not the speculation held)
-    if (!(spec && ctx->zero_copy)) HIPCHK(hipMemcpyAsync(hb, ctx->d_ctrl + C0, (size_t)CN * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (spec) {
-      // mia_hip_iterate, one context, a cut line that needs no scores on the host: no wait here.  The caller queues cull,
-      // tally and consensus behind this copy; their kernels look at the exact-kernel count themselves (abort_if) and
-      // iterate_body reads these counters when it waits for the consensus (align_counters_collect).
-      ctx->spec_pending = true; ctx->spec_filtered = filtered != 0; ctx->spec_bx = bx; ctx->spec_plain = use_plain;
-      ctx->abort_if = ctx->spec_force ? ctx->d_one : d_wide_count;      // (MIA_HIP_SPEC_TEST=1: every iteration takes the second round)
-      ctx->aligned = true; ctx->culled = false; ctx->tallied = false; ctx->pre_cull_valid = false;
-      return MIA_HIP_OK;
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    align_counters_collect(ctx, hb, filtered != 0, bx, use_plain);
-    const int32_t n_wide = hb[0];
-    if (n_wide > 0) { if (int rcw = run_wide(ctx, ref, n_wide)) return rcw; }
-    if (pre_cull && comm_pre_cull_collect(ctx)) {
-      // some rank had reads for the exact kernel: its sums were taken before their scores were final.  Every rank saw the
-      // same eight words per rank, so every rank comes here and the all-gather is repeated with the final numbers.
-      if (int rcp = comm_pre_cull_enqueue(ctx, nullptr)) return rcp;
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      (void)comm_pre_cull_collect(ctx);
-    }
-    ctx->aligned = true; ctx->culled = false; ctx->tallied = false; ctx->pre_cull_valid = false;
     return MIA_HIP_OK;
   }
-  // host copies of the counters live in pinned memory when there is some: a copy to or from pageable memory makes the
-  // host wait for the stream even when it is called "async"
+  RefPrep rp2;
+  rp2.ascii = ctx->ascii_src; rp2.L = ctx->pend_L; rp2.wl = ctx->pend_wl; rp2.total = ctx->pend_total; rp2.codes = ctx->d_ref;
+  rp2.ctrl = ctx->d_ctrl; rp2.ctrl_words = CTRL_WORDS;
+  rp2.kslot = ctx->d_khash; rp2.kovf = ctx->d_khash_ovf; rp2.kslots = kslots; rp2.kmask = kh.mask; rp2.kshift = kh.shift; rp2.kwild = kh.wild;
+  rp2.plane_words = words; rp2.plo = ctx->d_planes; rp2.phi = ctx->d_planes + ctx->plane_cap; rp2.pok = ctx->d_planes + 2 * ctx->plane_cap;
+  rp2.nib_words = nw; rp2.nib = ctx->d_refnib;
+  const int64_t want = ((int64_t)wrap + (kh.wild > 0 ? 63 : 255)) / (kh.wild > 0 ? 64 : 256);       // (N columns spelled out: 64 positions per workgroup, see kmer_hash_insert_block)
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, ctx->cus));      // one workgroup per compute unit at most: all resident
+  // the grid barrier's target: what the counter reaches when this launch's workgroups have all arrived.  The host's count only
+  // moves once the launch is known to be queued (a refused launch adds nothing on the device either), the wait inside the
+  // kernel is bounded, and a barrier given up on is reported through a pinned word the step's one wait looks at.
+  rp2.bar = ctx->d_prep_bar; rp2.bar_target = ctx->prep_bar_count + grid;
+  rp2.stuck = ctx->h_pin ? reinterpret_cast<uint32_t*>(ctx->h_pin + (62 << 10)) : nullptr;
+  rp2.kbits = r.want_bits ? ctx->d_kbits : nullptr;
+  hipLaunchKernelGGL(k_ref_prep, dim3(grid), dim3(256), 0, ctx->stream, rp2);
+  HIPCHK(hipGetLastError());
+  ctx->prep_bar_count += grid;
+  ctx->pend_encode = false;
+  return MIA_HIP_OK;
+}
+
+// what the band pipeline's kernels are handed: tables, lists and counters as the route wants them
+static void align_bx_dev(mia_hip_ctx* ctx, AlignCall& c) {
+  const AlignRoute& r = c.r;
+  BxDev& bd = c.bd;
+  bd.tab.sub = ctx->d_bx_sub; bd.tab.mrow = ctx->d_bx_mrow; bd.tab.loss = ctx->d_bx_loss; bd.tab.dl = ctx->d_bx_dl;
+  bd.dbg = ctx->bx_dbg & (3u | 32u | 64u | 128u | 512u);
+  bd.retry = ctx->d_retry2; bd.retry_n = ctx->d_plan_hdr + PH_RETRY2 + 1;
+  bd.listed_mark = r.new_flow ? -5 : 0;
+  bd.tab.min_m = ctx->bx_min_m; bd.tab.max_m = ctx->bx_max_m;
+  bd.tab.maxw = r.maxw;
+  bd.sub256 = ctx->d_bx_sub + BX_SUB_WORDS;
+  bd.refnib = ctx->d_refnib;
+  bd.umax = (ctx->umax_valid && ctx->rs.roff == ctx->d_roff) ? ctx->d_umax : nullptr;    // (a borrowed read set has none)
+  bd.rplanes = bd.umax ? ctx->d_rplanes : nullptr;
+  bd.rplane_words = ctx->rplane_words;
+  bd.plan = ctx->d_bx_plan; bd.expect = ctx->d_bx_expect; bd.lists = ctx->d_bx_lists; bd.list_stride = ctx->bx_cap; bd.ctr = ctx->d_bx_ctr;
+  bd.cand = r.split ? ctx->d_bx_cand : nullptr; bd.cand_n = ctx->d_bx_ctr + (size_t)BXC_CAND * BXC_STRIDE;
+  bd.cand2 = r.fine ? ctx->d_bx_cand2 : nullptr; bd.cand2_n = ctx->d_bx_ctr + (size_t)BXC_CAND2 * BXC_STRIDE;
+  bd.open = r.direct_open ? ctx->d_open_list : nullptr; bd.open_n = ctx->d_bx_ctr + (size_t)BXC_OPEN * BXC_STRIDE;
+  bd.qlist = r.quick ? ctx->d_left_list : nullptr; bd.qlist_n = ctx->d_filter_n + 1; bd.mark_all = 0; bd.to_late = 0; bd.qch = r.qch;
+  bd.kb = KmerBits{r.quick ? ctx->d_kbits : nullptr, ctx->L};
+  bd.plane_words = (int32_t)(r.quick_lds ? r.plane_words : 0);
+}
+
+// k_bx_plan<NW, PH> for the 64-row words of the longest read and a phase of the route
+using PlanKernel = decltype(&k_bx_plan<1, 0>);
+template <int PH>
+static PlanKernel plan_kernel_nw(int nwords) {
+  switch (nwords) { case 1: return k_bx_plan<1, PH>; case 2: return k_bx_plan<2, PH>; case 3: return k_bx_plan<3, PH>; default: return k_bx_plan<4, PH>; }
+}
+static PlanKernel plan_kernel(int nwords, int phase) {
+  switch (phase) {
+    case 0: return plan_kernel_nw<0>(nwords); case 1: return plan_kernel_nw<1>(nwords); case 2: return plan_kernel_nw<2>(nwords); case 3: return plan_kernel_nw<3>(nwords);
+    case 4: return plan_kernel_nw<4>(nwords); case 5: return plan_kernel_nw<5>(nwords); default: return plan_kernel_nw<6>(nwords);
+  }
+}
+
+// PLAN LAUNCHES: the quick plan over all reads, the full plan over what it left (or over all reads), and -- where the plan gives up on
+// many reads -- the planner's three head kernels in front of the fork (align_route.h: planner_head_first)
+static int align_plan_launches(mia_hip_ctx* ctx, AlignCall& c) {
+  const AlignRoute& r = c.r;
+  const int64_t n = ctx->rs.n, wrap = ctx->wrap;
+  BxDev& bd = c.bd;
+  const dim3 pb(256);
+  const uint32_t* in_n = (const uint32_t*)(ctx->d_filter_n + 1);
+  ctx->diag_scripts_missing = true;         // (the scripts of reads finished as pure diagonals: k_diag_scripts makes them when asked for)
+  if (r.direct_open) ctx->direct_open_steps++;
+  if (r.quick) ctx->quick_steps++;
+  if (stage_begin(ctx, STG_BX_PLAN)) return MIA_HIP_ERR_NOMEM;
+  if (r.quick) {
+    const dim3 pg((unsigned)((n + 256 * bd.qch - 1) / (256 * bd.qch)));
+    const size_t lds = (size_t)(bx_quick_lds_words(bd.qch) * 8 + (r.quick_phase == 5 ? r.plane_words * 24 : 0));
+    // (this launch walks all n reads: no in_list)
+    launch_k(plan_kernel(r.nwords, r.quick_phase), pg, pb, lds, ctx->stream, (r.fork_at_quick && r.fork_by_launch) ? ctx->ev_fork : nullptr, ctx->rs, c.ref, c.rp, c.kh, wrap, bd,
+             (const int32_t*)nullptr, in_n, n, ctx->d_bin_of);
+    bd.mark_all = 1;
+    if (r.fork_at_quick) {
+      if (!r.fork_by_launch) HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
+      bd.to_late = 1;
+    }
+  }
+  const int32_t* in_list = r.quick ? ctx->d_left_list : nullptr;
+  for (int phase = r.full_first; phase <= r.full_last; phase++) {
+    // (the fork event rides on the last launch's own completion signal: no marker between the plan and the values DP)
+    hipEvent_t done = (r.fork_by_launch && phase == r.full_last && !r.planner_head_first && !r.fork_at_quick) ? ctx->ev_fork : nullptr;
+    launch_k(plan_kernel(r.nwords, phase), dim3(align_route_plan_grid(r, phase, n)), pb, 0, ctx->stream, done, ctx->rs, c.ref, c.rp, c.kh, wrap, bd, in_list, in_n, n, ctx->d_bin_of);
+  }
+  bd.to_late = 0;
+  stage_end(ctx, STG_BX_PLAN);
+  HIPCHK(hipGetLastError());
+  if (r.planner_head_first) {
+    // (banded, many rejects: the values-only quad pass is on)
+    hipLaunchKernelGGL(k_plan_count, dim3(c.gb), dim3(256), 0, ctx->stream, ctx->rs, c.ref, ctx->packs, /*use_quad=*/1, 1, 1, ctx->d_bin_of, c.d_count, ctx->d_filter_n);
+    hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(512), 0, ctx->stream, c.d_count, c.d_off, ctx->d_plan_hdr, 0, ctx->d_list);
+    launch_k(k_plan_fill, dim3(c.gb), dim3(256), 0, ctx->stream, r.fork_by_launch ? ctx->ev_fork : nullptr, n, (const int32_t*)ctx->d_bin_of, (const int32_t*)c.d_off, c.d_cursor, ctx->d_list);
+    HIPCHK(hipGetLastError());
+  }
+  return MIA_HIP_OK;
+}
+
+// BAND DPs, THREE STREAMS (align_route.h: BAND DPs): trace DP on stream3, values DP and late trace on stream2 or on the context's
+static int align_band_dps(mia_hip_ctx* ctx, AlignCall& c) {
+  const AlignRoute& r = c.r;
+  const BxDev& bd = c.bd;
+  hipStream_t vs = r.values_aside ? ctx->stream2 : ctx->stream;
+  if (r.fork_at_quick) {
+    if (stage_launch(ctx, STG_BX_VALUES, k_bxl_trace_late2, dim3((unsigned)ctx->bx_late_wgs), dim3(256), 0, ctx->stream, ctx->rs, c.ref, bd, ctx->d_bx_slabs_late2, c.slab_words, ctx->d_bin_of))
+      return MIA_HIP_ERR_NOMEM;
+  }
+  if (!r.fork_by_launch && !r.fork_at_quick) HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
+  HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+  HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_fork, 0));
+  if (stage_begin(ctx, STG_BX_TRACE, ctx->stream3)) return MIA_HIP_ERR_NOMEM;
+  if (!(ctx->bx_dbg & 8u))
+    launch_k(k_bxl_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream3, r.trace_signals ? ctx->ev_join3 : nullptr, ctx->rs, c.ref, bd, ctx->d_bx_slabs, c.slab_words, ctx->d_bin_of);
+  stage_end(ctx, STG_BX_TRACE, ctx->stream3);
+  if (!r.trace_signals) HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
+  if (!(ctx->bx_dbg & 4u)) {
+    if (stage_launch(ctx, STG_BX_VALUES, k_bxl_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, vs, ctx->rs, c.ref, bd, ctx->d_bin_of)) return MIA_HIP_ERR_NOMEM;
+    if (stage_launch(ctx, STG_BX_VALUES, k_bxl_trace_late, dim3((unsigned)ctx->bx_late_wgs), dim3(256), 0, vs, ctx->rs, c.ref, bd, ctx->d_bx_slabs_late, c.slab_words, ctx->d_bin_of))
+      return MIA_HIP_ERR_NOMEM;
+  }
+  if (r.values_aside) HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
+  HIPCHK(hipGetLastError());
+  c.pending_join = true;
+  return MIA_HIP_OK;
+}
+
+// BAND DPs, TWO STREAMS (MIA_HIP_BX_SERIAL, MIA_HIP_NO_LANES, caller-supplied windows): round 2's order, the planner behind them.
+// The two band DPs do not depend on each other (a read the values DP cannot finish stays open for the full-window
+// kernels): they run side by side on two streams -- both are persistent grids whose wavefronts leave as soon as the
+// chunks run out, so each fills what the other leaves idle, and the step pays the longer of the two tails, not both.
+static int align_band_dps_serial(mia_hip_ctx* ctx, AlignCall& c) {
+  const BxDev& bd = c.bd;
+  HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
+  HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+  if (stage_begin(ctx, STG_BX_TRACE, ctx->stream2)) return MIA_HIP_ERR_NOMEM;
+  if (ctx->bx_dbg & 8u) {}
+  else if (ctx->use_lanes) hipLaunchKernelGGL(k_bxl_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream2, ctx->rs, c.ref, bd, ctx->d_bx_slabs, c.slab_words, ctx->d_bin_of);
+#ifdef MIA_HIP_ALT_PATHS
+  else hipLaunchKernelGGL(k_bx_trace, dim3((unsigned)ctx->bx_trace_wgs), dim3(256), 0, ctx->stream2, ctx->rs, c.ref, bd, ctx->d_bx_slabs, c.slab_words, ctx->d_bin_of);
+#endif
+  stage_end(ctx, STG_BX_TRACE, ctx->stream2);
+  HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
+  if (stage_begin(ctx, STG_BX_VALUES)) return MIA_HIP_ERR_NOMEM;
+  if (ctx->bx_dbg & 4u) {}
+  else if (ctx->use_lanes) hipLaunchKernelGGL(k_bxl_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, ctx->stream, ctx->rs, c.ref, bd, ctx->d_bin_of);
+#ifdef MIA_HIP_ALT_PATHS
+  else hipLaunchKernelGGL(k_bx_values, dim3((unsigned)ctx->bx_values_wgs), dim3(256), 0, ctx->stream, ctx->rs, c.ref, bd, ctx->d_bin_of);
+#endif
+  stage_end(ctx, STG_BX_VALUES);
+  HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+  HIPCHK(hipGetLastError());
+  return MIA_HIP_OK;
+}
+
+// ROUND 1 (flat matrix, MIA_HIP_NO_BANDX): reads whose alignment is provably one gap-free diagonal never reach the DP kernels
+// (diag_filter.h); what the filter leaves over goes through k_band_align, a persistent grid of wavefronts, each with its own trace slab
+// (the number of left-over reads stays on the device)
+static int align_round1(mia_hip_ctx* ctx, AlignCall& c) {
+  const AlignRoute& r = c.r;
+  const int64_t n = ctx->rs.n, wrap = ctx->wrap;
+  if (r.run_filter) {
+    if (stage_begin(ctx, STG_FILTER)) return MIA_HIP_ERR_NOMEM;
+    hipLaunchKernelGGL(k_diag_filter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rs, c.ref, c.rp, c.ko, wrap, ctx->d_bin_of, ctx->dbg,
+                       r.banded ? ctx->d_left_list : nullptr, ctx->d_filter_n + 1);
+    stage_end(ctx, STG_FILTER);
+    HIPCHK(hipGetLastError());
+  }
+  if (!r.banded) return MIA_HIP_OK;
+  const int grid = (int)std::min<int64_t>((n + 63) / 64, 3072);          // three wavefronts per SIMD
+  if (stage_begin(ctx, STG_BAND)) return MIA_HIP_ERR_NOMEM;
+  hipLaunchKernelGGL(k_band_align, dim3(grid), dim3(64), 0, ctx->stream, ctx->rs, c.ref, c.rp, c.ko, wrap, ctx->d_left_list, ctx->d_filter_n + 1,
+                     ctx->d_band_slabs, c.slab_words, ctx->d_bin_of, ctx->d_filter_n + 2, ctx->d_filter_n + 3, ctx->dbg);
+  stage_end(ctx, STG_BAND);
+  HIPCHK(hipGetLastError());
+  return MIA_HIP_OK;
+}
+
+// The band kernels of the three-stream order are still running beside the context's stream: wait for them
+// there, then let a window kernel take what they put on the retry list (its length stays on the device).
+static int bx_join_and_retry(mia_hip_ctx* ctx, AlignCall& c) {
+  if (!c.pending_join) return MIA_HIP_OK;
+  c.pending_join = false;
+  const int32_t* range = ctx->d_plan_hdr + PH_RETRY2;
+  const int cols = ctx->max_len + 2 * REALIGN_BUFFER + 2;
+  const bool aside = c.r.planner_aside;
+  // mia_hip_iterate: the retry list is the band kernels' alone, so its window kernel only waits for THEM (the trace DP on
+  // stream3; values and late trace are ahead of it on this stream) and runs beside the tail of the planner's chain on
+  // stream2, with trace slabs of its own; the planner is waited for behind it
+  if (c.r.values_aside) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));      // (values DP and late trace on stream2)
+  HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join3, 0));
+  // (this launch is the last of the alignment on the context's stream: with ext_events it signals ev_fork, which
+  // mia_hip_iterate's counting sort on stream2 waits for -- see queue_cull)
+  hipEvent_t stop = (aside && (ctx->ext_events & 8u)) ? ctx->ev_fork : nullptr;
+  ctx->align_end_signalled = stop != nullptr;
+  if (c.r.direct_open) {
+    // the plan's own open list and the band DPs' retry list in ONE launch, a read of either per wavefront (k_align_open): the planner's
+    // stream has had nothing to do in this alignment -- no kernel beside the DPs for the open reads, no wait for that stream here
+    if (stage_begin(ctx, STG_TRACE)) return MIA_HIP_ERR_NOMEM;
+    launch_k(k_align_open, dim3(OPEN_WGS), dim3(64), 0, ctx->stream, stop, ctx->rs, c.ref, (const int32_t*)ctx->d_pssm, ctx->packs, (const int32_t*)ctx->d_open_list,
+             (const uint32_t*)(ctx->d_bx_ctr + (size_t)BXC_OPEN * BXC_STRIDE), ctx->d_slabs_open, (int64_t)OPEN_SLAB_BYTES, ctx->d_wide_list, c.d_wide_count, ctx->dbg,
+             (const int32_t*)ctx->d_retry2, (const uint32_t*)(range + 1));
+    stage_end(ctx, STG_TRACE);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { ctx->err = std::string("k_align_open launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
+    return MIA_HIP_OK;
+  }
+  hipError_t e = launch_window_class(ctx, cols <= 64 * 4 ? 0 : cols <= 64 * 8 ? 1 : 2, ctx->d_retry2, 0, range, nullptr, aside, stop);
+  if (e != hipSuccess) { ctx->err = std::string("k_align_window (band retry list) launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
+  if (aside) {
+    if (!c.planner_end_signalled) HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));      // (the planner's chain ends here)
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+  }
+  return MIA_HIP_OK;
+}
+
+// every window class reads its own range from the header (the list is rewritten by the re-plan, so they all go
+// before it; a class without reads costs an empty launch -- a few microseconds -- and three of them in front of the quad
+// kernel delayed it by ~50 us of launch gaps on a chain that ends about when the band DPs' does: they go behind its first launch)
+static int align_window_classes(mia_hip_ctx* ctx, AlignCall& c) {
+  for (int ci = 0; ci < N_CPL; ci++) {
+    hipError_t e = launch_window_class(ctx, ci, ctx->d_list, 0, ctx->d_plan_hdr + PH_WIN + 2 * ci, c.ps);
+    if (e != hipSuccess) { ctx->err = std::string("k_align_window launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
+  }
+  align_ck(ctx, c, "window classes");
+  return MIA_HIP_OK;
+}
+
+// PLANNER CHAIN, DEFERRED FORM (mia_hip_iterate): the same plan, but its numbers stay on the device (k_plan_scan) and every DP kernel
+// reads its own range; the host looks at the counters once, when everything has been queued (align_finish_deferred)
+static int align_planner_deferred(mia_hip_ctx* ctx, AlignCall& c) {
+  const AlignRoute& r = c.r;
+  const int64_t n = ctx->rs.n;
+  hipStream_t ps = c.ps;
+  int32_t* hdr = ctx->d_plan_hdr;
+  align_ck(ctx, c, "plan_count");
+  // (the plan's open list is taken by the alignment's LAST launch, together with the band DPs' retry list: bx_join_and_retry)
+  if (r.direct_open) return MIA_HIP_OK;
+  if (!r.planner_head_first) {
+    hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(512), 0, ps, c.d_count, c.d_off, hdr, 0, ctx->d_list);      // (writes the quad bins' padding itself: -1 = empty slot)
+    hipLaunchKernelGGL(k_plan_fill, dim3(c.gb), dim3(256), 0, ps, n, ctx->d_bin_of, c.d_off, c.d_cursor, ctx->d_list);
+  }
+  align_ck(ctx, c, "memsets");
+  hipLaunchKernelGGL(k_wide_seed, dim3(1), dim3(256), 0, ps, ctx->d_list, hdr, ctx->d_wide_list, c.d_wide_count,
+                     r.use_plain ? c.d_count : (int32_t*)nullptr, c.d_cursor);      // (cleared for the re-plan below)
+  align_ck(ctx, c, "scan fill seed");
+  const size_t quad_lds = (size_t)Q_G * q_sub_bytes(ctx->max_len) + 16;
+  if (r.use_plain) {
+    if (stage_begin(ctx, STG_PLAIN, ps)) return MIA_HIP_ERR_NOMEM;
+    hipLaunchKernelGGL(k_align_quad_plain, dim3(ctx->quad_wgs), dim3(64), quad_lds, ps, ctx->rs, c.ref, ctx->d_pssm, ctx->d_list, 0, ctx->d_bin_of,
+                       (const int32_t*)(hdr + PH_QUAD));
+    stage_end(ctx, STG_PLAIN, ps);
+    align_ck(ctx, c, "quad plain");
+    if (int rcw = align_window_classes(ctx, c)) return rcw;
+    // what it could not finish (and what the filter's gap hint kept out of it), re-planned into quads
+    // (d_count / d_cursor: cleared by k_wide_seed)
+    hipLaunchKernelGGL(k_plan_recount, dim3(c.gb), dim3(256), 0, ps, n, ctx->d_bin_of, c.d_count);
+    hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(512), 0, ps, c.d_count, c.d_off, hdr, 1, ctx->d_list);
+    hipLaunchKernelGGL(k_plan_fill, dim3(c.gb), dim3(256), 0, ps, n, ctx->d_bin_of, c.d_off, c.d_cursor, ctx->d_list);
+    align_ck(ctx, c, "replan");
+  }
+  const int64_t slab = (int64_t)Q_G * MAX_READ * Q_TRACE_STRIDE;
+  if (!ctx->d_quad_slabs && hipMalloc((void**)&ctx->d_quad_slabs, (size_t)slab * ctx->quad_wgs) != hipSuccess) return MIA_HIP_ERR_NOMEM;
+  if (c.dbg_steps) {
+    int32_t hh[PH_WORDS];
+    (void)hipMemcpy(hh, hdr, sizeof hh, hipMemcpyDeviceToHost);
+    fprintf(stderr, "[align_all deferred] hdr:");
+    for (int k = 0; k < PH_WORDS; k++) fprintf(stderr, " %d", hh[k]);
+    fprintf(stderr, "  n=%lld max_len=%d quad_lds=%zu\n", (long long)n, ctx->max_len, quad_lds);
+  }
+  if (stage_begin(ctx, STG_TRACE, ps)) return MIA_HIP_ERR_NOMEM;
+  hipLaunchKernelGGL(k_align_quad, dim3(ctx->quad_wgs), dim3(64), quad_lds, ps, ctx->rs, c.ref, ctx->d_pssm, ctx->packs.p[0], ctx->d_list, 0,
+                     ctx->d_quad_slabs, slab, ctx->d_wide_list, c.d_wide_count, ctx->d_retry_list, hdr + PH_RETRY + 1, /*band=*/1, ctx->dbg,
+                     (const int32_t*)(hdr + PH_QUAD));
+  stage_end(ctx, STG_TRACE, ps);
+  HIPCHK(hipGetLastError());
+  align_ck(ctx, c, "quad trace");
+  if (!r.use_plain) { if (int rcw = align_window_classes(ctx, c)) return rcw; }
+  // (the last launch of the planner's chain: on stream2 it signals ev_join itself, see bx_join_and_retry)
+  const bool sig = r.planner_aside && c.pending_join && (ctx->ext_events & 4u);
+  hipError_t e = launch_window_class(ctx, 0, ctx->d_retry_list, 0, hdr + PH_RETRY, ps, false, sig ? ctx->ev_join : nullptr);
+  c.planner_end_signalled = sig && e == hipSuccess;
+  if (e != hipSuccess) { ctx->err = std::string("k_align_window retry launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
+  return MIA_HIP_OK;
+}
+
+// CLOSING STATE: an alignment stands, whatever was derived from the one before does not
+static int align_close(mia_hip_ctx* ctx) {
+  ctx->aligned = true; ctx->culled = false; ctx->tallied = false; ctx->pre_cull_valid = false;
+  return MIA_HIP_OK;
+}
+
+// ... the join and the deferred call's one look at the counters: wide / retry counts, the planner's header, filter and band-pipeline
+// counters lie side by side in the control block
+static int align_finish_deferred(mia_hip_ctx* ctx, AlignCall& c) {
+  const AlignRoute& r = c.r;
+  align_ck(ctx, c, "retry");
+  if (int rcj = bx_join_and_retry(ctx, c)) return rcj;
+  align_ck(ctx, c, "band join");
+  constexpr int C0 = CTRL_C0, CN = CTRL_CN;
+  std::vector<int32_t> pageable;
+  int32_t* hb;
+  if (ctx->h_pin) hb = reinterpret_cast<int32_t*>(ctx->h_pin);
+  else { pageable.resize(CN); hb = pageable.data(); }
+  const bool pre_cull = ctx->in_iterate && ctx->comm;
+  if (pre_cull) { if (int rcp = comm_pre_cull_enqueue(ctx, c.d_wide_count)) return rcp; }
+  const bool spec = ctx->spec_ok && ctx->h_pin && !pre_cull && !c.dbg_steps;
+  // (a copy in the middle of the step holds the stream up for 20 us: with zero_copy the step's last kernel, k_cons_scatter,
+  // writes these words into h_pin itself, whether or not the speculation held)
+  if (!(spec && ctx->zero_copy)) HIPCHK(hipMemcpyAsync(hb, ctx->d_ctrl + C0, (size_t)CN * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (spec) {
+    // mia_hip_iterate, one context, a cut line that needs no scores on the host: no wait here.  The caller queues cull,
+    // tally and consensus behind this copy; their kernels look at the exact-kernel count themselves (abort_if) and
+    // iterate_body reads these counters when it waits for the consensus (align_counters_collect).
+    ctx->spec_pending = true; ctx->spec_filtered = r.filtered; ctx->spec_bx = r.bx; ctx->spec_plain = r.use_plain;
+    ctx->abort_if = ctx->spec_force ? ctx->d_one : c.d_wide_count;      // (MIA_HIP_SPEC_TEST=1: every iteration takes the second round)
+    return align_close(ctx);
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  align_counters_collect(ctx, hb, r.filtered, r.bx, r.use_plain);
+  const int32_t n_wide = hb[0];
+  if (n_wide > 0) { if (int rcw = run_wide(ctx, c.ref, n_wide)) return rcw; }
+  if (pre_cull && comm_pre_cull_collect(ctx)) {
+    // some rank had reads for the exact kernel: its sums were taken before their scores were final.  Every rank saw the
+    // same eight words per rank, so every rank comes here and the all-gather is repeated with the final numbers.
+    if (int rcp = comm_pre_cull_enqueue(ctx, nullptr)) return rcp;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    (void)comm_pre_cull_collect(ctx);
+  }
+  return align_close(ctx);
+}
+
+// PLANNER CHAIN, HOST-ROUND-TRIP FORM (mia_hip_realign, mia_hip_align_windows, pass 1): the bins' counts come to the host, which sizes
+// every launch.  Host copies of the counters live in pinned memory when there is some: a copy to or from pageable memory makes the
+// host wait for the stream even when it is called "async"
+struct HostPlan {
   int32_t local_buf[4 * N_BINS + 16];
-  int32_t* hb = ctx->h_pin ? reinterpret_cast<int32_t*>(ctx->h_pin) : local_buf;
-  int32_t *h_count = hb, *h_off = hb + N_BINS, *h_count2 = hb + 2 * N_BINS, *h_off2 = hb + 3 * N_BINS, *h_misc = hb + 4 * N_BINS;
-  h_misc[0] = 0;
-  h_misc[6] = 0;
+  int32_t *h_count, *h_off, *h_count2, *h_off2, *h_misc;
   std::vector<uint32_t> bxc_pageable;
   uint32_t* h_bxc;                                  // all counters of the band pipeline (8 KB), read once the stream is waited for anyway
-  if (ctx->h_pin) h_bxc = reinterpret_cast<uint32_t*>(ctx->h_pin + (24 << 10));
-  else { bxc_pageable.resize(BXC_WORDS); h_bxc = bxc_pageable.data(); }
-  for (int k = 0; k < BXC_COUNTERS; k++) h_bxc[k * BXC_STRIDE] = 0;
-  if (filtered) {
+  bool bx_counters_later = false;                   // (with the band kernels still running beside this stream their counters are read behind the join)
+  int n_quads = 0, quad_begin = 0;
+  bool wide_known = false;
+};
+
+static void host_take_bx_counters(mia_hip_ctx* ctx, const HostPlan& h) {
+  ctx->filter_proven += h.h_bxc[BXC_DONE_PLAN * BXC_STRIDE];          // finished without any DP: by the diagonal filter or by the band plan
+  for (int k = 0; k < 3; k++) ctx->bx_done[k] += h.h_bxc[(BXC_DONE_PLAN + k) * BXC_STRIDE];
+  ctx->bx_seen += h.h_bxc[BXC_SEEN * BXC_STRIDE];
+  for (int k = 0; k < BXC_COUNTERS; k++) ctx->bx_last[k] = h.h_bxc[k * BXC_STRIDE];
+}
+
+// ... its first round: counters to the host, the lists filled, the window classes launched
+static int align_planner_host_fill(mia_hip_ctx* ctx, AlignCall& c, HostPlan& h) {
+  const AlignRoute& r = c.r;
+  const int64_t n = ctx->rs.n;
+  int32_t* hb = ctx->h_pin ? reinterpret_cast<int32_t*>(ctx->h_pin) : h.local_buf;
+  h.h_count = hb; h.h_off = hb + N_BINS; h.h_count2 = hb + 2 * N_BINS; h.h_off2 = hb + 3 * N_BINS; h.h_misc = hb + 4 * N_BINS;
+  int32_t *h_count = h.h_count, *h_off = h.h_off, *h_misc = h.h_misc;
+  h_misc[0] = 0;
+  h_misc[6] = 0;
+  if (ctx->h_pin) h.h_bxc = reinterpret_cast<uint32_t*>(ctx->h_pin + (24 << 10));
+  else { h.bxc_pageable.resize(BXC_WORDS); h.h_bxc = h.bxc_pageable.data(); }
+  for (int k = 0; k < BXC_COUNTERS; k++) h.h_bxc[k * BXC_STRIDE] = 0;
+  if (r.filtered) {
     HIPCHK(hipMemcpyAsync(&h_misc[0], ctx->d_filter_n, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(&h_misc[6], ctx->d_filter_n + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (bx) HIPCHK(hipMemcpyAsync(h_bxc, ctx->d_bx_ctr, BXC_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (r.bx) HIPCHK(hipMemcpyAsync(h.h_bxc, ctx->d_bx_ctr, BXC_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
   }
-  HIPCHK(hipMemcpyAsync(h_count, d_count, (size_t)N_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(h_count, c.d_count, (size_t)N_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  h_filter_n = (uint32_t)h_misc[0];
-  ctx->filter_proven += h_filter_n;
+  ctx->filter_proven += (uint32_t)h_misc[0];
   ctx->band_done += (uint32_t)h_misc[6];
   ctx->filter_seen += n;
-  // (with the band kernels still running beside this stream their counters are read behind the join, below)
-  const bool bx_counters_later = ctx->bx_pending_join;
-  auto take_bx_counters = [&]() {
-    ctx->filter_proven += h_bxc[BXC_DONE_PLAN * BXC_STRIDE];          // finished without any DP: by the diagonal filter or by the band plan
-    for (int k = 0; k < 3; k++) ctx->bx_done[k] += h_bxc[(BXC_DONE_PLAN + k) * BXC_STRIDE];
-    ctx->bx_seen += h_bxc[BXC_SEEN * BXC_STRIDE];
-    for (int k = 0; k < BXC_COUNTERS; k++) ctx->bx_last[k] = h_bxc[k * BXC_STRIDE];
-  };
-  if (!bx_counters_later) take_bx_counters();
+  h.bx_counters_later = c.pending_join;
+  if (!h.bx_counters_later) host_take_bx_counters(ctx, h);
   int run = 0;
   for (int b = 0; b < N_BINS; b++) {
     h_off[b] = run;
     run += b >= BIN_QUAD0 ? ((h_count[b] + 3) & ~3) : h_count[b];   // quad bins: every read length padded to whole quads
   }
-  const int quad_begin = h_off[BIN_QUAD0], n_quads = (run - quad_begin) / 4;
-  if (n_quads > 0) HIPCHK(hipMemsetAsync(ctx->d_list + quad_begin, 0xFF, (size_t)(run - quad_begin) * 4, ctx->stream));   // -1 = empty slot
-  HIPCHK(hipMemcpyAsync(d_off, h_off, (size_t)N_BINS * 4, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_plan_fill, dim3(gb), dim3(tb), 0, ctx->stream, n, ctx->d_bin_of, d_off, d_cursor, ctx->d_list);
+  h.quad_begin = h_off[BIN_QUAD0]; h.n_quads = (run - h.quad_begin) / 4;
+  if (h.n_quads > 0) HIPCHK(hipMemsetAsync(ctx->d_list + h.quad_begin, 0xFF, (size_t)(run - h.quad_begin) * 4, ctx->stream));   // -1 = empty slot
+  HIPCHK(hipMemcpyAsync(c.d_off, h_off, (size_t)N_BINS * 4, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_plan_fill, dim3(c.gb), dim3(256), 0, ctx->stream, n, ctx->d_bin_of, c.d_off, c.d_cursor, ctx->d_list);
   // reads that need the exact kernel from the start: copy their list to the head of wide_list
   const int n_wide0 = h_count[BIN_WIDE];
   if (n_wide0 > 0) {
     HIPCHK(hipMemcpyAsync(ctx->d_wide_list, ctx->d_list + h_off[BIN_WIDE], (size_t)n_wide0 * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_wide_count, &h_count[BIN_WIDE], 4, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(c.d_wide_count, &h_count[BIN_WIDE], 4, hipMemcpyHostToDevice, ctx->stream));
   }
   for (int ci = 0; ci < N_CPL; ci++) {
     if (h_count[ci] == 0) continue;
-    hipError_t e = ci == 0 ? launch_window<4>(ctx, ci, ctx->d_list + h_off[ci], h_count[ci])
-                 : ci == 1 ? launch_window<8>(ctx, ci, ctx->d_list + h_off[ci], h_count[ci])
-                           : launch_window<12>(ctx, ci, ctx->d_list + h_off[ci], h_count[ci]);
+    hipError_t e = launch_window_class(ctx, ci, ctx->d_list + h_off[ci], h_count[ci]);
     if (e != hipSuccess) { ctx->err = std::string("k_align_window launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
   }
-  int n_quads_trace = n_quads, quad_begin_trace = quad_begin;
-  bool wide_known = false;
-  if ((n_quads > 0 || filtered) && use_plain) {
-    // first pass: values only; reads whose alignment is provably the pure diagonal are finished there
-    if (n_quads > 0) {
-    const int grid = n_quads < ctx->quad_wgs ? n_quads : ctx->quad_wgs;
+  return MIA_HIP_OK;
+}
+
+// ... first pass over the quads: values only; reads whose alignment is provably the pure diagonal are finished there; what is left
+// (and what the filter's gap hint kept out of the first pass) is re-planned into quads of equal read length
+static int align_planner_host_plain(mia_hip_ctx* ctx, AlignCall& c, HostPlan& h) {
+  const int64_t n = ctx->rs.n;
+  if (h.n_quads > 0) {
+    const int grid = h.n_quads < ctx->quad_wgs ? h.n_quads : ctx->quad_wgs;
     const size_t quad_lds = (size_t)Q_G * q_sub_bytes(ctx->max_len) + 16;
     if (stage_begin(ctx, STG_PLAIN)) return MIA_HIP_ERR_NOMEM;
-    hipLaunchKernelGGL(k_align_quad_plain, dim3(grid), dim3(64), quad_lds, ctx->stream, ctx->rs, ref, ctx->d_pssm, ctx->d_list + quad_begin,
-                       n_quads, ctx->d_bin_of, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(k_align_quad_plain, dim3(grid), dim3(64), quad_lds, ctx->stream, ctx->rs, c.ref, ctx->d_pssm, ctx->d_list + h.quad_begin,
+                       h.n_quads, ctx->d_bin_of, (const int32_t*)nullptr);
     stage_end(ctx, STG_PLAIN);
     HIPCHK(hipGetLastError());
-    }
-    // re-plan what is left (and what the filter's gap hint kept out of the first pass) into quads of equal read length
-    HIPCHK(hipMemsetAsync(d_count, 0, (size_t)N_BINS * 4, ctx->stream));
-    HIPCHK(hipMemsetAsync(d_cursor, 0, (size_t)N_BINS * 4, ctx->stream));
-    hipLaunchKernelGGL(k_plan_recount, dim3(gb), dim3(tb), 0, ctx->stream, n, ctx->d_bin_of, d_count);
-    HIPCHK(hipMemcpyAsync(h_count2, d_count, (size_t)N_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    int run2 = 0;
-    for (int b = 0; b < N_BINS; b++) { h_off2[b] = run2; run2 += b >= BIN_QUAD0 ? ((h_count2[b] + 3) & ~3) : 0; }
-    n_quads_trace = run2 / 4;
-    quad_begin_trace = 0;
-    ctx->plain_total += (int64_t)n_quads * 4;
-    for (int b = BIN_QUAD0; b < N_BINS; b++) ctx->plain_retried += h_count2[b];
-    if (n_quads_trace > 0) {
-      HIPCHK(hipMemsetAsync(ctx->d_list, 0xFF, (size_t)run2 * 4, ctx->stream));
-      HIPCHK(hipMemcpyAsync(d_off, h_off2, (size_t)N_BINS * 4, hipMemcpyHostToDevice, ctx->stream));
-      hipLaunchKernelGGL(k_plan_fill, dim3(gb), dim3(tb), 0, ctx->stream, n, ctx->d_bin_of, d_off, d_cursor, ctx->d_list);
-    }
   }
-  if (n_quads_trace > 0) {
-    const int n_quads = n_quads_trace, quad_begin = quad_begin_trace;
-    const int64_t slab = (int64_t)Q_G * MAX_READ * Q_TRACE_STRIDE;
-    const int grid = n_quads < ctx->quad_wgs ? n_quads : ctx->quad_wgs;
-    if (!ctx->d_quad_slabs && hipMalloc((void**)&ctx->d_quad_slabs, (size_t)slab * ctx->quad_wgs) != hipSuccess) return MIA_HIP_ERR_NOMEM;
-    const size_t quad_lds = (size_t)Q_G * q_sub_bytes(ctx->max_len) + 16;
-    if (stage_begin(ctx, STG_TRACE)) return MIA_HIP_ERR_NOMEM;
-    hipLaunchKernelGGL(k_align_quad, dim3(grid), dim3(64), quad_lds, ctx->stream, ctx->rs, ref, ctx->d_pssm, ctx->packs.p[0], ctx->d_list + quad_begin,
-                       n_quads, ctx->d_quad_slabs, slab, ctx->d_wide_list, d_wide_count, ctx->d_retry_list, d_retry_count, /*band=*/1,
-                       ctx->dbg, (const int32_t*)nullptr);
-    stage_end(ctx, STG_TRACE);
-    HIPCHK(hipGetLastError());
-    // reads whose path left the stored trace band: one-read kernel with the full trace (windows <= 208 fit class 0)
-    // (the two counters sit side by side: one copy, one wait; the wide count is final unless the retry kernel runs)
-    HIPCHK(hipMemcpyAsync(&h_misc[2], d_wide_count, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const int32_t n_retry = h_misc[3];
-    if (n_retry > 0) {
-      hipError_t e = launch_window<4>(ctx, 0, ctx->d_retry_list, n_retry);
-      if (e != hipSuccess) { ctx->err = std::string("k_align_window retry launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
-    } else {
-      wide_known = true;
-    }
+  HIPCHK(hipMemsetAsync(c.d_count, 0, (size_t)N_BINS * 4, ctx->stream));
+  HIPCHK(hipMemsetAsync(c.d_cursor, 0, (size_t)N_BINS * 4, ctx->stream));
+  hipLaunchKernelGGL(k_plan_recount, dim3(c.gb), dim3(256), 0, ctx->stream, n, ctx->d_bin_of, c.d_count);
+  HIPCHK(hipMemcpyAsync(h.h_count2, c.d_count, (size_t)N_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  int run2 = 0;
+  for (int b = 0; b < N_BINS; b++) { h.h_off2[b] = run2; run2 += b >= BIN_QUAD0 ? ((h.h_count2[b] + 3) & ~3) : 0; }
+  ctx->plain_total += (int64_t)h.n_quads * 4;
+  for (int b = BIN_QUAD0; b < N_BINS; b++) ctx->plain_retried += h.h_count2[b];
+  h.n_quads = run2 / 4;
+  h.quad_begin = 0;
+  if (h.n_quads > 0) {
+    HIPCHK(hipMemsetAsync(ctx->d_list, 0xFF, (size_t)run2 * 4, ctx->stream));
+    HIPCHK(hipMemcpyAsync(c.d_off, h.h_off2, (size_t)N_BINS * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_plan_fill, dim3(c.gb), dim3(256), 0, ctx->stream, n, ctx->d_bin_of, c.d_off, c.d_cursor, ctx->d_list);
   }
-  if (ctx->bx_pending_join) { if (int rcj = bx_join_and_retry(ctx)) return rcj; wide_known = false; }
-  // exact kernel for whole-reference windows and escaped reads
-  if (!wide_known) {
-    HIPCHK(hipMemcpyAsync(&h_misc[2], d_wide_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (bx_counters_later) HIPCHK(hipMemcpyAsync(h_bxc, ctx->d_bx_ctr, BXC_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (bx_counters_later) take_bx_counters();
-  }
-  const int32_t n_wide = h_misc[2];
-  if (n_wide > 0) { if (int rcw = run_wide(ctx, ref, n_wide)) return rcw; }
-  ctx->aligned = true;
-  ctx->culled = false;
-  ctx->tallied = false;
-  ctx->pre_cull_valid = false;
   return MIA_HIP_OK;
+}
+
+// ... the trace pass over the quads, and the reads whose path left the stored trace band: one-read kernel with the full trace
+// (windows <= 208 fit class 0)
+static int align_planner_host_trace(mia_hip_ctx* ctx, AlignCall& c, HostPlan& h) {
+  const int64_t slab = (int64_t)Q_G * MAX_READ * Q_TRACE_STRIDE;
+  const int grid = h.n_quads < ctx->quad_wgs ? h.n_quads : ctx->quad_wgs;
+  if (!ctx->d_quad_slabs && hipMalloc((void**)&ctx->d_quad_slabs, (size_t)slab * ctx->quad_wgs) != hipSuccess) return MIA_HIP_ERR_NOMEM;
+  const size_t quad_lds = (size_t)Q_G * q_sub_bytes(ctx->max_len) + 16;
+  if (stage_begin(ctx, STG_TRACE)) return MIA_HIP_ERR_NOMEM;
+  hipLaunchKernelGGL(k_align_quad, dim3(grid), dim3(64), quad_lds, ctx->stream, ctx->rs, c.ref, ctx->d_pssm, ctx->packs.p[0], ctx->d_list + h.quad_begin,
+                     h.n_quads, ctx->d_quad_slabs, slab, ctx->d_wide_list, c.d_wide_count, ctx->d_retry_list, c.d_wide_count + 1, /*band=*/1,
+                     ctx->dbg, (const int32_t*)nullptr);
+  stage_end(ctx, STG_TRACE);
+  HIPCHK(hipGetLastError());
+  // (the two counters sit side by side: one copy, one wait; the wide count is final unless the retry kernel runs)
+  HIPCHK(hipMemcpyAsync(&h.h_misc[2], c.d_wide_count, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const int32_t n_retry = h.h_misc[3];
+  if (n_retry > 0) {
+    hipError_t e = launch_window_class(ctx, 0, ctx->d_retry_list, n_retry);
+    if (e != hipSuccess) { ctx->err = std::string("k_align_window retry launch: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
+  } else {
+    h.wide_known = true;
+  }
+  return MIA_HIP_OK;
+}
+
+static int align_planner_host(mia_hip_ctx* ctx, AlignCall& c) {
+  const AlignRoute& r = c.r;
+  HostPlan h;
+  if (int rc = align_planner_host_fill(ctx, c, h)) return rc;
+  if ((h.n_quads > 0 || r.filtered) && r.use_plain) { if (int rc = align_planner_host_plain(ctx, c, h)) return rc; }
+  if (h.n_quads > 0) { if (int rc = align_planner_host_trace(ctx, c, h)) return rc; }
+  if (c.pending_join) { if (int rcj = bx_join_and_retry(ctx, c)) return rcj; h.wide_known = false; }
+  // exact kernel for whole-reference windows and escaped reads
+  if (!h.wide_known) {
+    HIPCHK(hipMemcpyAsync(&h.h_misc[2], c.d_wide_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (h.bx_counters_later) HIPCHK(hipMemcpyAsync(h.h_bxc, ctx->d_bx_ctr, BXC_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (h.bx_counters_later) host_take_bx_counters(ctx, h);
+  }
+  const int32_t n_wide = h.h_misc[2];
+  if (n_wide > 0) { if (int rcw = run_wide(ctx, c.ref, n_wide)) return rcw; }
+  return align_close(ctx);
+}
+
+// every strand_known read against its window of ctx->d_ref: plan, values-only pass, trace kernels, exact kernel
+static int align_all(mia_hip_ctx* ctx) {
+  const int64_t n = ctx->rs.n;
+  if (!ctx->spec_ok) { ctx->spec_pending = false; ctx->abort_if = nullptr; }
+  ctx->align_end_signalled = false;
+  ctx->buckets_queued = 0;                  // (a counting sort queued for an earlier alignment is void)
+  if (n == 0) { ctx->aligned = true; return MIA_HIP_OK; }
+  AlignCall c;
+  c.r = align_route(align_route_in(ctx));
+  const AlignRoute& r = c.r;
+  c.ref = RefInfo{ctx->d_ref, ctx->L, ctx->wrap, ctx->explicit_win};
+  c.d_count = ctx->d_bins; c.d_off = ctx->d_bins + N_BINS; c.d_cursor = ctx->d_bins + 2 * N_BINS; c.d_wide_count = ctx->d_bins + 3 * N_BINS;
+  c.gb = (int)((n + (int64_t)256 * PLAN_PER - 1) / ((int64_t)256 * PLAN_PER));
+  c.dbg_steps = ctx->deferred && alt_env("MIA_HIP_ITER_DEBUG") != nullptr;
+  if (int rc = align_ensure_buffers(ctx, c)) return rc;
+  if (int rc = align_ref_prep(ctx, c)) return rc;
+  if (r.bx) {
+    align_bx_dev(ctx, c);
+    if (int rc = align_plan_launches(ctx, c)) return rc;
+    if (r.three_streams) { if (int rc = align_band_dps(ctx, c)) return rc; }
+    else if (r.two_streams) { if (int rc = align_band_dps_serial(ctx, c)) return rc; }
+    ctx->bx_launches++;
+  } else if (r.filtered) {
+    if (int rc = align_round1(ctx, c)) return rc;
+  }
+  c.ps = r.planner_aside ? ctx->stream2 : ctx->stream;
+  if (r.plan_count_late)
+    hipLaunchKernelGGL(k_plan_count, dim3(c.gb), dim3(256), 0, c.ps, ctx->rs, c.ref, ctx->packs, /*use_quad=*/1, (int)r.filtered, (int)(r.filtered && r.use_plain), ctx->d_bin_of,
+                       c.d_count, ctx->d_filter_n);
+  if (!ctx->deferred) return align_planner_host(ctx, c);
+  if (int rc = align_planner_deferred(ctx, c)) return rc;
+  return align_finish_deferred(ctx, c);
 }
 
 extern "C" int mia_hip_align_windows(mia_hip_ctx* ctx, const char* ref, int64_t ref_len, const int64_t* win_start, const int32_t* win_len) {
