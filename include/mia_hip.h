@@ -315,6 +315,22 @@ int mia_hip_ma_region(mia_hip_ctx *ctx, int32_t first, int32_t last, int64_t *n_
  * buffers hold (>= n_rows).  Either pointer may be NULL. */
 int mia_hip_get_ma_region(mia_hip_ctx *ctx, int64_t *rows, char *text, int64_t cap_rows);
 
+/* The read blocks of ace_output (src/io.c:756-913; ma -f 7) for the records of the last mia_hip_ma_tally, in record order.
+ * With G[p] = gaps[0] + .. + gaps[p-1] (and gaps[ref_len] = 0: a record may end on column ref_len) a record of columns start .. end gets
+ *   af_pos      = start + G[start] + 1                       the position its AF line prints
+ *   padded_len  = (end - start + 1) + G[end+1] - G[start]    the characters of its padded read; the RD and QA lines print
+ *                                                            this plus whatever its SEQ string held behind column end
+ *   its text: for every column its gaps[p] insert characters -- on the record's own first column too -- namely the insert
+ *   the record has there, cut off at gaps[p], then '*'; then its seq character; '-' as '*'; cut into lines of 50 with a
+ *   newline each, and the remainder line (empty when padded_len is a multiple of 50) with its newline:
+ *   padded_len + padded_len / 50 + 1 bytes.  Of several INS_POS pairs of one position the last one given counts.
+ * body_bytes = the bytes of all texts.  MIA_HIP_ERR_STATE without a mia_hip_ma_tally before; MIA_HIP_ERR_ARG when gaps[0] > 0
+ * (the reference reads past its consensus string then) or a gap is negative; the context stays usable. */
+int mia_hip_ma_ace(mia_hip_ctx *ctx, int64_t *n_records, int64_t *body_bytes);
+/* af_pos[n], padded_len[n], body_off[n+1] (record r's text is body[body_off[r] .. body_off[r+1])), body[body_bytes];
+ * cap_bytes = bytes body holds.  Any pointer may be NULL. */
+int mia_hip_get_ma_ace(mia_hip_ctx *ctx, int64_t *af_pos, int64_t *padded_len, int64_t *body_off, char *body, int64_t cap_bytes);
+
 /* ---- Myers edit distance -------------------------------------------------- */
 
 /* unsigned myers_diff(const char *seq_a, enum myers_align_mode mode, const char* seq_b, int maxd,
@@ -393,7 +409,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

@@ -23,7 +23,7 @@ struct MaRegionView {
   const int64_t* col_off;    // [n+1]: record r owns seq[col_off[r] .. col_off[r+1]) = columns start .. end
   const char* seq;
   const int32_t* rec_ins;    // [n+1]: record r owns ins_list[rec_ins[r] .. rec_ins[r+1])
-  const int32_t* ins_list;   // pair numbers, by record, in the order they were given
+  const int32_t* ins_list;   // pair numbers, by record, ascending ins_pos; pairs of one position in the order they were given
   const int32_t* ins_pos;    // per pair: the insert sits in front of column start + ins_pos
   const int64_t* ins_off;    // per pair (+1): its bases are ins_bases[ins_off[e] .. ins_off[e+1])
   const char* ins_bases;

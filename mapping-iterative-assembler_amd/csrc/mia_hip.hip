@@ -26,14 +26,15 @@
 #include "mia_peak_kernels.h"
 #include "mia_iter_kernels.h"
 #include "mia_ma_region_kernels.h"
+#include "mia_ma_ace_kernels.h"
 
 using namespace mia;
 
 // timed stages (HIP events on the context's stream around the kernel launches of that kind)
-enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_COUNT };
+enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_COUNT };
 static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan",
                                                    "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select",
-                                                   "k_ma_region_render"};
+                                                   "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render"};
 
 // One device block for every small counter of an iteration (planner bins and header, filter / band-pipeline counters, link
 // count, cull and tally flags, insert-event count): one memset at the start of the alignment clears them all, and one copy
@@ -247,6 +248,10 @@ struct mia_hip_ctx {
   char *d_ma_seq = nullptr, *d_ma_ib = nullptr, *d_ma_text = nullptr; int64_t ma_text_cap = 0;
   unsigned long long* d_ma_ctl = nullptr;
   int32_t ma_first = 0, ma_last = -1; int64_t ma_rows = 0, ma_width = 0; bool ma_region_done = false;
+  // ... and for mia_hip_ma_ace: whether the job has an ACE export at all (GAPS, the records' columns), the running sum of ref->gaps,
+  // per record the AF position, the padded length and the offset of its text, the text
+  bool ma_ace_gaps_ok = false, ma_ace_cols_ok = false, ma_ace_done = false; int64_t ma_ace_bytes = 0, ma_ace_cap = 0, ma_ace_rec_cap = 0, ma_ace_g_cap = 0;
+  int64_t *d_ace_g = nullptr, *d_ace_af = nullptr, *d_ace_len = nullptr, *d_ace_off = nullptr; char* d_ace_body = nullptr;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------
@@ -471,7 +476,8 @@ extern "C" void mia_hip_destroy(mia_hip_ctx* ctx) {
   if (ctx->d_open_list) (void)hipFree(ctx->d_open_list);
   if (ctx->d_kbits) (void)hipFree(ctx->d_kbits);
   for (void* p : {(void*)ctx->d_ma_start, (void*)ctx->d_ma_gaps, (void*)ctx->d_ma_ipos, (void*)ctx->d_ma_rec_ins, (void*)ctx->d_ma_ins_list, (void*)ctx->d_ma_coff,
-                  (void*)ctx->d_ma_ioff, (void*)ctx->d_ma_colmap, (void*)ctx->d_ma_rows, (void*)ctx->d_ma_seq, (void*)ctx->d_ma_ib, (void*)ctx->d_ma_text, (void*)ctx->d_ma_ctl})
+                  (void*)ctx->d_ma_ioff, (void*)ctx->d_ma_colmap, (void*)ctx->d_ma_rows, (void*)ctx->d_ma_seq, (void*)ctx->d_ma_ib, (void*)ctx->d_ma_text, (void*)ctx->d_ma_ctl,
+                  (void*)ctx->d_ace_g, (void*)ctx->d_ace_af, (void*)ctx->d_ace_len, (void*)ctx->d_ace_off, (void*)ctx->d_ace_body})
     if (p) (void)hipFree(p);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);

@@ -99,8 +99,11 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
     return MIA_HIP_ERR_ARG;
   if (!ctx->have_pssm) { ctx->err = "set_pssm must precede ma_tally"; return MIA_HIP_ERR_STATE; }
   HIPCHK(hipSetDevice(ctx->device));
-  for (int64_t r = 0; r < n; r++)
+  bool cols_ok = true;                             // (a record past the reference is the tally's to refuse; one of no columns it never sees)
+  for (int64_t r = 0; r < n; r++) {
     if (col_off[r + 1] < col_off[r] || start[r] < 0) { ctx->err = "malformed record geometry"; return MIA_HIP_ERR_ARG; }
+    cols_ok = cols_ok && (int64_t)start[r] + (col_off[r + 1] - col_off[r]) <= (int64_t)ref_len + 1;   // (a circular assembly's record may end on column L)
+  }
   for (int64_t e = 0; e < n_ins; e++)
     if (ins_record[e] < 0 || ins_record[e] >= n || ins_off[e + 1] < ins_off[e]) { ctx->err = "malformed insert list"; return MIA_HIP_ERR_ARG; }
   ctx->L = ref_len;
@@ -120,7 +123,8 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   if (rc) return rc;
   const int Lp = ctx->tb.Lp;
   const int64_t chars = n ? col_off[n] : 0;
-  // the INS_POS pairs by record (mia_hip_ma_region fetches a record's own range): a stable counting sort of the pair numbers
+  // the INS_POS pairs by record (mia_hip_ma_region and mia_hip_ma_ace fetch a record's own range): a stable counting sort of the
+  // pair numbers, and inside a record ascending positions (ma_ace_order_inserts: a record's pair is found by bisection)
   if (n > INT32_MAX - 1 || n_ins > INT32_MAX - 1) { ctx->err = "ma_tally: more than 2^31 records or INS_POS pairs"; return MIA_HIP_ERR_ARG; }
   std::vector<int32_t> rec_ins((size_t)n + 1, 0), ins_list((size_t)n_ins);
   for (int64_t e = 0; e < n_ins; e++) rec_ins[(size_t)ins_record[e] + 1]++;
@@ -128,11 +132,16 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   {
     std::vector<int32_t> cursor(rec_ins.begin(), rec_ins.end() - 1);
     for (int64_t e = 0; e < n_ins; e++) ins_list[(size_t)cursor[(size_t)ins_record[e]]++] = (int32_t)e;
+    for (int64_t r = 0; r < n; r++)
+      ma_ace_order_inserts(ins_list.data() + rec_ins[(size_t)r], rec_ins[(size_t)r + 1] - rec_ins[(size_t)r], ins_pos);
   }
   // The records stay on the device behind this call (mia_hip_ma_region reads them): buffers of the context, made here, before anything
   // is queued.  Strand, depth codes and the pairs' record numbers are needed by the tally alone.
   ctx->ma_resident = false;
   ctx->ma_region_done = false;
+  ctx->ma_ace_done = false;
+  ctx->ma_ace_gaps_ok = ma_ace_gaps_ok(gaps, ref_len);
+  ctx->ma_ace_cols_ok = cols_ok;
   int32_t* d_irec = nullptr;
   uint8_t* d_rev = nullptr;
   char* d_smp = nullptr;
@@ -236,6 +245,75 @@ extern "C" int mia_hip_get_ma_region(mia_hip_ctx* ctx, int64_t* rows, char* text
   if (rows && ctx->ma_rows > 0) HIPCHK(hipMemcpyAsync(rows, ctx->d_ma_rows, (size_t)ctx->ma_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (text && ctx->ma_rows > 0 && ctx->ma_width > 0)
     HIPCHK(hipMemcpyAsync(text, ctx->d_ma_text, (size_t)(ctx->ma_rows * ctx->ma_width), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return MIA_HIP_OK;
+}
+
+// The read blocks of ace_output (src/io.c:807-889) for the records of the last mia_hip_ma_tally: see mia_ma_ace_kernels.h
+extern "C" int mia_hip_ma_ace(mia_hip_ctx* ctx, int64_t* n_records, int64_t* body_bytes) {
+  if (!ctx || !n_records || !body_bytes) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_ace"; return MIA_HIP_ERR_STATE; }
+  if (!ctx->ma_ace_gaps_ok) { ctx->err = "ma_ace: GAPS opens insert columns in front of column 0, or holds a negative value: no ACE export"; return MIA_HIP_ERR_ARG; }
+  if (!ctx->ma_ace_cols_ok) { ctx->err = "ma_ace: a record reaches past the reference"; return MIA_HIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->ma_ace_done = false;
+  const int64_t n = ctx->ma_n;
+  const int32_t L = ctx->ma_L, n_wgs = (int32_t)((n + MAR_PER_WG - 1) / MAR_PER_WG);
+  if (ctx->ma_ace_g_cap < (int64_t)L + 2) {
+    ctx->ma_ace_g_cap = 0;
+    if (dev_alloc(ctx, &ctx->d_ace_g, (size_t)L + 2)) return MIA_HIP_ERR_NOMEM;
+    ctx->ma_ace_g_cap = (int64_t)L + 2;
+  }
+  if (ctx->ma_ace_rec_cap < n + 1) {
+    ctx->ma_ace_rec_cap = 0;
+    if (dev_alloc(ctx, &ctx->d_ace_af, (size_t)n + 1) || dev_alloc(ctx, &ctx->d_ace_len, (size_t)n + 1) || dev_alloc(ctx, &ctx->d_ace_off, (size_t)n + 1)) return MIA_HIP_ERR_NOMEM;
+    ctx->ma_ace_rec_cap = n + 1;
+  }
+  MaAceView v{n, ctx->d_ma_start, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos, ctx->d_ma_ioff, ctx->d_ma_ib, ctx->d_ace_g};
+  hipLaunchKernelGGL(k_ma_ace_gaps, dim3(1), dim3(MAA_SCAN_THREADS), 0, ctx->stream, (const int32_t*)ctx->d_ma_gaps, L, ctx->d_ace_g);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(ctx->d_ma_ctl, 0, ((size_t)MAR_STATE + (size_t)n_wgs) * 8, ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->d_ace_off, 0, 8, ctx->stream));         // (no records: the one offset there is)
+  if (n_wgs > 0) {
+    if (stage_launch(ctx, STG_MA_ACE_LAYOUT, k_ma_ace_layout, dim3((unsigned)n_wgs), dim3(MAR_THREADS), 0, ctx->stream, v, n_wgs, ctx->d_ma_ctl, ctx->d_ace_af,
+                     ctx->d_ace_len, ctx->d_ace_off))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+  }
+  unsigned long long hdr[MAR_STATE] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(hdr, ctx->d_ma_ctl, sizeof hdr, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const int64_t bytes = (int64_t)hdr[MAR_ROWS];
+  if (bytes < n) { ctx->err = "ma_ace: the layout came back inconsistent"; return MIA_HIP_ERR_DEVICE; }   // (a record's text holds a newline at least)
+  if (n > 0) {
+    if (ctx->ma_ace_cap < bytes) {
+      ctx->ma_ace_cap = 0;
+      if (dev_alloc(ctx, &ctx->d_ace_body, (size_t)bytes)) return MIA_HIP_ERR_NOMEM;
+      ctx->ma_ace_cap = bytes;
+    }
+    if (stage_launch(ctx, STG_MA_ACE_RENDER, k_ma_ace_render, dim3((unsigned)((n + MAR_THREADS / 64 - 1) / (MAR_THREADS / 64))), dim3(MAR_THREADS), 0, ctx->stream, v,
+                     (const int64_t*)ctx->d_ace_off, ctx->d_ace_body))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  ctx->ma_ace_bytes = bytes;
+  ctx->ma_ace_done = true;
+  *n_records = n;
+  *body_bytes = bytes;
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_ace(mia_hip_ctx* ctx, int64_t* af_pos, int64_t* padded_len, int64_t* body_off, char* body, int64_t cap_bytes) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident || !ctx->ma_ace_done) { ctx->err = "ma_ace first"; return MIA_HIP_ERR_STATE; }
+  if (body && cap_bytes < ctx->ma_ace_bytes) { ctx->err = "get_ma_ace: buffer too small"; return MIA_HIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t n = ctx->ma_n;
+  if (af_pos && n > 0) HIPCHK(hipMemcpyAsync(af_pos, ctx->d_ace_af, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (padded_len && n > 0) HIPCHK(hipMemcpyAsync(padded_len, ctx->d_ace_len, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (body_off) HIPCHK(hipMemcpyAsync(body_off, ctx->d_ace_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (body && ctx->ma_ace_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_ace_body, (size_t)ctx->ma_ace_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }

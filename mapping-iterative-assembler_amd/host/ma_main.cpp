@@ -1,14 +1,17 @@
 // ma_hip -- the reference's `ma` report tool (/root/reference/src/map_assembler.c): -f 1 (clustalw, the default), -f 2 (line
 // format), -f 5 (assembled sequence as FASTA), -f 41 and -f 4 (per-column table), -f 6 and -f 61 (the fragments of a region,
-// -R).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
+// -R), -f 7 (ACE export, every record in full) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
 // find_ins_cons run on the GPU (mia_hip_ma_tally, every record counts, dropped or not), and so do the selection and the
-// rows of the region view (mia_hip_ma_region); calling, phred score and printing follow src/map_alignment.c:107-220,
-// src/map_align.c:152-227,294-391,543-759 and src/io.c:929-1085.  Formats 3 and 7 and -m stay outside.  No CPU fallback.
+// rows of the region view (mia_hip_ma_region) and the padded reads of the ACE export (mia_hip_ma_ace); calling, phred score and
+// printing follow src/map_alignment.c:107-220, src/map_align.c:152-227,294-391,543-759 and src/io.c:756-913,929-1085.  Format 3
+// (show_consensus walks every record per column on the host and prints per-record lines no kernel here produces) stays outside.
+// No CPU fallback.
 #include <ctype.h>
 #include <float.h>
 #include <getopt.h>
 #include <limits.h>
 #include <math.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,6 +22,7 @@
 
 #include "../../include/mia_hip.h"
 #include "maln_text.h"
+#include "../csrc/ma_ace_body.h"
 
 namespace {
 
@@ -27,13 +31,14 @@ using namespace maln_text;
 typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6 or 61>\n   -R <REGION_START:REGION_END>\n"
-         "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n"
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6, 61 or 7>\n   -R <REGION_START:REGION_END>\n"
+         "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
          "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
          "(-f 1 clustalw, the default; -f 2 one line each plus coverage), the per-column table (-f 41 all positions, -f 4\n"
          "positions that differ from the reference), the assembled sequence (-f 5), and the reference, the consensus and every\n"
          "fragment of a region (-f 6, as multi-FASTA -f 61; -R, default 90:109).  Tallies, the selection of the fragments and\n"
-         "their rows are computed on the MI355X.  Formats 3 and 7 and -m are outside the accelerated path.\n");
+         "their rows are computed on the MI355X, and so are the padded reads of the ACE export (-f 7).  -m writes the .maln\n"
+         "again: records sorted, -c and -I applied.  Format 3 is outside the accelerated path.\n");
 }
 
 void read_ma(const char* fn, Maln* m) { read_maln_file(fn, m); }
@@ -117,6 +122,72 @@ void color_print(const char* s, size_t len) {
   printf("\33[0m\n");
 }
 
+// Output of the ACE export: one buffer, written out whenever it has grown past a few megabytes
+struct Out {
+  std::string buf;
+  void flush() { if (!buf.empty()) { fwrite(buf.data(), 1, buf.size(), stdout); buf.clear(); } }
+  void room() { if (buf.size() > ((size_t)4 << 20)) flush(); }
+  void fmt(const char* f, ...) __attribute__((format(printf, 2, 3))) {
+    char line[1024];
+    va_list ap;
+    va_start(ap, f);
+    const int k = vsnprintf(line, sizeof line, f, ap);
+    va_end(ap);
+    if (k > 0) buf.append(line, (size_t)k < sizeof line ? (size_t)k : sizeof line - 1);
+  }
+};
+
+// the consensus block of ace_output (src/io.c:780-793, 893-906): lines of 50, '-' as '*', ' ' as 'X', the remainder line even when empty
+void ace_consensus(Out& o, const std::string& cons) {
+  size_t at = o.buf.size(), line_pos = 0;
+  o.buf.resize(at + cons.size() + cons.size() / 50 + 1);
+  for (char c : cons) {
+    o.buf[at++] = c == '-' ? '*' : (c == ' ' ? 'X' : c);
+    if (++line_pos == 50) { o.buf[at++] = '\n'; line_pos = 0; }
+  }
+  o.buf[at++] = '\n';
+}
+
+// ace_output, src/io.c:756-913: everything but the padded reads, which come from the device already cut into lines
+void ace_print(const Maln& m, const std::string& cons, const std::vector<int64_t>& af_pos, const std::vector<int64_t>& padded_len,
+               const std::vector<int64_t>& body_off, const std::string& body) {
+  Out o;
+  const size_t n = m.rec.size();
+  const long long number_bases = (long long)cons.size();   // get_consensus_length: gaps[0] is 0 here, so it is the string's length
+  o.fmt("AS %d %zu\n\n", 1, n + 1);
+  o.buf += "CO " + m.ref_id;
+  o.fmt(" %lld %zu %d %c\n", number_bases, n + 1, 1, 'U');
+  ace_consensus(o, cons);
+  o.buf += "\nBQ\n";
+  for (size_t i = 0; i < cons.size(); i++) {
+    if (cons[i] != '-') o.buf += "40 ";
+    if (i % 50 == 0) o.buf += '\n';
+  }
+  o.buf += "\n\nAF FAKE_READ-IGNORE_ME U 1\n";
+  for (size_t r = 0; r < n; r++) {
+    o.buf += "AF " + m.rec[r].id;
+    o.fmt(" %c %lld\n", m.rec[r].rc ? 'C' : 'U', (long long)af_pos[r]);
+    o.room();
+  }
+  o.fmt("\nBS 1 %lld FAKE_READ-IGNORE_ME\n\n", number_bases);
+  for (size_t r = 0; r < n; r++) {
+    const MalnRecord& a = m.rec[r];
+    // strlen(aln_seq->seq) + gaps: what the SEQ string held behind column END counts, though it is not printed
+    const long long len = (long long)padded_len[r] + ((long long)a.seq_raw.size() - (long long)a.seq.size());
+    o.buf += "RD " + a.id;
+    o.fmt(" %lld 0 0\n", len);
+    o.buf.append(body, (size_t)body_off[r], (size_t)(body_off[r + 1] - body_off[r]));
+    o.fmt("\nQA 1 %lld 1 %lld\n", len, len);
+    o.buf += "DS CHROMAT_FILE: " + a.id + " PHD_FILE: " + a.id + "_FAKE.phd TIME: Tue Feb 21 15:42:35 1984\n\n";
+    o.room();
+  }
+  o.fmt("RD FAKE_READ-IGNORE_ME %lld 0 0\n", number_bases);
+  ace_consensus(o, cons);
+  o.fmt("\n\nQA 1 %lld 1 %lld\n", number_bases, number_bases);
+  o.buf += "DS CHROMAT_FILE: FAKE_READ PHD_FILE: FAKE_READ_FAKE.phd TIME: Tue Feb 21 23:23:23 1984\n";
+  o.flush();
+}
+
 void die(mia_hip_ctx* g, const char* what) {
   fprintf(stderr, "%s: %s\n", what, g ? mia_hip_last_error(g) : "no context");
   exit(1);
@@ -125,8 +196,8 @@ void die(mia_hip_ctx* g, const char* what) {
 }  // namespace
 
 int main(int argc, char* argv[]) {
-  std::string ma_in_fn, assign_id;
-  bool id_assigned = false, in_ma = false, any_arg = false;
+  std::string ma_in_fn, assign_id, ma_out_fn;
+  bool id_assigned = false, in_ma = false, any_arg = false, out_ma = false;
   int cons_scheme = 1, out_format = 1, gpu = 0, reg_start = 90, reg_end = 109;
   bool in_color = false;
   double score_int = -1.0, score_slo = -1.0;
@@ -142,7 +213,7 @@ int main(int argc, char* argv[]) {
       case 's': score_slo = atof(optarg); any_arg = true; break;
       case 'b': score_int = atof(optarg); any_arg = true; break;
       case 'C': in_color = true; break;
-      case 'm': fprintf(stderr, "option -m (rewrite the .maln) is outside the MI355X-accelerated path and is not supported by ma_hip\n"); exit(1);
+      case 'm': ma_out_fn = optarg; out_ma = true; any_arg = true; break;
       case 'M': ma_in_fn = optarg; in_ma = true; any_arg = true; break;
       case 'd': any_arg = true; break;
       case 'g': gpu = atoi(optarg); break;
@@ -150,13 +221,23 @@ int main(int argc, char* argv[]) {
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61) {
-    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6 and 61 are); use the reference's ma\n", out_format);
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61 && out_format != 7) {
+    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are); use the reference's ma\n", out_format);
     exit(1);
   }
   Maln m;
   read_ma(ma_in_fn.c_str(), &m);
   if (id_assigned) m.ref_id = assign_id.substr(0, 256);
+  if (out_format == 7 && !mia::ma_ace_gaps_ok(m.gaps.data(), m.L)) {
+    fprintf(stderr, "ma_hip: %s has no ACE export: its GAPS line opens insert columns in front of column 0 or holds a negative value\n", ma_in_fn.c_str());
+    exit(1);
+  }
+  // write_ma (src/map_assembler.c:214-217): after whatever report -f selected
+  auto finish = [&](mia_hip_ctx* ctx) {
+    mia_hip_destroy(ctx);
+    if (out_ma) { fflush(stdout); if (!write_maln_file(ma_out_fn.c_str(), m, cons_scheme)) exit(1); }
+    return 0;
+  };
 
   mia_hip_ctx* g = nullptr;
   if (mia_hip_create(&g, gpu) != MIA_HIP_OK) { fprintf(stderr, "ma_hip: no usable MI355X (gfx950) device %d; there is no CPU fallback\n", gpu); exit(1); }
@@ -178,8 +259,7 @@ int main(int argc, char* argv[]) {
     for (; i + FASTA_LINE_WIDTH <= clen; i += FASTA_LINE_WIDTH) { fwrite(&cons[(size_t)i], 1, FASTA_LINE_WIDTH, stdout); fputc('\n', stdout); }
     fwrite(&cons[(size_t)i], 1, (size_t)(clen - i), stdout);
     fputc('\n', stdout);
-    mia_hip_destroy(g);
-    return 0;
+    return finish(g);
   }
   // the other formats: BaseCounts of every column from the device, calls and the double-valued columns here
   std::vector<int32_t> tally((size_t)MIA_HIP_TALLY_WORDS * (size_t)(L + 1)), dgaps((size_t)L + 1), ins_off((size_t)L + 1);
@@ -223,7 +303,16 @@ int main(int argc, char* argv[]) {
       aln_ref += m.ref_seq[(size_t)p];
       cov.push_back(b.cov);
     }
-    if (out_format == 1) clustalw_print_cons(cons, aln_ref, m.ref_id);
+    if (out_format == 7) {
+      // ace_output, src/io.c:756-913: cons is get_consensus' string; the padded reads of all records come from the device
+      int64_t n_rec = 0, body_bytes = 0;
+      if (mia_hip_ma_ace(g, &n_rec, &body_bytes) != MIA_HIP_OK) die(g, "ma_ace");
+      std::vector<int64_t> af_pos((size_t)n_rec + 1), padded_len((size_t)n_rec + 1), body_off((size_t)n_rec + 1);
+      std::string body((size_t)body_bytes + 1, '\0');
+      if (mia_hip_get_ma_ace(g, af_pos.data(), padded_len.data(), body_off.data(), &body[0], body_bytes) != MIA_HIP_OK) die(g, "get_ma_ace");
+      if (n_rec != n) { fprintf(stderr, "ma_hip: the export holds %lld records, the file %lld\n", (long long)n_rec, (long long)n); exit(1); }
+      ace_print(m, cons, af_pos, padded_len, body_off, body);
+    } else if (out_format == 1) clustalw_print_cons(cons, aln_ref, m.ref_id);
     else if (out_format == 2) {                       // line_print_cons, src/io.c:1032-1042
       printf("Consensus, %s, coverage:\n%s\n%s\n", m.ref_id.c_str(), cons.c_str(), aln_ref.c_str());
       for (int c : cov) printf("%d ", c);
@@ -258,8 +347,7 @@ int main(int argc, char* argv[]) {
         }
       }
     }
-    mia_hip_destroy(g);
-    return 0;
+    return finish(g);
   }
   for (int p = 0; p < L; p++) {
     if (m.gaps[(size_t)p] > 0 && p > 0) {           // find_ins_cons (src/map_align.c:444-510)
@@ -277,6 +365,5 @@ int main(int argc, char* argv[]) {
     const char cb = find_consensus(b, cons_scheme, &frac);
     if (out_format == 41 || m.ref_seq[(size_t)p] != cb) show_single_pos(p, m.ref_seq[(size_t)p], cb, b, frac);
   }
-  mia_hip_destroy(g);
-  return 0;
+  return finish(g);
 }

@@ -1,15 +1,17 @@
 // maln_text.h -- reading the text of a .maln file the way the reference's read_ma does (src/map_alignment.c:384-607:
-// fgets with MAX_LINE_LEN, sscanf "KEY %s" / "KEY %d", fscanf " %d %s" for the insert list).  Shared by ma_hip and
-// ccheck_hip; ccheck_hip keeps its own record layout, ma_hip's (MalnFile, read_maln_file) is here so that a host-only caller can
-// read a .maln the same way.
+// fgets with MAX_LINE_LEN, sscanf "KEY %s" / "KEY %d", fscanf " %d %s" for the insert list), and writing it again the way
+// write_ma does (:283-382; ma -m).  Shared by ma_hip and ccheck_hip; ccheck_hip keeps its own record layout, ma_hip's
+// (MalnFile, read_maln_file, write_maln_file) is here so that a host-only caller can read and write a .maln the same way.
 #pragma once
 #include <ctype.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 #include <algorithm>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -104,20 +106,23 @@ inline bool slurp(const char* fn, std::string* buf) {
 
 // ---- a whole .maln as ma reads it (read_ma, src/map_alignment.c:384-607) -------------------------------------------------
 constexpr int PSSM_DEPTH = 15;   // src/params.h:21
+constexpr int INIT_NUM_ALN_SEQS = 16000;   // src/params.h:69
 
 struct MalnRecord {
-  std::string id;
-  int start = 0, end = 0, rc = 0, trimmed = 0, num_inputs = 1;
+  std::string id, desc;                       // desc: the DESC line behind "DESC " (src/map_alignment.c:551-552)
+  int start = 0, end = 0, rc = 0, trimmed = 0, num_inputs = 1, score = 0, dropped = 0;
   char segment = 'n';
   std::string seq, smp;                       // columns start .. end
+  std::string seq_raw, smp_raw;               // the SEQ and SMP strings as read: write_ma writes them whole, ace_output counts strlen(SEQ)
   std::vector<int32_t> ins_pos;               // INS_POS pairs, in file order
   std::vector<std::string> ins_seq;
 };
 
 // The records flattened the way mia_hip_ma_tally takes them, in the order of `rec`.
 struct MalnFile {
-  std::string ref_id, ref_seq;
+  std::string ref_id, ref_seq, ref_desc;
   int L = 0;
+  int maln_siz = 0, ref_size = 0, depth = 15; // maln->size as read_ma leaves it, ref->size, fpsm->depth
   std::vector<int32_t> gaps;
   int32_t fpsm[31][5][5], rpsm[31][5][5];
   std::vector<MalnRecord> rec;
@@ -164,14 +169,16 @@ inline void read_maln_file(const char* fn, MalnFile* m) {
   if (line.find("/* map_alignment") == std::string::npos) maln_bad("%s does not look like a map_alignment input file\n", fn);
   int nas = 0, tmp = 0;
   c.line(&line); field_int(line, "MALN_NAS", &nas);
-  c.line(&line);                       // MALN_SIZ: only sizes an array
+  c.line(&line);                       // MALN_SIZ: the record array doubles from INIT_NUM_ALN_SEQS until it is that large (:415-419)
+  m->maln_siz = INIT_NUM_ALN_SEQS;
+  if (field_int(line, "MALN_SIZ", &tmp)) while (m->maln_siz < tmp && m->maln_siz <= (1 << 29)) m->maln_siz *= 2;
   c.line(&line);                       // MALN_COC: overridden by -c (src/map_assembler.c:191)
   c.line(&line);
   if (line.find("__REFERENCE__") == std::string::npos) maln_bad("Do not see reference sequence header in %s\n", fn);
   c.line(&line); field(line, "ID", &m->ref_id);
-  c.line(&line);                       // DESC
+  c.line(&line); m->ref_desc.clear(); field(line, "DESC", &m->ref_desc);
   c.line(&line); field_int(line, "LEN", &m->L);
-  c.line(&line);                       // SIZE
+  c.line(&line); m->ref_size = 0; field_int(line, "SIZE", &m->ref_size);
   c.line(&line); field(line, "SEQ", &m->ref_seq);
   if ((int)m->ref_seq.size() != m->L) {
     fprintf(stderr, "Reported length of reference sequence %d is not observed length %d\n", m->L, (int)m->ref_seq.size());
@@ -186,6 +193,7 @@ inline void read_maln_file(const char* fn, MalnFile* m) {
   if (line.find("__PSSM__") == std::string::npos) { fprintf(stderr, "Do not see __PSSM__ line in %s\n", fn); exit(2); }
   int depth = PSSM_DEPTH;
   c.line(&line); field_int(line, "DEPTH", &depth);
+  m->depth = depth;
   c.line(&line);
   if (line.find("FPSM:") == std::string::npos) { fprintf(stderr, "Do not see the FPSM: in %s\n", fn); exit(2); }
   memset(m->fpsm, 0, sizeof m->fpsm);
@@ -202,8 +210,9 @@ inline void read_maln_file(const char* fn, MalnFile* m) {
     MalnRecord a;
     std::string seq, smp;
     c.line(&line); field(line, "ID", &a.id);
-    c.line(&line);                                  // DESC
-    c.line(&line);                                  // SCORE
+    c.line(&line);                                  // DESC: what follows "DESC ", without the newline
+    if (line.size() > 5) a.desc.assign(line, 5, line.size() - 6);
+    c.line(&line); field_int(line, "SCORE", &a.score);
     c.line(&line);                                  // NUM_INPUTS, if there (else 1)
     if (field_int(line, "NUM_INPUTS", &a.num_inputs)) c.line(&line);
     field_int(line, "START", &a.start);
@@ -211,7 +220,7 @@ inline void read_maln_file(const char* fn, MalnFile* m) {
     c.line(&line); field_int(line, "RC", &a.rc);
     c.line(&line); field_int(line, "TR", &a.trimmed);
     c.line(&line);                                  // DR, if there
-    if (field_int(line, "DR", &tmp)) c.line(&line);
+    if (field_int(line, "DR", &tmp)) { a.dropped = tmp; c.line(&line); }
     if (field(line, "SEG", &tok)) a.segment = tok[0];
     c.line(&line); field(line, "SEQ", &seq);
     c.line(&line); field(line, "SMP", &smp);
@@ -222,6 +231,8 @@ inline void read_maln_file(const char* fn, MalnFile* m) {
     }
     a.seq.assign(seq, 0, (size_t)ncols);
     a.smp.assign(smp, 0, (size_t)ncols);
+    a.seq_raw = std::move(seq);
+    a.smp_raw = std::move(smp);
     c.literal("INS_POS");
     for (;;) {
       const char* save = c.p;
@@ -235,6 +246,66 @@ inline void read_maln_file(const char* fn, MalnFile* m) {
   }
   sort_records(m);
   flatten_records(m);
+}
+
+// ---- ma -m (write_ma, src/map_alignment.c:283-382) ---------------------------------------------------------------------------
+// Everything from the MALN_NAS line on, the records in the order of `rec` (sorted: ma sorts before it writes).  cons_code is
+// ma's -c (src/map_assembler.c:191), not the file's MALN_COC.  A record's INS_POS pairs are written by ascending position, of
+// several pairs of one position the last, and only positions inside its SEQ string: write_ma walks ins[0 .. strlen(seq)).
+inline void maln_body_text(const MalnFile& m, int cons_code, std::string* out) {
+  char num[64];
+  auto put_int = [&](const char* key, long v) { snprintf(num, sizeof num, "%s%ld\n", key, v); *out += num; };
+  put_int("MALN_NAS ", (long)m.rec.size());
+  put_int("MALN_SIZ ", m.maln_siz);
+  put_int("MALN_COC ", cons_code);
+  *out += "__REFERENCE__\nID " + m.ref_id + "\nDESC " + m.ref_desc + "\n";
+  put_int("LEN ", m.L);
+  put_int("SIZE ", m.ref_size);
+  *out += "SEQ " + m.ref_seq + "\nGAPS";
+  for (int p = 0; p < m.L; p++) { snprintf(num, sizeof num, " %d", m.gaps[(size_t)p]); *out += num; }
+  *out += "\n__PSSM__\n";
+  put_int("DEPTH ", m.depth);
+  for (int s = 0; s < 2; s++) {
+    const int32_t (*sm)[5][5] = s ? m.rpsm : m.fpsm;
+    *out += s ? "RPSM:\n" : "FPSM:\n";
+    for (int i = 0; i <= m.depth * 2 && i < 31; i++) {
+      for (int row = 0; row <= 4; row++) {
+        snprintf(num, sizeof num, "%d %d %d %d %d\n", sm[i][row][0], sm[i][row][1], sm[i][row][2], sm[i][row][3], sm[i][row][4]);
+        *out += num;
+      }
+      *out += "\n";
+    }
+  }
+  *out += "__ALNSEQS__\n";
+  for (const MalnRecord& a : m.rec) {
+    *out += "ID " + a.id + "\nDESC " + a.desc + "\n";
+    put_int("SCORE ", a.score);
+    put_int("NUM_INPUTS ", a.num_inputs);
+    put_int("START ", a.start);
+    put_int("END ", a.end);
+    put_int("RC ", a.rc ? 1 : 0);
+    put_int("TR ", a.trimmed ? 1 : 0);
+    put_int("DR ", a.dropped ? 1 : 0);
+    *out += "SEG ";
+    *out += a.segment;
+    *out += "\nSEQ " + a.seq_raw + "\nSMP " + a.smp_raw + "\nINS_POS";
+    std::map<int32_t, size_t> last;                 // position -> the last pair given for it
+    for (size_t k = 0; k < a.ins_pos.size(); k++)
+      if (a.ins_pos[k] >= 0 && (size_t)a.ins_pos[k] < a.seq_raw.size()) last[a.ins_pos[k]] = k;
+    for (const auto& e : last) { snprintf(num, sizeof num, " %d ", e.first); *out += num; *out += a.ins_seq[e.second]; }
+    *out += "\n";
+  }
+}
+
+inline bool write_maln_file(const char* fn, const MalnFile& m, int cons_code) {
+  FILE* f = fopen(fn, "w");
+  if (!f) { fprintf(stderr, "%s\n", fn); perror("Cannot open file"); return false; }
+  time_t t = time(NULL);
+  std::string text = "/* map_alignment [V1.0] */ ";
+  text += asctime(localtime(&t));
+  maln_body_text(m, cons_code, &text);
+  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+  return (fclose(f) == 0) && ok;
 }
 
 // ---- ma -R (parse_region, src/map_assembler.c:73-82) and print_region's clamp (src/map_align.c:561-567) --------------------
