@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/mia_hip.h"
+#include "dev_buf.h"
 #include "mia_comm.h"
 #include "mia_consensus_kernels.h"
 #include "mia_kernels.h"
@@ -67,11 +68,11 @@ struct mia_hip_ctx {
   int device = 0;
   int cus = 1;
   std::string err;
-  struct PoolBlock { void* p; size_t cap; bool lent; };
+  struct PoolBlock { DevBuf<unsigned char> buf; bool lent; };
   std::vector<PoolBlock> pool;             // device temporaries of the one-off calls (pool_alloc)
   // pinned staging: small copies to and from pageable memory wait for the stream, pinned ones do not
   unsigned char* h_pin = nullptr; static constexpr size_t PIN_BYTES = 1 << 20, PIN_MISC = 64 << 10;
-  int32_t* d_ctrl = nullptr;               // the control block (CTRL_*)
+  DevBuf<int32_t> d_ctrl;                  // the control block (CTRL_*)
   uint32_t dbg = 0;                        // timing experiments only, results are wrong when set (read_alt_switches)
 
   // ---- streams and events ------------------------------------------------------------------------------------------------
@@ -89,111 +90,115 @@ struct mia_hip_ctx {
 
   // ---- reads (and the matrices they are scored with), reference --------------------------------------------------------------
   // PSSMs (fwd, rc)
-  int32_t* d_pssm = nullptr;
+  DevBuf<int32_t> d_pssm;
   int max_abs = 0;
   int max_pos = 0;   // largest positive PSSM entry: bounds any score by rows * max_pos
   bool have_pssm = false;
   bool flat = false;
   PackSet packs;
   ReadSet rs{};
-  uint8_t* d_packed = nullptr; uint32_t* d_roff = nullptr; uint16_t* d_len = nullptr;
-  uint8_t* d_rc = nullptr; uint8_t* d_sk = nullptr;
-  int32_t *d_as = nullptr, *d_ae = nullptr, *d_score = nullptr, *d_refstart = nullptr;
-  int16_t* d_abr = nullptr; uint32_t* d_status = nullptr; int16_t* d_cols = nullptr;
+  DevBuf<uint8_t> d_packed; DevBuf<uint32_t> d_roff; DevBuf<uint16_t> d_len;
+  DevBuf<uint8_t> d_rc, d_sk;
+  DevBuf<int32_t> d_as, d_ae, d_score, d_refstart;
+  DevBuf<int16_t> d_abr; DevBuf<uint32_t> d_status; DevBuf<int16_t> d_cols;
   int max_len = 0;
   int min_len = 0;                          // shortest stored read
   std::vector<int32_t> h_len;               // read lengths on the host (the score-cut regression of reads of different lengths)
-  uint64_t* d_rplanes = nullptr; int rplane_words = 0;   // bit planes of the stored reads (k_read_planes)
-  int32_t* d_umax = nullptr; bool umax_valid = false;
+  DevBuf<uint64_t> d_rplanes; int rplane_words = 0;   // bit planes of the stored reads (k_read_planes)
+  DevBuf<int32_t> d_umax; bool umax_valid = false;
   // reference
-  uint8_t* d_ref = nullptr; int ref_cap = 0; int L = 0, wrap = 0; int explicit_win = 0; bool have_ref = false; bool aligned = false;
+  DevBuf<uint8_t> d_ref; int L = 0, wrap = 0; int explicit_win = 0; bool have_ref = false; bool aligned = false;
   bool ref_mostly_bases = true;            // fewer than 2 % of the reference columns are N
   bool ref_few_n = true;                   // ... fewer than 0.2 %: four windows in five hold none (the quick plan asks those even where the table spells out N columns)
   int64_t kh_entries = 0;                  // > 0: the reference has N columns and its 10-mer table lists them (bandx_body.h, N COLUMNS)
 
   // ---- plan and full-window kernels ----------------------------------------------------------------------------------------
-  int32_t *d_bin_of = nullptr, *d_list = nullptr, *d_wide_list = nullptr, *d_retry_list = nullptr;
+  DevBuf<int32_t> d_bin_of, d_list, d_wide_list, d_retry_list;
   int32_t* d_bins = nullptr;  // [count N_BINS][off N_BINS][cursor N_BINS][wide_count 1]
   int32_t* d_plan_hdr = nullptr;            // PH_* (k_plan_scan)
   bool deferred = false;                    // align_all: no host round trip before its end
   // trace slabs of the persistent DP grid (one per workgroup, per CPL class)
-  unsigned char* d_slabs[N_CPL] = {nullptr, nullptr, nullptr};
-  unsigned char* d_slabs_retry[3] = {nullptr, nullptr, nullptr};      // trace slabs of the band kernels' retry launch (see launch_window)
-  unsigned char* d_quad_slabs = nullptr;
+  DevBuf<unsigned char> d_slabs[N_CPL];
+  DevBuf<unsigned char> d_slabs_retry[3];                             // trace slabs of the band kernels' retry launch (see launch_window)
+  DevBuf<unsigned char> d_quad_slabs;
   int quad_wgs = 0;
   int grid_wgs = 0;
   int window_wgs[N_CPL] = {0, 0, 0};
   int64_t plain_retried = 0, plain_total = 0;
   bool wide_to_caller = false;             // run_wide marks its reads ST_ESCAPE instead of aligning them (the anchored pass 1)
   // wide scratch
-  int32_t* d_scratch = nullptr; int64_t scratch_cap = 0; int64_t* d_scratch_off = nullptr; int64_t scratch_off_cap = 0;
+  DevBuf<int32_t> d_scratch; DevBuf<int64_t> d_scratch_off;
   // round 6: the band plan lists the reads it leaves open itself and k_align_open takes them one per wavefront (align_route.h: direct_open):
   // the plan's own open list (n entries), k_align_open's trace slabs (one per workgroup of its grid)
-  int32_t* d_open_list = nullptr; int64_t open_cap = 0; unsigned char* d_slabs_open = nullptr; bool use_direct_open = true; int64_t direct_open_steps = 0;
+  DevBuf<int32_t> d_open_list; DevBuf<unsigned char> d_slabs_open; bool use_direct_open = true; int64_t direct_open_steps = 0;
 
   // ---- band pipeline, round 1: the diagonal filter (diag_filter.h) and its banded DP (band_body.h), flat matrix only -----------
   int use_filter = 1;
-  int32_t *d_kocc_cnt = nullptr, *d_kocc_pos = nullptr;   // 10-mer table of the reference (diag_filter.h: KmerOcc)
-  uint64_t* d_planes = nullptr; int64_t plane_cap = 0;   // lo | hi | ok, plane_cap words each
+  DevBuf<int32_t> d_kocc_cnt, d_kocc_pos;   // 10-mer table of the reference (diag_filter.h: KmerOcc)
+  DevBuf<uint64_t> d_planes;                // lo | hi | ok, a third of the block each (plane_stride)
   uint32_t* d_filter_n = nullptr; int64_t filter_proven = 0, filter_seen = 0;   // device: {finished by the filter, left over, finished by the banded DP}
   int use_banddp = 1;
-  int32_t* d_left_list = nullptr; int64_t left_cap = 0;
-  uint32_t* d_band_slabs = nullptr; int64_t band_slab_cap = 0;
+  DevBuf<int32_t> d_left_list;
+  DevBuf<uint32_t> d_band_slabs;
   int64_t band_done = 0;
 
   // ---- band pipeline for any PSSM (bandx_kernels.h): plan -> values-only DP -> trace DP ------------------------------------------
   bool bx_ok = false;                       // the matrices allow it (bx_make_tables)
   int use_bx = 1, use_lanes = 1; bool bx_serial = false; uint32_t bx_dbg = 0;
-  int32_t *d_bx_sub = nullptr, *d_bx_mrow = nullptr; int16_t *d_bx_loss = nullptr, *d_bx_dl = nullptr;   // sub | sub * 256; M; losses; block costs
+  DevBuf<int32_t> d_bx_sub, d_bx_mrow; DevBuf<int16_t> d_bx_loss, d_bx_dl;   // sub | sub * 256; M; losses; block costs
   int32_t bx_min_m = 0, bx_max_m = 0;
-  uint32_t* d_refnib = nullptr; int64_t refnib_cap = 0;
-  uint32_t* d_khash = nullptr; int32_t* d_khash_ovf = nullptr; uint32_t khash_cap = 0;   // 10-mers of the reference (bandx_body.h: KmerHash)
-  KbPair* d_kbits = nullptr;            // the quick plan's bitmaps over all 4^10 10-mers (bandx_body.h: KmerBits), remade with the table
+  DevBuf<uint32_t> d_refnib;
+  DevBuf<uint32_t> d_khash; DevBuf<int32_t> d_khash_ovf;   // 10-mers of the reference (bandx_body.h: KmerHash)
+  DevBuf<KbPair> d_kbits;               // the quick plan's bitmaps over all 4^10 10-mers (bandx_body.h: KmerBits), remade with the table
   int use_quick = 1; int64_t quick_steps = 0;      // the quick plan in front of k_bx_plan's launches
-  uint32_t* d_prep_bar = nullptr; uint32_t prep_bar_count = 0; bool no_prep_fuse = false;   // k_ref_prep's grid barrier
-  uint32_t* d_bx_plan = nullptr; int32_t* d_bx_expect = nullptr; int32_t* d_bx_lists = nullptr; int64_t bx_cap = 0;
-  BxCandRec* d_bx_cand = nullptr; int64_t cand_cap = 0, cand2_cap = 0; bool plan_split = true;      // k_bx_plan's hand-over list between its two launches
-  BxCandRec* d_bx_cand2 = nullptr; int use_fine = 1;      // the third launch's list (reads for the fine blocks)
+  DevBuf<uint32_t> d_prep_bar; uint32_t prep_bar_count = 0; bool no_prep_fuse = false;   // k_ref_prep's grid barrier
+  DevBuf<uint32_t> d_bx_plan; DevBuf<int32_t> d_bx_expect, d_bx_lists;
+  DevBuf<BxCandRec> d_bx_cand; bool plan_split = true;      // k_bx_plan's hand-over list between its two launches
+  DevBuf<BxCandRec> d_bx_cand2; int use_fine = 1;      // the third launch's list (reads for the fine blocks)
   uint32_t* d_bx_ctr = nullptr;
-  uint32_t* d_bx_slabs = nullptr; int64_t bx_slab_cap = 0;
+  DevBuf<uint32_t> d_bx_slabs;
   int bx_values_wgs = 0, bx_trace_wgs = 0;
-  uint32_t* d_bx_slabs_late = nullptr; int64_t bx_slab_late_cap = 0; int bx_late_wgs = 0;
-  uint32_t* d_bx_slabs_late2 = nullptr;      // the second late trace's slabs (align_route.h: fork_at_quick)
-  int32_t* d_retry2 = nullptr; int64_t retry2_cap = 0;                              // reads no band kernel could finish
+  DevBuf<uint32_t> d_bx_slabs_late; int bx_late_wgs = 0;
+  DevBuf<uint32_t> d_bx_slabs_late2;         // the second late trace's slabs (align_route.h: fork_at_quick)
+  DevBuf<int32_t> d_retry2;                                                         // reads no band kernel could finish
   bool diag_scripts_missing = false;       // the last alignment left the scripts of its ST_DIAG reads unwritten (k_diag_scripts)
   int64_t bx_seen = 0, bx_done[3] = {0, 0, 0};   // reads planned on; finished by the plan / the values DP / the trace DP
   int64_t bx_launches = 0;
   uint32_t bx_last[BXC_COUNTERS] = {0};     // counters of the last call (list lengths, reasons a read was not planned)
 
   // ---- cull ----------------------------------------------------------------------------------------------------------------
-  int64_t* d_slot = nullptr; int64_t* d_partial = nullptr; int64_t* d_total = nullptr;
-  uint8_t *d_slot_dropped = nullptr, *d_drop_f = nullptr, *d_drop_b = nullptr; int64_t n_slots = 0;
+  DevBuf<int64_t> d_slot, d_partial, d_total;
+  DevBuf<uint8_t> d_slot_dropped, d_drop_f, d_drop_b; int64_t n_slots = 0;
   // stale back_asp emulation (mia_consensus_kernels.h, k_cull_mark)
-  int64_t* d_back_slot = nullptr;          // per read, persistent across iterations
-  int64_t* d_front_slot0 = nullptr;        // per read: pass-1 front slot (followed for strand-unknown reads only)
-  int32_t* d_link_act = nullptr;
+  DevBuf<int64_t> d_back_slot;             // per read, persistent across iterations
+  DevBuf<int64_t> d_front_slot0;           // per read: pass-1 front slot (followed for strand-unknown reads only)
+  DevBuf<int32_t> d_link_act;
+  // the kernels take ri, si, lk and tb by value: views, set beside their owners' allocation (mia_hip_upload_reads, ensure_tally, ensure_events)
   RecInfo ri{};                            // per read, per iteration
+  DevBuf<int32_t> d_ri_flen, d_ri_blen, d_ri_actf, d_ri_trec;
   SlotInfo si{};                           // per local slot, per iteration
-  int64_t slot_cap = 0;
+  DevBuf<int32_t> d_si_reclen, d_si_recact, d_si_mult; DevBuf<unsigned long long> d_si_writer;
   Links lk{};                              // links produced by this context in the last cull
-  int64_t* d_links_all = nullptr; int32_t n_links_all = 0; int64_t links_all_cap = 0;   // links to apply (own, or gathered from all ranks)
-  int32_t* d_n_links_all = nullptr; int64_t links_cap_all = 0; int32_t* d_n_links_gathered = nullptr;
-  int32_t* d_link_len = nullptr; int64_t link_len_cap = 0;
+  DevBuf<int64_t> d_lk_rec;
+  int64_t* d_links_all = nullptr; int32_t n_links_all = 0;   // links to apply (own, or gathered from all ranks): lk.rec or owned_links.back()
+  int32_t* d_n_links_all = nullptr; int64_t links_cap_all = 0; DevBuf<int32_t> d_n_links_gathered;
+  DevBuf<int32_t> d_link_len;
   uint32_t* d_cull_flags = nullptr;
-  uint32_t* d_cull_sync = nullptr;          // k_slot_count's arrival counter (zero between launches)
-  unsigned long long* d_sums = nullptr;
+  DevBuf<uint32_t> d_cull_sync;             // k_slot_count's arrival counter (zero between launches)
+  DevBuf<unsigned long long> d_sums;
   int64_t read_base = 0;                   // global index of this context's first read (sharded runs)
   int64_t slot_base = 0;
   bool culled = false, links_applied = false;
-  std::vector<int64_t*> owned_links;       // gathered link buffers (mia_hip_set_links)
+  std::vector<DevBuf<int64_t>> owned_links;   // gathered link buffers (mia_hip_set_links)
   bool cull_scan = false, tail_scans = false;
   bool cull_with_records = true;           // k_cull_records writes the tally records of an iteration without links itself
   int64_t pre_cull_records = 0, pre_cull_links = 0; bool pre_cull_valid = false;   // mia_hip_score_sums' by-products
 
   // ---- tally and consensus -------------------------------------------------------------------------------------------------
-  TallyBuf tb{}; int tally_cap = 0; int32_t* d_ins_off = nullptr; int32_t* d_ins_total = nullptr;
-  int32_t* d_ins_tally = nullptr; int64_t ins_tally_cap = 0; char* d_calls = nullptr; char* d_ins_calls = nullptr;
-  int64_t ins_calls_cap = 0; int32_t n_events_host = 0; bool tallied = false;
+  TallyBuf tb{}; DevBuf<int32_t> d_tb_tally, d_ins_off, d_ins_total; DevBuf<uint64_t> d_tb_events;
+  DevBuf<int32_t> d_ins_tally; DevBuf<char> d_calls, d_ins_calls;
+  int64_t ins_tally_cap = 0;               // insert slots d_ins_tally and d_ins_calls both hold: a kernel argument (like tb.cap_events), set with them in mia_hip_consensus
+  int32_t n_events_host = 0; bool tallied = false;
   int64_t ins_total_host = 0;
   bool consensus_done = false;
   bool fake_event_overflow = false;
@@ -202,12 +207,12 @@ struct mia_hip_ctx {
   int tally_pk_bias = -1;                   // the tally's packed end-base sums (k_tally_binned): the bias that makes every score positive, or -1: entries too large
   // read bucketing for the LDS-privatised tally
   int use_binned_tally = 1;
-  int32_t* d_bucket = nullptr; int bucket_cap = 0; int32_t* d_order = nullptr;
+  DevBuf<int32_t> d_bucket, d_order;
   int bucket_clean_nb = -1;                 // the tally's bucket counts are zero for this bucket count (k_bucket_scan leaves them so)
   int buckets_queued = 0;                   // the tally's counting sort is already queued: 1 on the context's stream, 2 on stream2 (ev_join behind it)
   bool no_side_buckets = false;
-  int32_t* d_tally_slabs = nullptr; int64_t tally_slab_cap = 0;   // one LDS window per tally workgroup, summed by k_tally_reduce
-  int32_t* d_gen_list = nullptr; int64_t gen_cap = 0;             // the reads k_tally_binned leaves to k_tally_reduce's extra workgroups (a thousand in a million; room for all)
+  DevBuf<int32_t> d_tally_slabs;   // one LDS window per tally workgroup, summed by k_tally_reduce
+  DevBuf<int32_t> d_gen_list;             // the reads k_tally_binned leaves to k_tally_reduce's extra workgroups (a thousand in a million; room for all)
   bool tally_defer = true;                 // ... false: they are taken inside k_tally_binned, one per wavefront
   // position-specific matrices: a workgroup's reads all of one strand, sorted by start (round 5).  Measured against round 4's tally:
   // configs[2] 1.313 -> 1.306 ms, configs[4] at 5 M reads 9.91 -> 10.2 ms (twice the part-filled workgroups and slabs; the end rows'
@@ -215,7 +220,7 @@ struct mia_hip_ctx {
   bool tally_strand_split = true;
   bool tally_rall = true;                  // reads of 129 .. 256 bases: every row through the runs
   bool tally_runs = true;                  // ... and the rows at either end of a read reduced over runs of equal starts
-  int32_t* d_order2 = nullptr; uint8_t* d_okey = nullptr; int32_t* d_sort2 = nullptr; int64_t sort2_cap = 0;      // the reads of every bucket by start; histogram + cursors of that sort
+  DevBuf<int32_t> d_order2; DevBuf<uint8_t> d_okey; DevBuf<int32_t> d_sort2;      // the reads of every bucket by start; histogram + cursors of that sort
 
   // ---- iterate: one iteration with the planner's answers, the cut line and the insert-event count left on the device ------------
   bool in_iterate = false;                  // the control block was cleared as a whole by the alignment's one memset
@@ -226,13 +231,13 @@ struct mia_hip_ctx {
   bool spec_ok = false, spec_pending = false, spec_filtered = false, spec_bx = false, spec_plain = false;
   int64_t spec_redone = 0;                  // iterations whose cull / tally / consensus were queued twice (reads for the exact kernel)
   bool no_spec = false;
-  bool spec_force = false; int32_t* d_one = nullptr;      // (tests) every iteration takes the second round; a word that holds 1
+  bool spec_force = false; DevBuf<int32_t> d_one;      // (tests) every iteration takes the second round; a word that holds 1
   bool pend_encode = false; int32_t pend_L = 0, pend_wl = 0, pend_total = 0;      // d_ascii holds the new reference, d_ref not yet
   bool zero_copy = true;                   // the last kernel writes consensus and counters into pinned host memory itself
-  const double* dev_cut = nullptr; double* d_cut_buf = nullptr;
-  char* d_ascii = nullptr; int64_t ascii_cap = 0; const char* ascii_src = nullptr;     // ascii_src: where the pending reference is read from (d_ascii, or the pinned staging area)
-  char* d_cons = nullptr; int64_t cons_cap = 0;              // result of an iteration: [CH_WORDS header][consensus string]
-  int32_t* d_cons_pos = nullptr; int64_t cons_pos_cap = 0;
+  const double* dev_cut = nullptr; DevBuf<double> d_cut_buf;
+  DevBuf<char> d_ascii; const char* ascii_src = nullptr;     // ascii_src: where the pending reference is read from (d_ascii, or the pinned staging area)
+  DevBuf<char> d_cons;                                       // result of an iteration: [CH_WORDS header][consensus string]
+  DevBuf<int32_t> d_cons_pos;
   unsigned char* h_pin2 = nullptr; size_t pin2_bytes = 0;   // results of an iteration (header + consensus string)
   int64_t iter_fallbacks = 0;
 
@@ -243,26 +248,24 @@ struct mia_hip_ctx {
   // the records of the last mia_hip_ma_tally stay on the device for mia_hip_ma_region: start, col_off, seq, the INS_POS pairs (and
   // which pairs each record owns), ref->gaps; the region's column map, selected records and text
   bool ma_resident = false; int64_t ma_n = 0; int32_t ma_L = 0;
-  int32_t *d_ma_start = nullptr, *d_ma_gaps = nullptr, *d_ma_ipos = nullptr, *d_ma_rec_ins = nullptr, *d_ma_ins_list = nullptr;
-  int64_t *d_ma_coff = nullptr, *d_ma_ioff = nullptr, *d_ma_colmap = nullptr, *d_ma_rows = nullptr;
-  char *d_ma_seq = nullptr, *d_ma_ib = nullptr, *d_ma_text = nullptr; int64_t ma_text_cap = 0;
-  unsigned long long* d_ma_ctl = nullptr;
+  DevBuf<int32_t> d_ma_start, d_ma_gaps, d_ma_ipos, d_ma_rec_ins, d_ma_ins_list;
+  DevBuf<int64_t> d_ma_coff, d_ma_ioff, d_ma_colmap, d_ma_rows;
+  DevBuf<char> d_ma_seq, d_ma_ib, d_ma_text;
+  DevBuf<unsigned long long> d_ma_ctl;
   int32_t ma_first = 0, ma_last = -1; int64_t ma_rows = 0, ma_width = 0; bool ma_region_done = false;
   // ... and for mia_hip_ma_ace: whether the job has an ACE export at all (GAPS, the records' columns), the running sum of ref->gaps,
   // per record the AF position, the padded length and the offset of its text, the text
-  bool ma_ace_gaps_ok = false, ma_ace_cols_ok = false, ma_ace_done = false; int64_t ma_ace_bytes = 0, ma_ace_cap = 0, ma_ace_rec_cap = 0, ma_ace_g_cap = 0;
-  int64_t *d_ace_g = nullptr, *d_ace_af = nullptr, *d_ace_len = nullptr, *d_ace_off = nullptr; char* d_ace_body = nullptr;
+  bool ma_ace_gaps_ok = false, ma_ace_cols_ok = false, ma_ace_done = false; int64_t ma_ace_bytes = 0;
+  DevBuf<int64_t> d_ace_g, d_ace_af, d_ace_len, d_ace_off; DevBuf<char> d_ace_body;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------
   mia_hip_collectives coll{}; bool comm = false; int comm_ranks = 1, comm_rank = 0; std::string coll_name;
-  unsigned long long* d_gather = nullptr;   // [PRE_WORDS * ranks] score sums, record, link and exact-kernel counts of every rank
+  DevBuf<unsigned long long> d_gather;      // [PRE_WORDS * ranks] score sums, record, link and exact-kernel counts of every rank
   std::vector<int64_t> h_gather;            // ... on the host, once the alignment's one wait is over
   int64_t ev_pad = 0;                       // insert events per rank the event all-gather is sized for (0: not known yet)
-  int64_t* d_lstage = nullptr; int64_t lstage_cap = 0;       // links / insert events of all ranks, padded to the longest
-  int64_t* d_lmine = nullptr; int64_t lmine_cap = 0;
-  int64_t* d_lall = nullptr; int64_t lall_cap = 0;
-  int32_t* d_scores_all = nullptr; int64_t scores_all_cap = 0;
+  DevBuf<int64_t> d_lstage, d_lmine, d_lall;                 // links / insert events of all ranks, padded to the longest
+  DevBuf<int32_t> d_scores_all;
 };
 
 // The alternative routes and diagnostics of libmia_hip_alt.so (alt_env reads nothing in the release build), one line each.  What the
@@ -319,46 +322,42 @@ static void read_alt_switches(mia_hip_ctx* ctx) {
     }                                                                                                  \
   } while (0)
 
-// frees the watched temporaries when the scope is left, whichever way (every early return of a long entry point)
-struct ScopeFree {
-  std::vector<void**> w;
-  void watch(void** pp) { w.push_back(pp); }
-  ~ScopeFree() { for (void** pp : w) if (*pp) { (void)hipFree(*pp); *pp = nullptr; } }
-};
-
-template <class T>
-static int dev_alloc(mia_hip_ctx* ctx, T** p, size_t n) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (n == 0) n = 1;
-  hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-  if (e != hipSuccess) { ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); *p = nullptr; return MIA_HIP_ERR_NOMEM; }
-  return MIA_HIP_OK;
+// what a DevBuf's alloc / ensure answered, as the ABI's code (and the context's message)
+static int dev_nomem(mia_hip_ctx* ctx, hipError_t e) {
+  if (e == hipSuccess) return MIA_HIP_OK;
+  ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
+  return MIA_HIP_ERR_NOMEM;
 }
+template <class T>
+static int dev_alloc(mia_hip_ctx* ctx, DevBuf<T>& b, int64_t n) { return dev_nomem(ctx, b.alloc(n)); }
+template <class T>
+static int dev_ensure(mia_hip_ctx* ctx, DevBuf<T>& b, int64_t need, int64_t alloc_elems) { return dev_nomem(ctx, b.ensure(need, alloc_elems)); }
+template <class T>
+static int dev_ensure(mia_hip_ctx* ctx, DevBuf<T>& b, int64_t need) { return dev_nomem(ctx, b.ensure(need, need)); }
 
 // Temporaries of the one-off calls (pass 1, adapter trimming) come from blocks the context keeps: hipMalloc/hipFree of
 // twenty-odd buffers per call cost more than the kernels between them.  A block is lent for the length of a scope.
 template <class T>
 static int pool_alloc(mia_hip_ctx* ctx, T** p, size_t n) {
-  size_t bytes = (n ? n : 1) * sizeof(T);
+  const int64_t bytes = (int64_t)((n ? n : 1) * sizeof(T));
   int best = -1;
   for (size_t k = 0; k < ctx->pool.size(); k++) {
     auto& b = ctx->pool[k];
-    if (!b.lent && b.cap >= bytes && (best < 0 || b.cap < ctx->pool[best].cap)) best = (int)k;
+    if (!b.lent && b.buf.cap >= bytes && (best < 0 || b.buf.cap < ctx->pool[best].buf.cap)) best = (int)k;
   }
   if (best < 0) {
     // grow the largest idle block rather than keep one that nothing fits any more
     int idle = -1;
     for (size_t k = 0; k < ctx->pool.size(); k++)
-      if (!ctx->pool[k].lent && (idle < 0 || ctx->pool[k].cap > ctx->pool[idle].cap)) idle = (int)k;
-    if (idle >= 0) { (void)hipFree(ctx->pool[idle].p); ctx->pool.erase(ctx->pool.begin() + idle); }
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) { ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e); *p = nullptr; return MIA_HIP_ERR_NOMEM; }
-    ctx->pool.push_back({q, bytes, false});
+      if (!ctx->pool[k].lent && (idle < 0 || ctx->pool[k].buf.cap > ctx->pool[idle].buf.cap)) idle = (int)k;
+    if (idle >= 0) ctx->pool.erase(ctx->pool.begin() + idle);
+    DevBuf<unsigned char> q;
+    if (dev_alloc(ctx, q, bytes)) { *p = nullptr; return MIA_HIP_ERR_NOMEM; }
+    ctx->pool.push_back({std::move(q), false});
     best = (int)ctx->pool.size() - 1;
   }
   ctx->pool[best].lent = true;
-  *p = (T*)ctx->pool[best].p;
+  *p = (T*)ctx->pool[best].buf.p;
   return MIA_HIP_OK;
 }
 struct PoolScope {
@@ -369,15 +368,11 @@ struct PoolScope {
   ~PoolScope() {
     for (void** pp : w) {
       if (!*pp) continue;
-      for (auto& b : c->pool) if (b.p == *pp) b.lent = false;
+      for (auto& b : c->pool) if (b.buf.p == *pp) b.lent = false;
       *pp = nullptr;
     }
   }
 };
-static void pool_drop(mia_hip_ctx* ctx) {
-  for (auto& b : ctx->pool) (void)hipFree(b.p);
-  ctx->pool.clear();
-}
 
 extern "C" const char* mia_hip_last_error(const mia_hip_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
@@ -407,11 +402,11 @@ extern "C" int mia_hip_create(mia_hip_ctx** out, int device_index) {
     read_alt_switches(ctx);
     if (const char* sw = getenv("MIA_HIP_SPIN_WAIT")) ctx->spin_wait = atoi(sw) != 0;
   }
-  if (dev_alloc(ctx, &ctx->d_pssm, 2 * PSSM_WORDS) || dev_alloc(ctx, &ctx->d_ctrl, CTRL_WORDS) ||
-      dev_alloc(ctx, &ctx->d_total, 1) || dev_alloc(ctx, &ctx->d_ins_total, 1) ||
-      dev_alloc(ctx, &ctx->d_bx_sub, 2 * BX_SUB_WORDS) || dev_alloc(ctx, &ctx->d_bx_mrow, 2 * 31 * 4) || dev_alloc(ctx, &ctx->d_bx_loss, BX_LOSS_WORDS) ||
-      dev_alloc(ctx, &ctx->d_bx_dl, BX_DL_WORDS) ||
-      dev_alloc(ctx, &ctx->d_cut_buf, 2)) {
+  if (dev_alloc(ctx, ctx->d_pssm, 2 * PSSM_WORDS) || dev_alloc(ctx, ctx->d_ctrl, CTRL_WORDS) ||
+      dev_alloc(ctx, ctx->d_total, 1) || dev_alloc(ctx, ctx->d_ins_total, 1) ||
+      dev_alloc(ctx, ctx->d_bx_sub, 2 * BX_SUB_WORDS) || dev_alloc(ctx, ctx->d_bx_mrow, 2 * 31 * 4) || dev_alloc(ctx, ctx->d_bx_loss, BX_LOSS_WORDS) ||
+      dev_alloc(ctx, ctx->d_bx_dl, BX_DL_WORDS) ||
+      dev_alloc(ctx, ctx->d_cut_buf, 2)) {
     delete ctx;
     return MIA_HIP_ERR_NOMEM;
   }
@@ -426,8 +421,8 @@ extern "C" int mia_hip_create(mia_hip_ctx** out, int device_index) {
   if (hipMemset(ctx->d_ctrl, 0, CTRL_WORDS * 4) != hipSuccess) { delete ctx; return MIA_HIP_ERR_DEVICE; }
   {
     const int32_t one = 1;
-    if (hipMalloc((void**)&ctx->d_one, 4) != hipSuccess || hipMemcpy(ctx->d_one, &one, 4, hipMemcpyHostToDevice) != hipSuccess) { delete ctx; return MIA_HIP_ERR_DEVICE; }
-    if (hipMalloc((void**)&ctx->d_prep_bar, 4) != hipSuccess || hipMemset(ctx->d_prep_bar, 0, 4) != hipSuccess) { delete ctx; return MIA_HIP_ERR_DEVICE; }
+    if (dev_alloc(ctx, ctx->d_one, 1) || hipMemcpy(ctx->d_one, &one, 4, hipMemcpyHostToDevice) != hipSuccess) { delete ctx; return MIA_HIP_ERR_DEVICE; }
+    if (dev_alloc(ctx, ctx->d_prep_bar, 1) || hipMemset(ctx->d_prep_bar, 0, 4) != hipSuccess) { delete ctx; return MIA_HIP_ERR_DEVICE; }
   }
   if (hipHostMalloc((void**)&ctx->h_pin, mia_hip_ctx::PIN_BYTES, hipHostMallocDefault) != hipSuccess) ctx->h_pin = nullptr;   // optional
   if (ctx->h_pin) memset(ctx->h_pin, 0, mia_hip_ctx::PIN_MISC);
@@ -442,18 +437,6 @@ extern "C" void mia_hip_destroy(mia_hip_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
   (void)mia_hip_comm_destroy(ctx);
-  void* ptrs[] = {ctx->d_ctrl, ctx->d_pssm, ctx->d_packed, ctx->d_roff, ctx->d_len, ctx->d_rc, ctx->d_sk, ctx->d_as, ctx->d_ae, ctx->d_score,
-                  ctx->d_refstart, ctx->d_abr, ctx->d_status, ctx->d_cols, ctx->d_bin_of, ctx->d_list, ctx->d_wide_list, ctx->d_retry_list,
-                  ctx->d_ref, ctx->d_slot, ctx->d_partial, ctx->d_total, ctx->d_slot_dropped, ctx->d_drop_f,
-                  ctx->d_drop_b, ctx->tb.tally, ctx->tb.events, ctx->d_ins_off,
-                  ctx->d_ins_total, ctx->d_ins_tally, ctx->d_calls, ctx->d_ins_calls, ctx->d_scratch, ctx->d_scratch_off,
-                  ctx->d_slabs[0], ctx->d_slabs[1], ctx->d_slabs[2], ctx->d_quad_slabs, ctx->d_bucket, ctx->d_order, ctx->d_order2, ctx->d_okey, ctx->d_sort2,
-                  ctx->d_back_slot, ctx->ri.flen, ctx->ri.blen, ctx->ri.actf, ctx->ri.trec, ctx->si.reclen, ctx->si.writer, ctx->si.mult,
-                  ctx->lk.rec, ctx->d_link_len, ctx->d_link_act, ctx->d_front_slot0, ctx->si.recact, ctx->d_sums, ctx->d_n_links_gathered, ctx->d_tally_slabs, ctx->d_planes, ctx->d_kocc_cnt, ctx->d_kocc_pos, ctx->d_left_list, ctx->d_band_slabs,
-                  ctx->d_bx_sub, ctx->d_bx_mrow, ctx->d_bx_loss, ctx->d_bx_dl, ctx->d_rplanes, ctx->d_khash, ctx->d_khash_ovf, ctx->d_refnib, ctx->d_umax, ctx->d_bx_plan, ctx->d_bx_expect, ctx->d_bx_lists, ctx->d_bx_slabs, ctx->d_cut_buf, ctx->d_ascii, ctx->d_cons, ctx->d_cons_pos, ctx->d_gather, ctx->d_lstage, ctx->d_lmine, ctx->d_lall, ctx->d_scores_all};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  pool_drop(ctx);
-  for (int64_t* p : ctx->owned_links) if (p) (void)hipFree(p);
   if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
   if (ctx->h_pin2) (void)hipHostFree(ctx->h_pin2);
   for (auto& e : ctx->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -461,27 +444,10 @@ extern "C" void mia_hip_destroy(mia_hip_ctx* ctx) {
   (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
-  if (ctx->d_gen_list) (void)hipFree(ctx->d_gen_list);
   if (ctx->ev_join3) (void)hipEventDestroy(ctx->ev_join3);
-  if (ctx->d_retry2) (void)hipFree(ctx->d_retry2);
-  if (ctx->d_cull_sync) (void)hipFree(ctx->d_cull_sync);
-  if (ctx->d_bx_slabs_late) (void)hipFree(ctx->d_bx_slabs_late);
-  if (ctx->d_bx_slabs_late2) (void)hipFree(ctx->d_bx_slabs_late2);
-  if (ctx->d_one) (void)hipFree(ctx->d_one);
-  if (ctx->d_bx_cand) (void)hipFree(ctx->d_bx_cand);
-  if (ctx->d_bx_cand2) (void)hipFree(ctx->d_bx_cand2);
-  for (int k = 0; k < 3; k++) if (ctx->d_slabs_retry[k]) (void)hipFree(ctx->d_slabs_retry[k]);
-  if (ctx->d_prep_bar) (void)hipFree(ctx->d_prep_bar);
-  if (ctx->d_slabs_open) (void)hipFree(ctx->d_slabs_open);
-  if (ctx->d_open_list) (void)hipFree(ctx->d_open_list);
-  if (ctx->d_kbits) (void)hipFree(ctx->d_kbits);
-  for (void* p : {(void*)ctx->d_ma_start, (void*)ctx->d_ma_gaps, (void*)ctx->d_ma_ipos, (void*)ctx->d_ma_rec_ins, (void*)ctx->d_ma_ins_list, (void*)ctx->d_ma_coff,
-                  (void*)ctx->d_ma_ioff, (void*)ctx->d_ma_colmap, (void*)ctx->d_ma_rows, (void*)ctx->d_ma_seq, (void*)ctx->d_ma_ib, (void*)ctx->d_ma_text, (void*)ctx->d_ma_ctl,
-                  (void*)ctx->d_ace_g, (void*)ctx->d_ace_af, (void*)ctx->d_ace_len, (void*)ctx->d_ace_off, (void*)ctx->d_ace_body})
-    if (p) (void)hipFree(p);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-  delete ctx;
+  delete ctx;                               // its DevBuf members free every device block, the pool's included
 }
 
 extern "C" int mia_hip_sync(mia_hip_ctx* ctx) {
@@ -603,40 +569,43 @@ extern "C" int mia_hip_upload_reads(mia_hip_ctx* ctx, int64_t n, const char* bas
   for (int64_t i = 0; i < n; i++) if ((int)len[(size_t)i] < ctx->min_len) ctx->min_len = len[(size_t)i];
   const int stride = (max_len + 3) & ~3;
   int rcx = 0;
-  rcx |= dev_alloc(ctx, &ctx->d_packed, packed.size());
-  rcx |= dev_alloc(ctx, &ctx->d_roff, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_len, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_rc, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_sk, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_as, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_ae, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_score, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_refstart, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_abr, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_status, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_cols, (size_t)n * stride);
-  rcx |= dev_alloc(ctx, &ctx->d_bin_of, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_umax, (size_t)n);
+  rcx |= dev_alloc(ctx, ctx->d_packed, packed.size());
+  rcx |= dev_alloc(ctx, ctx->d_roff, n);
+  rcx |= dev_alloc(ctx, ctx->d_len, n);
+  rcx |= dev_alloc(ctx, ctx->d_rc, n);
+  rcx |= dev_alloc(ctx, ctx->d_sk, n);
+  rcx |= dev_alloc(ctx, ctx->d_as, n);
+  rcx |= dev_alloc(ctx, ctx->d_ae, n);
+  rcx |= dev_alloc(ctx, ctx->d_score, n);
+  rcx |= dev_alloc(ctx, ctx->d_refstart, n);
+  rcx |= dev_alloc(ctx, ctx->d_abr, n);
+  rcx |= dev_alloc(ctx, ctx->d_status, n);
+  rcx |= dev_alloc(ctx, ctx->d_cols, n * stride);
+  rcx |= dev_alloc(ctx, ctx->d_bin_of, n);
+  rcx |= dev_alloc(ctx, ctx->d_umax, n);
   ctx->rplane_words = (max_len + 63) >> 6;
-  rcx |= dev_alloc(ctx, &ctx->d_rplanes, (size_t)n * 2 * ctx->rplane_words + 2);      // (+ 2: k_tally_binned asks for a second word of every plane)
-  rcx |= dev_alloc(ctx, &ctx->d_list, (size_t)n + 4 * N_BINS);   // quad bins are padded to multiples of four
-  rcx |= dev_alloc(ctx, &ctx->d_wide_list, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_retry_list, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_slot, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_partial, (size_t)(n / 256 + n / 4096 + 8));      // per 256 reads, and behind them per 4 096 (k_slot_count)
-  rcx |= dev_alloc(ctx, &ctx->d_drop_f, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->d_drop_b, (size_t)n);
-  ctx->n_slots = 2 * n + 16;
-  rcx |= dev_alloc(ctx, &ctx->d_slot_dropped, (size_t)ctx->n_slots);
-  rcx |= dev_alloc(ctx, &ctx->d_back_slot, (size_t)n) | dev_alloc(ctx, &ctx->d_front_slot0, (size_t)n);
-  rcx |= dev_alloc(ctx, &ctx->ri.flen, (size_t)n) | dev_alloc(ctx, &ctx->ri.blen, (size_t)n) | dev_alloc(ctx, &ctx->ri.actf, (size_t)n) |
-         dev_alloc(ctx, &ctx->ri.trec, (size_t)n * 16);
-  ctx->slot_cap = 2 * n + 16;
-  rcx |= dev_alloc(ctx, &ctx->si.reclen, (size_t)ctx->slot_cap) | dev_alloc(ctx, &ctx->si.recact, (size_t)ctx->slot_cap) | dev_alloc(ctx, &ctx->si.writer, (size_t)ctx->slot_cap) |
-         dev_alloc(ctx, &ctx->si.mult, (size_t)ctx->slot_cap);
+  rcx |= dev_alloc(ctx, ctx->d_rplanes, n * 2 * ctx->rplane_words + 2);      // (+ 2: k_tally_binned asks for a second word of every plane)
+  rcx |= dev_alloc(ctx, ctx->d_list, n + 4 * N_BINS);   // quad bins are padded to multiples of four
+  rcx |= dev_alloc(ctx, ctx->d_wide_list, n);
+  rcx |= dev_alloc(ctx, ctx->d_retry_list, n);
+  rcx |= dev_alloc(ctx, ctx->d_slot, n);
+  rcx |= dev_alloc(ctx, ctx->d_partial, (size_t)(n / 256 + n / 4096 + 8));      // per 256 reads, and behind them per 4 096 (k_slot_count)
+  rcx |= dev_alloc(ctx, ctx->d_drop_f, n);
+  rcx |= dev_alloc(ctx, ctx->d_drop_b, n);
+  rcx |= dev_alloc(ctx, ctx->d_slot_dropped, 2 * n + 16);
+  ctx->n_slots = ctx->d_slot_dropped.cap;
+  rcx |= dev_alloc(ctx, ctx->d_back_slot, n) | dev_alloc(ctx, ctx->d_front_slot0, n);
+  rcx |= dev_alloc(ctx, ctx->d_ri_flen, n) | dev_alloc(ctx, ctx->d_ri_blen, n) | dev_alloc(ctx, ctx->d_ri_actf, n) |
+         dev_alloc(ctx, ctx->d_ri_trec, n * 16);
+  const int64_t slot_cap = 2 * n + 16;
+  rcx |= dev_alloc(ctx, ctx->d_si_reclen, slot_cap) | dev_alloc(ctx, ctx->d_si_recact, slot_cap) | dev_alloc(ctx, ctx->d_si_writer, slot_cap) |
+         dev_alloc(ctx, ctx->d_si_mult, slot_cap);
   ctx->lk.cap = (int32_t)std::min<int64_t>(n + 16, (int64_t)1 << 20);     // link index field of SlotInfo::writer: 20 bits
   if (ctx->lk.cap > (int32_t)LINK_NONE - 1) ctx->lk.cap = (int32_t)LINK_NONE - 1;
-  rcx |= dev_alloc(ctx, &ctx->lk.rec, (size_t)ctx->lk.cap * 4);
+  rcx |= dev_alloc(ctx, ctx->d_lk_rec, (size_t)ctx->lk.cap * 4);
+  ctx->ri.flen = ctx->d_ri_flen; ctx->ri.blen = ctx->d_ri_blen; ctx->ri.actf = ctx->d_ri_actf; ctx->ri.trec = ctx->d_ri_trec;
+  ctx->si.reclen = ctx->d_si_reclen; ctx->si.recact = ctx->d_si_recact; ctx->si.writer = ctx->d_si_writer; ctx->si.mult = ctx->d_si_mult;
+  ctx->lk.rec = ctx->d_lk_rec;
   if (rcx) return MIA_HIP_ERR_NOMEM;
   HIPCHK(hipMemcpyAsync(ctx->d_packed, packed.data(), packed.size(), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(ctx->d_roff, roff.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -658,9 +627,7 @@ extern "C" int mia_hip_upload_reads(mia_hip_ctx* ctx, int64_t n, const char* bas
   r.n = n; r.packed = ctx->d_packed; r.roff = ctx->d_roff; r.len = ctx->d_len; r.rc = ctx->d_rc; r.sk = ctx->d_sk;
   r.as = ctx->d_as; r.ae = ctx->d_ae; r.score = ctx->d_score; r.refstart = ctx->d_refstart; r.abr = ctx->d_abr;
   r.status = ctx->d_status; r.cols = ctx->d_cols; r.stride = stride;
-  if (ctx->d_order) { (void)hipFree(ctx->d_order); ctx->d_order = nullptr; }
-  if (ctx->d_order2) { (void)hipFree(ctx->d_order2); ctx->d_order2 = nullptr; }
-  if (ctx->d_okey) { (void)hipFree(ctx->d_okey); ctx->d_okey = nullptr; }
+  ctx->d_order.release(); ctx->d_order2.release(); ctx->d_okey.release();      // sized by n: made again by the next tally
   ctx->umax_valid = false;
   if (n > 0) hipLaunchKernelGGL(k_read_planes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rs, ctx->rplane_words, ctx->d_rplanes);
   if (ctx->have_pssm && ctx->bx_ok && n > 0) {
@@ -868,12 +835,10 @@ static hipError_t launch_window(mia_hip_ctx* ctx, int ci, const int32_t* list, i
   unsigned char* slabs = nullptr;
   if (own_slabs) {
     grid = std::min(grid, 1024);
-    if (!ctx->d_slabs_retry[ci] && hipMalloc((void**)&ctx->d_slabs_retry[ci], (size_t)slab * 1024) != hipSuccess) return hipErrorOutOfMemory;
+    if (!ctx->d_slabs_retry[ci] && dev_alloc(ctx, ctx->d_slabs_retry[ci], slab * 1024)) return hipErrorOutOfMemory;
     slabs = ctx->d_slabs_retry[ci];
   } else {
-    if (!ctx->d_slabs[ci]) {
-      if (hipMalloc((void**)&ctx->d_slabs[ci], (size_t)slab * ctx->grid_wgs) != hipSuccess) return hipErrorOutOfMemory;
-    }
+    if (!ctx->d_slabs[ci] && dev_alloc(ctx, ctx->d_slabs[ci], slab * ctx->grid_wgs)) return hipErrorOutOfMemory;
     slabs = ctx->d_slabs[ci];
   }
   RefInfo ref{ctx->d_ref, ctx->L, ctx->wrap, ctx->explicit_win};
@@ -915,10 +880,7 @@ extern "C" int mia_hip_realign(mia_hip_ctx* ctx, const char* new_ref, int32_t re
     ctx->kh_entries = kh_wild_entries(codes.data(), wrap, BX_WILD);
     if (ctx->kh_entries > ((int64_t)1 << 24)) ctx->kh_entries = 0;
   }
-  if ((int)codes.size() > ctx->ref_cap) {
-    if (dev_alloc(ctx, &ctx->d_ref, codes.size() * 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->ref_cap = (int)codes.size() * 2;
-  }
+  if (dev_ensure(ctx, ctx->d_ref, (int64_t)codes.size(), (int64_t)codes.size() * 2)) return MIA_HIP_ERR_NOMEM;
   if (ctx->h_pin && codes.size() <= mia_hip_ctx::PIN_BYTES - mia_hip_ctx::PIN_MISC) {
     HIPCHK(hipStreamSynchronize(ctx->stream));             // the staging area may still feed an earlier copy
     memcpy(ctx->h_pin + mia_hip_ctx::PIN_MISC, codes.data(), codes.size());
@@ -954,14 +916,7 @@ static int run_wide(mia_hip_ctx* ctx, const RefInfo& ref, int32_t n_wide) {
       soff[t] = total;
       total += (int64_t)ln[t] * n1 + 5 * (int64_t)n1 + 16;
     }
-    if (total > ctx->scratch_cap) {
-      if (dev_alloc(ctx, &ctx->d_scratch, (size_t)total)) return MIA_HIP_ERR_NOMEM;
-      ctx->scratch_cap = total;
-    }
-    if (n_wide > ctx->scratch_off_cap) {
-      if (dev_alloc(ctx, &ctx->d_scratch_off, (size_t)n_wide)) return MIA_HIP_ERR_NOMEM;
-      ctx->scratch_off_cap = n_wide;
-    }
+    if (dev_ensure(ctx, ctx->d_scratch, total) || dev_ensure(ctx, ctx->d_scratch_off, n_wide)) return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipMemcpyAsync(ctx->d_scratch_off, soff.data(), (size_t)n_wide * 8, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_align_wide, dim3((n_wide + 63) / 64), dim3(64), 0, ctx->stream, ctx->rs, ref, ctx->d_pssm, ctx->d_wide_list,
                        n_wide, ctx->d_scratch_off, ctx->d_scratch);
@@ -1037,14 +992,6 @@ static void align_ck(mia_hip_ctx* ctx, const AlignCall& c, const char* what) {
   fprintf(stderr, "[align_all deferred] %s: %s\n", what, hipGetErrorString(e)); fflush(stderr);
 }
 
-template <class T>
-static int grow(mia_hip_ctx* ctx, T** p, int64_t* cap, int64_t want, size_t elems) {
-  if (want <= *cap) return MIA_HIP_OK;
-  if (dev_alloc(ctx, p, elems)) return MIA_HIP_ERR_NOMEM;
-  *cap = want;
-  return MIA_HIP_OK;
-}
-
 // BUFFERS: everything the route's kernels write to, grown to this alignment's sizes (the full-window kernels' trace slabs are made
 // where those are launched: launch_window)
 static int align_ensure_buffers(mia_hip_ctx* ctx, AlignCall& c) {
@@ -1052,33 +999,23 @@ static int align_ensure_buffers(mia_hip_ctx* ctx, AlignCall& c) {
   const int64_t n = ctx->rs.n;
   const int wrap = ctx->wrap;
   if (!r.filtered) return MIA_HIP_OK;
-  if (grow(ctx, &ctx->d_planes, &ctx->plane_cap, r.plane_words, (size_t)r.plane_words * 3)) return MIA_HIP_ERR_NOMEM;
-  if (r.kocc && !ctx->d_kocc_cnt && (dev_alloc(ctx, &ctx->d_kocc_cnt, (size_t)DF_KTAB) || dev_alloc(ctx, &ctx->d_kocc_pos, (size_t)DF_KTAB * DF_KCAP)))
+  if (dev_ensure(ctx, ctx->d_planes, r.plane_words * 3)) return MIA_HIP_ERR_NOMEM;
+  if (r.kocc && !ctx->d_kocc_cnt && (dev_alloc(ctx, ctx->d_kocc_cnt, DF_KTAB) || dev_alloc(ctx, ctx->d_kocc_pos, (int64_t)DF_KTAB * DF_KCAP)))
     return MIA_HIP_ERR_NOMEM;
-  if (((r.run_filter && r.banded) || r.quick) && grow(ctx, &ctx->d_left_list, &ctx->left_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+  if (((r.run_filter && r.banded) || r.quick) && dev_ensure(ctx, ctx->d_left_list, n)) return MIA_HIP_ERR_NOMEM;
   if (!r.bx) {
     // round 1's banded DP: a persistent grid of wavefronts (three per SIMD), each with its own trace slab
     c.slab_words = (int64_t)ctx->max_len * BAND_ROW_WORDS;
     const int64_t words = c.slab_words * std::min<int64_t>((n + 63) / 64, 3072);
-    return r.banded ? grow(ctx, &ctx->d_band_slabs, &ctx->band_slab_cap, words, (size_t)words) : MIA_HIP_OK;
+    return r.banded ? dev_ensure(ctx, ctx->d_band_slabs, words) : MIA_HIP_OK;
   }
   // the reference as 4-bit codes, the lists, one slab per wavefront of the trace kernel's persistent grid
   c.nib_words = bx_nib_words((int64_t)wrap + 64);
-  if (c.nib_words > ctx->refnib_cap) {
-    if (dev_alloc(ctx, &ctx->d_refnib, (size_t)c.nib_words * 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->refnib_cap = c.nib_words * 2;
-  }
+  if (dev_ensure(ctx, ctx->d_refnib, c.nib_words, c.nib_words * 2)) return MIA_HIP_ERR_NOMEM;
   c.kslots = kh_slots_for_entries(wrap, ctx->kh_entries);
-  if (c.kslots > ctx->khash_cap) {
-    if (dev_alloc(ctx, &ctx->d_khash, (size_t)c.kslots * 4) || dev_alloc(ctx, &ctx->d_khash_ovf, (size_t)c.kslots * 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->khash_cap = c.kslots;
-  }
-  if (r.want_bits && !ctx->d_kbits && dev_alloc(ctx, &ctx->d_kbits, (size_t)KB_WORDS)) return MIA_HIP_ERR_NOMEM;
-  if (n > ctx->bx_cap) {
-    if (dev_alloc(ctx, &ctx->d_bx_plan, (size_t)n) || dev_alloc(ctx, &ctx->d_bx_expect, (size_t)n) || dev_alloc(ctx, &ctx->d_bx_lists, (size_t)n * 4 * BX_NCLS))
-      return MIA_HIP_ERR_NOMEM;
-    ctx->bx_cap = n;
-  }
+  if (dev_ensure(ctx, ctx->d_khash, (int64_t)c.kslots * 4) || dev_ensure(ctx, ctx->d_khash_ovf, (int64_t)c.kslots * 2)) return MIA_HIP_ERR_NOMEM;
+  if (r.want_bits && !ctx->d_kbits && dev_alloc(ctx, ctx->d_kbits, KB_WORDS)) return MIA_HIP_ERR_NOMEM;
+  if (dev_ensure(ctx, ctx->d_bx_plan, n) || dev_ensure(ctx, ctx->d_bx_expect, n) || dev_ensure(ctx, ctx->d_bx_lists, n * 4 * BX_NCLS)) return MIA_HIP_ERR_NOMEM;
   if (!ctx->bx_values_wgs) {
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ctx->use_lanes ? (const void*)k_bxl_values : ALT_KERNEL(k_bx_values), 256, 0) != hipSuccess || occ < 1) occ = 1;
@@ -1089,22 +1026,19 @@ static int align_ensure_buffers(mia_hip_ctx* ctx, AlignCall& c) {
   // (the lanes kernels store four rows per word: whole blocks of four rows)
   c.slab_words = ctx->use_lanes ? (int64_t)((ctx->max_len + 3) & ~3) * BXL_SLAB_ROW_WORDS : (int64_t)ctx->max_len * BX_SLAB_ROW_WORDS;
   const int64_t trace_words = c.slab_words * ctx->bx_trace_wgs * 4;
-  if (grow(ctx, &ctx->d_bx_slabs, &ctx->bx_slab_cap, trace_words, (size_t)trace_words)) return MIA_HIP_ERR_NOMEM;
+  if (dev_ensure(ctx, ctx->d_bx_slabs, trace_words)) return MIA_HIP_ERR_NOMEM;
   if (r.new_flow) {
-    if (grow(ctx, &ctx->d_retry2, &ctx->retry2_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+    if (dev_ensure(ctx, ctx->d_retry2, n)) return MIA_HIP_ERR_NOMEM;
     if (!ctx->bx_late_wgs) ctx->bx_late_wgs = ctx->cus;        // the values DP's left-overs are few: one workgroup per CU
     const int64_t late_words = (int64_t)((ctx->max_len + 3) & ~3) * BXL_SLAB_ROW_WORDS * ctx->bx_late_wgs * 4;
-    if (late_words > ctx->bx_slab_late_cap) {
-      if (dev_alloc(ctx, &ctx->d_bx_slabs_late, (size_t)late_words) || dev_alloc(ctx, &ctx->d_bx_slabs_late2, (size_t)late_words)) return MIA_HIP_ERR_NOMEM;
-      ctx->bx_slab_late_cap = late_words;
-    }
+    if (dev_ensure(ctx, ctx->d_bx_slabs_late, late_words) || dev_ensure(ctx, ctx->d_bx_slabs_late2, late_words)) return MIA_HIP_ERR_NOMEM;
   }
-  if (r.split && grow(ctx, &ctx->d_bx_cand, &ctx->cand_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+  if (r.split && dev_ensure(ctx, ctx->d_bx_cand, n)) return MIA_HIP_ERR_NOMEM;
   // (the third launch's list only where that launch runs: a record is 72 bytes -- 0.7 GB at 10 M reads)
-  if (r.fine && grow(ctx, &ctx->d_bx_cand2, &ctx->cand2_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+  if (r.fine && dev_ensure(ctx, ctx->d_bx_cand2, n)) return MIA_HIP_ERR_NOMEM;
   if (r.direct_open) {
-    if (grow(ctx, &ctx->d_open_list, &ctx->open_cap, n, (size_t)n)) return MIA_HIP_ERR_NOMEM;
-    if (!ctx->d_slabs_open && hipMalloc((void**)&ctx->d_slabs_open, (size_t)OPEN_SLAB_BYTES * OPEN_WGS) != hipSuccess) return MIA_HIP_ERR_NOMEM;
+    if (dev_ensure(ctx, ctx->d_open_list, n)) return MIA_HIP_ERR_NOMEM;
+    if (!ctx->d_slabs_open && dev_alloc(ctx, ctx->d_slabs_open, OPEN_SLAB_BYTES * OPEN_WGS)) return MIA_HIP_ERR_NOMEM;
   }
   return MIA_HIP_OK;
 }
@@ -1114,16 +1048,16 @@ static int align_ensure_buffers(mia_hip_ctx* ctx, AlignCall& c) {
 static int align_ref_prep(mia_hip_ctx* ctx, AlignCall& c) {
   const AlignRoute& r = c.r;
   const int wrap = ctx->wrap;
-  const int64_t words = r.plane_words;
+  const int64_t words = r.plane_words, pstride = ctx->d_planes.cap / 3;      // the block holds three planes
   if (!r.fused_prep) {
     encode_now(ctx);
     HIPCHK(hipMemsetAsync(ctx->d_ctrl, 0, (size_t)CTRL_WORDS * 4, ctx->stream));     // every counter of the iteration at once
   }
   if (!r.filtered) return MIA_HIP_OK;
-  c.rp = RefPlanes{ctx->d_planes, ctx->d_planes + ctx->plane_cap, ctx->d_planes + 2 * ctx->plane_cap};
+  c.rp = RefPlanes{ctx->d_planes, ctx->d_planes + pstride, ctx->d_planes + 2 * pstride};
   if (!r.fused_prep)
     hipLaunchKernelGGL(k_ref_planes, dim3((unsigned)((words + 3) / 4 < 4096 ? (words + 3) / 4 : 4096)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap + 64, words,
-                       ctx->d_planes, ctx->d_planes + ctx->plane_cap, ctx->d_planes + 2 * ctx->plane_cap);
+                       ctx->d_planes, ctx->d_planes + pstride, ctx->d_planes + 2 * pstride);
   if (r.kocc) {
     HIPCHK(hipMemsetAsync(ctx->d_kocc_cnt, 0, (size_t)DF_KTAB * 4, ctx->stream));
     hipLaunchKernelGGL(k_kmer_occ, dim3((unsigned)((wrap + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ref, (int64_t)wrap, ctx->d_kocc_cnt, ctx->d_kocc_pos, 0);
@@ -1150,7 +1084,7 @@ static int align_ref_prep(mia_hip_ctx* ctx, AlignCall& c) {
   rp2.ascii = ctx->ascii_src; rp2.L = ctx->pend_L; rp2.wl = ctx->pend_wl; rp2.total = ctx->pend_total; rp2.codes = ctx->d_ref;
   rp2.ctrl = ctx->d_ctrl; rp2.ctrl_words = CTRL_WORDS;
   rp2.kslot = ctx->d_khash; rp2.kovf = ctx->d_khash_ovf; rp2.kslots = kslots; rp2.kmask = kh.mask; rp2.kshift = kh.shift; rp2.kwild = kh.wild;
-  rp2.plane_words = words; rp2.plo = ctx->d_planes; rp2.phi = ctx->d_planes + ctx->plane_cap; rp2.pok = ctx->d_planes + 2 * ctx->plane_cap;
+  rp2.plane_words = words; rp2.plo = ctx->d_planes; rp2.phi = ctx->d_planes + pstride; rp2.pok = ctx->d_planes + 2 * pstride;
   rp2.nib_words = nw; rp2.nib = ctx->d_refnib;
   const int64_t want = ((int64_t)wrap + (kh.wild > 0 ? 63 : 255)) / (kh.wild > 0 ? 64 : 256);       // (N columns spelled out: 64 positions per workgroup, see kmer_hash_insert_block)
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, ctx->cus));      // one workgroup per compute unit at most: all resident
@@ -1182,7 +1116,7 @@ static void align_bx_dev(mia_hip_ctx* ctx, AlignCall& c) {
   bd.umax = (ctx->umax_valid && ctx->rs.roff == ctx->d_roff) ? ctx->d_umax : nullptr;    // (a borrowed read set has none)
   bd.rplanes = bd.umax ? ctx->d_rplanes : nullptr;
   bd.rplane_words = ctx->rplane_words;
-  bd.plan = ctx->d_bx_plan; bd.expect = ctx->d_bx_expect; bd.lists = ctx->d_bx_lists; bd.list_stride = ctx->bx_cap; bd.ctr = ctx->d_bx_ctr;
+  bd.plan = ctx->d_bx_plan; bd.expect = ctx->d_bx_expect; bd.lists = ctx->d_bx_lists; bd.list_stride = ctx->d_bx_lists.cap / (4 * BX_NCLS); bd.ctr = ctx->d_bx_ctr;
   bd.cand = r.split ? ctx->d_bx_cand : nullptr; bd.cand_n = ctx->d_bx_ctr + (size_t)BXC_CAND * BXC_STRIDE;
   bd.cand2 = r.fine ? ctx->d_bx_cand2 : nullptr; bd.cand2_n = ctx->d_bx_ctr + (size_t)BXC_CAND2 * BXC_STRIDE;
   bd.open = r.direct_open ? ctx->d_open_list : nullptr; bd.open_n = ctx->d_bx_ctr + (size_t)BXC_OPEN * BXC_STRIDE;
@@ -1410,7 +1344,7 @@ static int align_planner_deferred(mia_hip_ctx* ctx, AlignCall& c) {
     align_ck(ctx, c, "replan");
   }
   const int64_t slab = (int64_t)Q_G * MAX_READ * Q_TRACE_STRIDE;
-  if (!ctx->d_quad_slabs && hipMalloc((void**)&ctx->d_quad_slabs, (size_t)slab * ctx->quad_wgs) != hipSuccess) return MIA_HIP_ERR_NOMEM;
+  if (!ctx->d_quad_slabs && dev_alloc(ctx, ctx->d_quad_slabs, slab * ctx->quad_wgs)) return MIA_HIP_ERR_NOMEM;
   if (c.dbg_steps) {
     int32_t hh[PH_WORDS];
     (void)hipMemcpy(hh, hdr, sizeof hh, hipMemcpyDeviceToHost);
@@ -1584,7 +1518,7 @@ static int align_planner_host_plain(mia_hip_ctx* ctx, AlignCall& c, HostPlan& h)
 static int align_planner_host_trace(mia_hip_ctx* ctx, AlignCall& c, HostPlan& h) {
   const int64_t slab = (int64_t)Q_G * MAX_READ * Q_TRACE_STRIDE;
   const int grid = h.n_quads < ctx->quad_wgs ? h.n_quads : ctx->quad_wgs;
-  if (!ctx->d_quad_slabs && hipMalloc((void**)&ctx->d_quad_slabs, (size_t)slab * ctx->quad_wgs) != hipSuccess) return MIA_HIP_ERR_NOMEM;
+  if (!ctx->d_quad_slabs && dev_alloc(ctx, ctx->d_quad_slabs, slab * ctx->quad_wgs)) return MIA_HIP_ERR_NOMEM;
   const size_t quad_lds = (size_t)Q_G * q_sub_bytes(ctx->max_len) + 16;
   if (stage_begin(ctx, STG_TRACE)) return MIA_HIP_ERR_NOMEM;
   hipLaunchKernelGGL(k_align_quad, dim3(grid), dim3(64), quad_lds, ctx->stream, ctx->rs, c.ref, ctx->d_pssm, ctx->packs.p[0], ctx->d_list + h.quad_begin,
@@ -1675,10 +1609,7 @@ extern "C" int mia_hip_align_windows(mia_hip_ctx* ctx, const char* ref, int64_t 
   }
   std::vector<uint8_t> codes((size_t)ref_len + 64, 4);
   for (int64_t i = 0; i < ref_len; i++) codes[(size_t)i] = base_code(ref[i]);
-  if ((int64_t)codes.size() > ctx->ref_cap) {
-    if (dev_alloc(ctx, &ctx->d_ref, codes.size())) return MIA_HIP_ERR_NOMEM;
-    ctx->ref_cap = (int)codes.size();
-  }
+  if (dev_ensure(ctx, ctx->d_ref, (int64_t)codes.size())) return MIA_HIP_ERR_NOMEM;
   HIPCHK(hipMemcpyAsync(ctx->d_ref, codes.data(), codes.size(), hipMemcpyHostToDevice, ctx->stream));
   if (n) {
     HIPCHK(hipMemcpyAsync(ctx->d_as, as.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1727,11 +1658,8 @@ static int finish_params(mia_hip_ctx* ctx);
 // second half of the cull: every link (own or gathered) acts on the slot it points at, then each read's dropped bits,
 // depth-code parameters and multiplicities are final.  Runs at the end of mia_hip_cull and again after mia_hip_set_links.
 static int finish_cull(mia_hip_ctx* ctx) {
-  if (ctx->links_cap_all > ctx->link_len_cap) {
-    if (dev_alloc(ctx, &ctx->d_link_len, (size_t)ctx->links_cap_all + 64) || dev_alloc(ctx, &ctx->d_link_act, (size_t)ctx->links_cap_all + 64))
-      return MIA_HIP_ERR_NOMEM;
-    ctx->link_len_cap = ctx->links_cap_all + 64;
-  }
+  const int64_t nl = ctx->links_cap_all;
+  if (dev_ensure(ctx, ctx->d_link_len, nl, nl + 64) || dev_ensure(ctx, ctx->d_link_act, nl, nl + 64)) return MIA_HIP_ERR_NOMEM;
   hipLaunchKernelGGL(k_links_apply, dim3(32), dim3(256), 0, ctx->stream, ctx->d_links_all, ctx->d_n_links_all, (int32_t)ctx->links_cap_all, ctx->si,
                      ctx->d_slot_dropped, ctx->n_slots, ctx->d_link_len, ctx->d_link_act, ctx->d_cull_flags, ctx->abort_if);
   ctx->links_applied = true;
@@ -1771,21 +1699,20 @@ extern "C" int mia_hip_cull(mia_hip_ctx* ctx, int32_t hard_cut, double slope, do
   // geometry, dropped marks and links of every read in one kernel -- k_slot_count / k_cull_records)
   const int nb = (int)((n + 255) / 256);
   if (!ctx->d_cull_sync) {
-    if (dev_alloc(ctx, &ctx->d_cull_sync, 4)) return MIA_HIP_ERR_NOMEM;
+    if (dev_alloc(ctx, ctx->d_cull_sync, 4)) return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipMemsetAsync(ctx->d_cull_sync, 0, 16, ctx->stream));
   }
   hipLaunchKernelGGL(k_slot_count, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, ctx->stream, ctx->rs, ctx->L, ctx->d_partial, nb, slot_base, ctx->d_total, (uint32_t*)nullptr, ctx->abort_if);
   // (MIA_HIP_CULL_SCAN=1: the counts scanned by a single-workgroup launch in between, as before)
   if (ctx->cull_scan) hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(256), 0, ctx->stream, ctx->d_partial, nb, slot_base, ctx->d_total, ctx->abort_if);
   if (slot_base + 2 * n + 16 > ctx->n_slots) {   // sharded runs: slots are global indices
-    uint8_t* nd = nullptr;
+    DevBuf<uint8_t> nd;
     const int64_t ns = slot_base + 2 * n + 16;
-    if (hipMalloc((void**)&nd, (size_t)ns) != hipSuccess) return MIA_HIP_ERR_NOMEM;
+    if (dev_alloc(ctx, nd, ns)) return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipMemsetAsync(nd, 0, (size_t)ns, ctx->stream));
     HIPCHK(hipMemcpyAsync(nd, ctx->d_slot_dropped, (size_t)ctx->n_slots, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->d_slot_dropped);
-    ctx->d_slot_dropped = nd;
+    ctx->d_slot_dropped = std::move(nd);
     ctx->n_slots = ns;
   }
   // records per read and per slot, the reads' own dropped marks, and the links of formerly split reads -- all without a
@@ -1857,16 +1784,15 @@ extern "C" int mia_hip_set_links(mia_hip_ctx* ctx, const int64_t* d_links_all, i
   if (n_all >= (int64_t)LINK_NONE) { ctx->err = "too many links"; return MIA_HIP_ERR_RANGE; }
   HIPCHK(hipSetDevice(ctx->device));
   // own copy of the gathered list (the caller's buffer may be a temporary of the collective)
-  if (n_all > ctx->links_all_cap) {
-    int64_t* nb = nullptr;
-    if (hipMalloc((void**)&nb, (size_t)(n_all + 64) * 32) != hipSuccess) return MIA_HIP_ERR_NOMEM;
-    ctx->links_all_cap = n_all + 64;
-    ctx->d_links_all = nb;          // (the previous gathered buffer, if any, is released with the context)
-    ctx->owned_links.push_back(nb);
-  } else if (!ctx->owned_links.empty()) ctx->d_links_all = ctx->owned_links.back();
+  if (n_all * 4 > (ctx->owned_links.empty() ? 0 : ctx->owned_links.back().cap)) {      // (a link is four words)
+    DevBuf<int64_t> nb;
+    if (dev_alloc(ctx, nb, (n_all + 64) * 4)) return MIA_HIP_ERR_NOMEM;
+    ctx->owned_links.push_back(std::move(nb));      // (the previous gathered buffer, if any, is released with the context)
+  }
+  if (!ctx->owned_links.empty()) ctx->d_links_all = ctx->owned_links.back();
   if (n_all > 0) HIPCHK(hipMemcpyAsync(ctx->d_links_all, d_links_all, (size_t)n_all * 32, hipMemcpyDeviceToDevice, ctx->stream));
   ctx->n_links_all = (int32_t)n_all;
-  if (!ctx->d_n_links_gathered && dev_alloc(ctx, &ctx->d_n_links_gathered, 1)) return MIA_HIP_ERR_NOMEM;
+  if (!ctx->d_n_links_gathered && dev_alloc(ctx, ctx->d_n_links_gathered, 1)) return MIA_HIP_ERR_NOMEM;
   const int32_t n32 = (int32_t)n_all;
   HIPCHK(hipMemcpyAsync(ctx->d_n_links_gathered, &n32, 4, hipMemcpyHostToDevice, ctx->stream));
   ctx->d_n_links_all = ctx->d_n_links_gathered;
@@ -1927,8 +1853,9 @@ extern "C" int mia_hip_set_slot_dropped(mia_hip_ctx* ctx, const uint8_t* flags, 
   if (!ctx->d_slot_dropped) { ctx->err = "upload_reads first"; return MIA_HIP_ERR_STATE; }
   HIPCHK(hipSetDevice(ctx->device));
   if (n_flags > ctx->n_slots) {            // a shard is handed the marks of ALL slots: its own lie behind the other ranks'
-    if (dev_alloc(ctx, &ctx->d_slot_dropped, (size_t)n_flags + 16)) return MIA_HIP_ERR_NOMEM;
-    ctx->n_slots = n_flags + 16;
+    const int rca = dev_alloc(ctx, ctx->d_slot_dropped, n_flags + 16);
+    ctx->n_slots = ctx->d_slot_dropped.cap;      // (0 with the block gone)
+    if (rca) return rca;
   }
   HIPCHK(hipMemsetAsync(ctx->d_slot_dropped, 0, (size_t)ctx->n_slots, ctx->stream));
   HIPCHK(hipMemcpyAsync(ctx->d_slot_dropped, flags, (size_t)n_flags, hipMemcpyHostToDevice, ctx->stream));
@@ -1988,7 +1915,7 @@ extern "C" int mia_hip_score_sums(mia_hip_ctx* ctx, int64_t* sums5) {
   if (!ctx || !sums5) return MIA_HIP_ERR_ARG;
   if (!ctx->aligned) { ctx->err = "realign first"; return MIA_HIP_ERR_STATE; }
   HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->d_sums && dev_alloc(ctx, &ctx->d_sums, 8)) return MIA_HIP_ERR_NOMEM;
+  if (!ctx->d_sums && dev_alloc(ctx, ctx->d_sums, 8)) return MIA_HIP_ERR_NOMEM;
   ctx->pre_cull_valid = false;
   hipLaunchKernelGGL(k_score_sums_init, dim3(1), dim3(64), 0, ctx->stream, ctx->d_sums, (const int32_t*)nullptr);
   const int64_t n = ctx->rs.n;
@@ -2051,26 +1978,25 @@ extern "C" int mia_hip_num_records(mia_hip_ctx* ctx, int64_t* n_records) {
 }
 
 // ---- tally + consensus -------------------------------------------------------------
+// The insert-event list: exactly `elems` entries, and the kernels' view of it (tb.events, tb.cap_events: an int32) set with it.
+// Every caller decides for itself when the list is too short.
+static int ensure_events(mia_hip_ctx* ctx, int64_t elems) {
+  const int rc = dev_alloc(ctx, ctx->d_tb_events, elems);
+  ctx->tb.events = ctx->d_tb_events;
+  ctx->tb.cap_events = (int32_t)std::min<int64_t>(ctx->d_tb_events.cap, INT32_MAX);
+  return rc;
+}
+
 static int ensure_tally(mia_hip_ctx* ctx) {
   const int Lp = ctx->L + 1;
-  if (Lp > ctx->tally_cap) {
-    int rc = 0;
-    rc |= dev_alloc(ctx, &ctx->tb.tally, (size_t)(TALLY_WORDS + 1) * Lp + 256);      // tally[12][Lp], then gaps[Lp] (+ one slot per rank of a sharded run): one memset clears all
-    rc |= dev_alloc(ctx, &ctx->d_ins_off, (size_t)Lp);
-    rc |= dev_alloc(ctx, &ctx->d_calls, (size_t)Lp);
-    if (rc) return MIA_HIP_ERR_NOMEM;
-    ctx->tally_cap = Lp;
-  }
-  if (!ctx->tb.events) {
-    // every inserted read base is one event; 1/8 of all bases is far beyond any real data,
-    // overflow is detected and reported
-    int64_t cap = ctx->rs.n * 32 + 4096;
-    if (cap > ((int64_t)1 << 30)) cap = (int64_t)1 << 30;
-    int rc = 0;
-    rc |= dev_alloc(ctx, &ctx->tb.events, (size_t)cap);
-    if (rc) return MIA_HIP_ERR_NOMEM;
-    ctx->tb.cap_events = (int32_t)cap;
-  }
+  // tally[12][Lp], then gaps[Lp] (+ one slot per rank of a sharded run): one memset clears all
+  int rc = dev_ensure(ctx, ctx->d_tb_tally, (int64_t)(TALLY_WORDS + 1) * Lp + 256);
+  rc |= dev_ensure(ctx, ctx->d_ins_off, Lp);
+  rc |= dev_ensure(ctx, ctx->d_calls, Lp);
+  if (rc) return MIA_HIP_ERR_NOMEM;
+  // every inserted read base is one event; 1/8 of all bases is far beyond any real data, overflow is detected and reported
+  if (!ctx->tb.events && ensure_events(ctx, std::min<int64_t>(ctx->rs.n * 32 + 4096, (int64_t)1 << 30))) return MIA_HIP_ERR_NOMEM;
+  ctx->tb.tally = ctx->d_tb_tally;
   ctx->tb.Lp = Lp;
   ctx->tb.gaps = ctx->tb.tally + (size_t)TALLY_WORDS * Lp;      // right behind the tally of THIS reference length
   return MIA_HIP_OK;
@@ -2105,12 +2031,11 @@ static int bucket_launch(mia_hip_ctx* ctx, hipStream_t on) {
   const int nb = tally_nb(ctx), split = tally_split(ctx);
   const int chunk = tally_chunk(ctx);
   const int grid = (int)(n / chunk) + nb + 1;
-  if (4 * (nb + 1) + 4 * grid > ctx->bucket_cap) {
-    if (dev_alloc(ctx, &ctx->d_bucket, (size_t)(4 * (nb + 1) + 4 * grid) * 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->bucket_cap = (4 * (nb + 1) + 4 * grid) * 2;
+  if (4 * (nb + 1) + 4 * grid > ctx->d_bucket.cap) {
+    if (dev_alloc(ctx, ctx->d_bucket, (int64_t)(4 * (nb + 1) + 4 * grid) * 2)) return MIA_HIP_ERR_NOMEM;
     ctx->bucket_clean_nb = -1;
   }
-  if (!ctx->d_order && dev_alloc(ctx, &ctx->d_order, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+  if (!ctx->d_order && dev_alloc(ctx, ctx->d_order, n)) return MIA_HIP_ERR_NOMEM;
   int32_t *d_cnt = ctx->d_bucket, *d_off = d_cnt + (nb + 1), *d_wgoff = d_off + (nb + 1), *d_cur = d_wgoff + (nb + 1), *d_wgb = d_cur + (nb + 1);
   // the bucket counts are left at zero by k_bucket_scan; only a fresh (or differently laid out) buffer is cleared here
   if (ctx->bucket_clean_nb != nb) { HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)(nb + 1) * 4, on)); ctx->bucket_clean_nb = nb; }
@@ -2122,10 +2047,10 @@ static int bucket_launch(mia_hip_ctx* ctx, hipStream_t on) {
   else {
     // ... and every bucket by alignment start (k_sort2_count / k_sort2_fill: the tally's runs of equal starts)
     const int64_t words2 = (int64_t)nb * SORT2_KEYS * 2;
-    if (words2 > ctx->sort2_cap) { if (dev_alloc(ctx, &ctx->d_sort2, (size_t)words2)) return MIA_HIP_ERR_NOMEM; ctx->sort2_cap = words2; }
+    if (dev_ensure(ctx, ctx->d_sort2, words2)) return MIA_HIP_ERR_NOMEM;
     // (each on its own: a failure of the second must not leave the first behind as "both are there" -- ADVICE r05)
-    if (!ctx->d_order2 && dev_alloc(ctx, &ctx->d_order2, (size_t)n)) return MIA_HIP_ERR_NOMEM;
-    if (!ctx->d_okey && dev_alloc(ctx, &ctx->d_okey, (size_t)n + 64)) return MIA_HIP_ERR_NOMEM;
+    if (!ctx->d_order2 && dev_alloc(ctx, ctx->d_order2, n)) return MIA_HIP_ERR_NOMEM;
+    if (!ctx->d_okey && dev_alloc(ctx, ctx->d_okey, n + 64)) return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipMemsetAsync(ctx->d_sort2, 0, (size_t)words2 * 4, on));
     const int32_t packed = (n < (1 << 24) && !ctx->sort2_unpacked) ? 1 : 0;      // (the key in the entry's top byte, or -- 2^24 reads and more -- in a byte array beside it)
     hipLaunchKernelGGL(k_bucket_fill, dim3(gb), dim3(256), (size_t)nb * 8, on, ctx->rs, nb, (const int32_t*)d_off, d_cur, ctx->d_order, ctx->abort_if, split, ctx->d_okey, packed);
@@ -2164,17 +2089,11 @@ static int tally_launch(mia_hip_ctx* ctx) {
       const int grid = (int)(n / chunk) + nb + 1;
       int32_t *d_cnt = ctx->d_bucket, *d_off = d_cnt + (nb + 1), *d_wgoff = d_off + (nb + 1), *d_cur = d_wgoff + (nb + 1), *d_wgb = d_cur + (nb + 1);
       const int64_t slab_words = (int64_t)grid * (TALLY_WORDS - 1) * TALLY_WIN;
-      if (slab_words > ctx->tally_slab_cap) {
-        if (dev_alloc(ctx, &ctx->d_tally_slabs, (size_t)slab_words)) return MIA_HIP_ERR_NOMEM;
-        ctx->tally_slab_cap = slab_words;
-      }
+      if (dev_ensure(ctx, ctx->d_tally_slabs, slab_words)) return MIA_HIP_ERR_NOMEM;
       // (the bit planes and the N marks of the context's own reads: k_read_planes / k_bx_umax at upload)
       const bool planes_ok = ctx->umax_valid && ctx->rs.roff == ctx->d_roff && ctx->d_rplanes && ctx->d_umax;
       const bool defer = ctx->tally_defer;
-      if (defer && n > ctx->gen_cap) {
-        if (dev_alloc(ctx, &ctx->d_gen_list, (size_t)n)) return MIA_HIP_ERR_NOMEM;
-        ctx->gen_cap = n;
-      }
+      if (defer && dev_ensure(ctx, ctx->d_gen_list, n)) return MIA_HIP_ERR_NOMEM;
       int32_t* n_gen = ctx->d_ctrl + CTRL_GENN;
       if (defer && !ctx->in_iterate) HIPCHK(hipMemsetAsync(n_gen, 0, 4, ctx->stream));     // (mia_hip_iterate clears the whole control block)
 #define MIA_TALLY_ARGS(PL, RW, UM, BIAS)                                                                                                              \
@@ -2249,10 +2168,7 @@ extern "C" int mia_hip_ins_events(mia_hip_ctx* ctx, uint64_t** d_events, int64_t
 extern "C" int mia_hip_set_ins_events(mia_hip_ctx* ctx, const uint64_t* d_events, int64_t n_events) {
   if (!ctx || !ctx->tallied || n_events < 0) return MIA_HIP_ERR_STATE;
   HIPCHK(hipSetDevice(ctx->device));
-  if (n_events > ctx->tb.cap_events) {
-    if (dev_alloc(ctx, &ctx->tb.events, (size_t)n_events)) return MIA_HIP_ERR_NOMEM;
-    ctx->tb.cap_events = (int32_t)n_events;
-  }
+  if (n_events > ctx->tb.cap_events && ensure_events(ctx, n_events)) return MIA_HIP_ERR_NOMEM;
   if (n_events > 0 && d_events != ctx->tb.events)
     HIPCHK(hipMemcpyAsync(ctx->tb.events, d_events, (size_t)n_events * 8, hipMemcpyDeviceToDevice, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2349,7 +2265,8 @@ extern "C" int mia_hip_consensus(mia_hip_ctx* ctx, int cons_code, char* out, int
   std::vector<char> ins_big;
   if (total > ctx->ins_tally_cap) {
     const int64_t cap = (int64_t)total + total / 4 + 1024;
-    if (dev_alloc(ctx, &ctx->d_ins_tally, (size_t)ins_words(cap)) || dev_alloc(ctx, &ctx->d_ins_calls, (size_t)cap)) return MIA_HIP_ERR_NOMEM;
+    ctx->ins_tally_cap = 0;
+    if (dev_alloc(ctx, ctx->d_ins_tally, ins_words(cap)) || dev_alloc(ctx, ctx->d_ins_calls, cap)) return MIA_HIP_ERR_NOMEM;
     ctx->ins_tally_cap = cap;
     rc0 = insert_part(cap);
     if (rc0) return rc0;

@@ -17,7 +17,7 @@ constexpr int PRE_WORDS = 8;         // per rank before the cull: five score sum
   } while (0)
 
 static int comm_attach_table(mia_hip_ctx* ctx, const mia_hip_collectives& t) {
-  if (dev_alloc(ctx, &ctx->d_gather, (size_t)PRE_WORDS * t.n_ranks)) return MIA_HIP_ERR_NOMEM;
+  if (dev_alloc(ctx, ctx->d_gather, (int64_t)PRE_WORDS * t.n_ranks)) return MIA_HIP_ERR_NOMEM;
   ctx->coll = t;
   ctx->coll_name = t.name ? t.name : "";                  // (the table is copied, its name included: the caller's string may go away)
   ctx->coll.name = t.name ? ctx->coll_name.c_str() : nullptr;
@@ -79,9 +79,8 @@ static int comm_gather_ragged(mia_hip_ctx* ctx, const int64_t* mine, const std::
   *total_out = total;
   if (total == 0) return MIA_HIP_OK;
   const int64_t pad = mx * words;
-  if (pad > ctx->lmine_cap) { if (dev_alloc(ctx, &ctx->d_lmine, (size_t)pad * 2)) return MIA_HIP_ERR_NOMEM; ctx->lmine_cap = pad * 2; }
-  if (pad * W > ctx->lstage_cap) { if (dev_alloc(ctx, &ctx->d_lstage, (size_t)pad * W * 2)) return MIA_HIP_ERR_NOMEM; ctx->lstage_cap = pad * W * 2; }
-  if (total * words > ctx->lall_cap) { if (dev_alloc(ctx, &ctx->d_lall, (size_t)total * words * 2)) return MIA_HIP_ERR_NOMEM; ctx->lall_cap = total * words * 2; }
+  if (dev_ensure(ctx, ctx->d_lmine, pad, pad * 2) || dev_ensure(ctx, ctx->d_lstage, pad * W, pad * W * 2) || dev_ensure(ctx, ctx->d_lall, total * words, total * words * 2))
+    return MIA_HIP_ERR_NOMEM;
   HIPCHK(hipMemsetAsync(ctx->d_lmine, 0, (size_t)pad * 8, ctx->stream));
   const int64_t nm = counts[(size_t)ctx->comm_rank] * words;
   if (nm > 0) HIPCHK(hipMemcpyAsync(ctx->d_lmine, mine, (size_t)nm * 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -102,7 +101,7 @@ static int comm_gather_ragged(mia_hip_ctx* ctx, const int64_t* mine, const std::
 static int comm_pre_cull_enqueue(mia_hip_ctx* ctx, const int32_t* d_wide_count) {
   const int64_t n = ctx->rs.n;
   const int W = ctx->comm_ranks;
-  if (!ctx->d_sums && dev_alloc(ctx, &ctx->d_sums, 8)) return MIA_HIP_ERR_NOMEM;
+  if (!ctx->d_sums && dev_alloc(ctx, ctx->d_sums, 8)) return MIA_HIP_ERR_NOMEM;
   hipLaunchKernelGGL(k_score_sums_init, dim3(1), dim3(64), 0, ctx->stream, ctx->d_sums, d_wide_count);
   const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cus);
   hipLaunchKernelGGL(k_score_sums, dim3(grid), dim3(256), 0, ctx->stream, ctx->rs, ctx->d_sums, ctx->L, ctx->d_back_slot, ctx->d_front_slot0);
@@ -203,14 +202,7 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
     }
     ctx->kh_entries = e > ((int64_t)1 << 24) ? 0 : e;
   }
-  if (total > ctx->ref_cap) {
-    if (dev_alloc(ctx, &ctx->d_ref, (size_t)total * 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->ref_cap = total * 2;
-  }
-  if (L > ctx->ascii_cap) {
-    if (dev_alloc(ctx, &ctx->d_ascii, (size_t)L * 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->ascii_cap = (int64_t)L * 2;
-  }
+  if (dev_ensure(ctx, ctx->d_ref, total, (int64_t)total * 2) || dev_ensure(ctx, ctx->d_ascii, L, (int64_t)L * 2)) return MIA_HIP_ERR_NOMEM;
   if (ctx->h_pin && (size_t)L <= mia_hip_ctx::PIN_BYTES - mia_hip_ctx::PIN_MISC) {
     HIPCHK(hipStreamSynchronize(ctx->stream));             // the staging area may still feed an earlier copy
     memcpy(ctx->h_pin + mia_hip_ctx::PIN_MISC, new_ref, (size_t)L);
@@ -284,24 +276,19 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
   } else {
     // the same over the reads of ALL ranks in fsdb order (= rank order): scores and lengths gathered, the regression on
     // every rank's host (identical inputs, identical arithmetic)
-    int32_t* d_nl = nullptr;                               // {score..., len...} of this rank, padded to the longest
-    ScopeFree sf; sf.watch((void**)&d_nl);
+    DevBuf<int32_t> d_nl;                                  // {score..., len...} of this rank, padded to the longest
     std::vector<int64_t> cnt1((size_t)W, 1);
     int64_t tot = 0;
     int64_t n64 = n;
-    int64_t* d_n = nullptr; sf.watch((void**)&d_n);
-    if (hipMalloc((void**)&d_n, 8) != hipSuccess) return MIA_HIP_ERR_NOMEM;
+    DevBuf<int64_t> d_n;
+    if (dev_alloc(ctx, d_n, 1)) return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipMemcpyAsync(d_n, &n64, 8, hipMemcpyHostToDevice, ctx->stream));
     if (int rcg = comm_gather_ragged(ctx, d_n, cnt1, 1, &tot)) return rcg;
     HIPCHK(hipMemcpyAsync(n_of.data(), ctx->d_lall, (size_t)W * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     int64_t nmax = 0, ntot = 0;
     for (int r = 0; r < W; r++) { nmax = std::max(nmax, n_of[(size_t)r]); ntot += n_of[(size_t)r]; }
-    if (hipMalloc((void**)&d_nl, (size_t)nmax * 2 * 4) != hipSuccess) return MIA_HIP_ERR_NOMEM;
-    if ((int64_t)W * nmax * 2 > ctx->scores_all_cap) {
-      if (dev_alloc(ctx, &ctx->d_scores_all, (size_t)W * nmax * 2)) return MIA_HIP_ERR_NOMEM;
-      ctx->scores_all_cap = (int64_t)W * nmax * 2;
-    }
+    if (dev_alloc(ctx, d_nl, nmax * 2) || dev_ensure(ctx, ctx->d_scores_all, (int64_t)W * nmax * 2)) return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipMemsetAsync(d_nl, 0, (size_t)nmax * 2 * 4, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_nl, ctx->d_score, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_nl + nmax, ctx->h_len.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -359,11 +346,7 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
     if (const char* e = alt_env("MIA_HIP_EV_PAD")) { const long long v = atoll(e); if (v > 0) ctx->ev_pad = v; }   // (tests: force the overflow path; every rank reads the same value)
     // the gathered events land in this context's list: room for every rank's block before anything is tallied into it
     if (int rct = ensure_tally(ctx)) return rct;
-    if (ctx->ev_pad * W > ctx->tb.cap_events) {
-      const int64_t cap = std::min<int64_t>(ctx->ev_pad * W + 4096, (int64_t)1 << 30);
-      if (dev_alloc(ctx, &ctx->tb.events, (size_t)cap)) return MIA_HIP_ERR_NOMEM;
-      ctx->tb.cap_events = (int32_t)cap;
-    }
+    if (ctx->ev_pad * W > ctx->tb.cap_events && ensure_events(ctx, std::min<int64_t>(ctx->ev_pad * W + 4096, (int64_t)1 << 30))) return MIA_HIP_ERR_NOMEM;
   }
   if (int rct = tally_launch(ctx)) return rct;
   checkpoint("tally");
@@ -381,10 +364,7 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
     for (int r = 0; r < W; r++) ev_counts[(size_t)r] = h_evc[r];
     int64_t total_ev = 0;
     if (int rcg = comm_gather_ragged(ctx, reinterpret_cast<const int64_t*>(ctx->tb.events), ev_counts, 1, &total_ev)) return rcg;
-    if (total_ev > ctx->tb.cap_events) {
-      if (dev_alloc(ctx, &ctx->tb.events, (size_t)total_ev + 4096)) return MIA_HIP_ERR_NOMEM;
-      ctx->tb.cap_events = (int32_t)std::min<int64_t>(total_ev + 4096, INT32_MAX);
-    }
+    if (total_ev > ctx->tb.cap_events && ensure_events(ctx, total_ev + 4096)) return MIA_HIP_ERR_NOMEM;
     if (total_ev > 0) HIPCHK(hipMemcpyAsync(ctx->tb.events, ctx->d_lall, (size_t)total_ev * 8, hipMemcpyDeviceToDevice, ctx->stream));
     int32_t* te = ctx->h_pin ? reinterpret_cast<int32_t*>(ctx->h_pin + (60 << 10)) : nullptr;
     int32_t te_local = (int32_t)total_ev;
@@ -396,10 +376,10 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
   // same on every rank), the counts that rode on the gaps reduce tell k_events_compact how much of each block is real
   auto exchange_events_padded = [&]() -> int {
     const int64_t pad = ctx->ev_pad;
-    if (pad * W > ctx->lstage_cap) { if (dev_alloc(ctx, &ctx->d_lstage, (size_t)pad * W * 2)) return MIA_HIP_ERR_NOMEM; ctx->lstage_cap = pad * W * 2; }
+    if (dev_ensure(ctx, ctx->d_lstage, pad * W, pad * W * 2)) return MIA_HIP_ERR_NOMEM;
     COLLCHK(ctx->coll.all_gather(ctx->coll.user, ctx->tb.events, ctx->d_lstage, (size_t)pad * 8, ctx->stream));
     const unsigned gx = (unsigned)std::min<int64_t>((pad + 255) / 256, 64);
-    hipLaunchKernelGGL(k_events_compact, dim3(gx, (unsigned)W), dim3(256), 0, ctx->stream, (const uint64_t*)ctx->d_lstage, pad, (const int32_t*)(ctx->tb.gaps + Lp), W,
+    hipLaunchKernelGGL(k_events_compact, dim3(gx, (unsigned)W), dim3(256), 0, ctx->stream, (const uint64_t*)ctx->d_lstage.p, pad, (const int32_t*)(ctx->tb.gaps + Lp), W,
                        ctx->tb.events, ctx->tb.cap_events, ctx->tb.n_events, ctx->tb.flags);
     HIPCHK(hipGetLastError());
     return MIA_HIP_OK;
@@ -419,14 +399,7 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
   }
   const int64_t cons_cap = (int64_t)L + ctx->ins_tally_cap + 64;          // string bytes
   const int64_t res_bytes = (int64_t)CH_WORDS * 4 + cons_cap;
-  if (res_bytes > ctx->cons_cap) {
-    if (dev_alloc(ctx, &ctx->d_cons, (size_t)res_bytes * 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->cons_cap = res_bytes * 2;
-  }
-  if (Lp > ctx->cons_pos_cap) {
-    if (dev_alloc(ctx, &ctx->d_cons_pos, (size_t)Lp * 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->cons_pos_cap = (int64_t)Lp * 2;
-  }
+  if (dev_ensure(ctx, ctx->d_cons, res_bytes, res_bytes * 2) || dev_ensure(ctx, ctx->d_cons_pos, Lp, (int64_t)Lp * 2)) return MIA_HIP_ERR_NOMEM;
   const size_t need = (size_t)res_bytes;
   if (need > ctx->pin2_bytes) {
     if (ctx->h_pin2) (void)hipHostFree(ctx->h_pin2);
@@ -442,7 +415,7 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
     // (a workgroup alone on sixteen thousand columns is slower than a launch costs -- 44 + 111 us for two single-workgroup
     // kernels against 5 us each for these: the launches that remain are the ones with a chip-wide dependence between them)
     const int64_t cap = ctx->ins_tally_cap;
-    int32_t* d_res = reinterpret_cast<int32_t*>(ctx->d_cons);
+    int32_t* d_res = reinterpret_cast<int32_t*>(ctx->d_cons.p);
     const unsigned gl = (unsigned)((L + 255) / 256);
     const bool zc = ctx->zero_copy;        // header, string and the alignment's counters written to the host by k_cons_scatter itself
     // the two prefix sums of the tail (insert columns before a column, characters before a column) are worked out by the blocks

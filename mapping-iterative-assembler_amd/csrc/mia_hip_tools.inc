@@ -35,20 +35,16 @@ extern "C" int mia_hip_trim(mia_hip_ctx* ctx, const char* adapter, int64_t n, co
   int64_t grid = (int64_t)ctx->cus * occ;
   if (grid > n) grid = n;
   const int64_t slab = (int64_t)(MAX_ADAPTER + 1) * MAX_READ;
-  uint8_t *d_codes = nullptr, *d_ap = nullptr, *d_ac = nullptr, *d_trimmed = nullptr;
-  int64_t* d_off = nullptr;
-  int32_t *d_flat = nullptr, *d_tp = nullptr, *d_list = nullptr, *d_scratch = nullptr;
-  uint32_t* d_status = nullptr;
-  unsigned char* d_slabs = nullptr;
-  int16_t* d_cols = nullptr;
-  ScopeFree guard;   // every temporary is released on any return
-  for (void** pp : {(void**)&d_codes, (void**)&d_ap, (void**)&d_ac, (void**)&d_trimmed, (void**)&d_off, (void**)&d_flat, (void**)&d_tp,
-                    (void**)&d_list, (void**)&d_scratch, (void**)&d_status, (void**)&d_slabs, (void**)&d_cols})
-    guard.watch(pp);
-  int rcx = dev_alloc(ctx, &d_codes, (size_t)chars + 8) | dev_alloc(ctx, &d_ap, apacked.size()) | dev_alloc(ctx, &d_ac, (size_t)len2) |
-            dev_alloc(ctx, &d_trimmed, (size_t)n) | dev_alloc(ctx, &d_off, (size_t)n + 1) | dev_alloc(ctx, &d_flat, (size_t)PSSM_WORDS) |
-            dev_alloc(ctx, &d_tp, (size_t)n) | dev_alloc(ctx, &d_status, (size_t)n) | dev_alloc(ctx, &d_slabs, (size_t)(slab * grid)) |
-            dev_alloc(ctx, &d_cols, (size_t)(grid * MAX_READ));
+  DevBuf<uint8_t> d_codes, d_ap, d_ac, d_trimmed;   // every temporary is released on any return
+  DevBuf<int64_t> d_off;
+  DevBuf<int32_t> d_flat, d_tp, d_list, d_scratch;
+  DevBuf<uint32_t> d_status;
+  DevBuf<unsigned char> d_slabs;
+  DevBuf<int16_t> d_cols;
+  int rcx = dev_alloc(ctx, d_codes, chars + 8) | dev_alloc(ctx, d_ap, (int64_t)apacked.size()) | dev_alloc(ctx, d_ac, len2) |
+            dev_alloc(ctx, d_trimmed, n) | dev_alloc(ctx, d_off, n + 1) | dev_alloc(ctx, d_flat, PSSM_WORDS) |
+            dev_alloc(ctx, d_tp, n) | dev_alloc(ctx, d_status, n) | dev_alloc(ctx, d_slabs, slab * grid) |
+            dev_alloc(ctx, d_cols, grid * MAX_READ);
   if (rcx) return MIA_HIP_ERR_NOMEM;
   hipError_t e = hipSuccess;
   auto up = [&](void* d, const void* h, size_t b) { if (e == hipSuccess && b) e = hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream); };
@@ -68,7 +64,7 @@ extern "C" int mia_hip_trim(mia_hip_ctx* ctx, const char* adapter, int64_t n, co
     for (int64_t i = 0; i < n; i++) if (status[(size_t)i] != ST_OK) esc.push_back((int32_t)i);
   if (e == hipSuccess && !esc.empty()) {
     const int64_t words = (int64_t)len2 * MAX_READ + 5 * (int64_t)MAX_READ;
-    if (dev_alloc(ctx, &d_list, esc.size()) || dev_alloc(ctx, &d_scratch, (size_t)(words * (int64_t)esc.size()))) return MIA_HIP_ERR_NOMEM;
+    if (dev_alloc(ctx, d_list, (int64_t)esc.size()) || dev_alloc(ctx, d_scratch, words * (int64_t)esc.size())) return MIA_HIP_ERR_NOMEM;
     up(d_list, esc.data(), esc.size() * 4);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(k_trim_wide, dim3((unsigned)((esc.size() + 63) / 64)), dim3(64), 0, ctx->stream, tr, d_ac, len2, d_flat, d_list,
@@ -109,16 +105,8 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->L = ref_len;
   ctx->wrap = ref_len;
   const int64_t ins_chars = n_ins ? ins_off[n_ins] : 0;
-  if (ctx->tb.events && ctx->tb.cap_events < ins_chars + 16) {   // the list was sized for another job
-    (void)hipFree(ctx->tb.events); ctx->tb.events = nullptr;
-    if (dev_alloc(ctx, &ctx->tb.events, (size_t)ins_chars + 4096)) return MIA_HIP_ERR_NOMEM;
-    ctx->tb.cap_events = (int32_t)std::min<int64_t>(ins_chars + 4096, INT32_MAX);
-  }
-  if (!ctx->tb.events) {
-    int rc0 = dev_alloc(ctx, &ctx->tb.events, (size_t)ins_chars + 4096);
-    if (rc0) return MIA_HIP_ERR_NOMEM;
-    ctx->tb.cap_events = (int32_t)std::min<int64_t>(ins_chars + 4096, INT32_MAX);
-  }
+  // no list yet (cap_events 0), or one that was sized for another job
+  if (ctx->tb.cap_events < ins_chars + 16 && ensure_events(ctx, ins_chars + 4096)) return MIA_HIP_ERR_NOMEM;
   int rc = ensure_tally(ctx);
   if (rc) return rc;
   const int Lp = ctx->tb.Lp;
@@ -142,18 +130,16 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->ma_ace_done = false;
   ctx->ma_ace_gaps_ok = ma_ace_gaps_ok(gaps, ref_len);
   ctx->ma_ace_cols_ok = cols_ok;
-  int32_t* d_irec = nullptr;
-  uint8_t* d_rev = nullptr;
-  char* d_smp = nullptr;
-  ScopeFree guard;   // every temporary is released on any return
-  for (void** pp : {(void**)&d_rev, (void**)&d_smp, (void**)&d_irec}) guard.watch(pp);
-  int rcx = dev_alloc(ctx, &ctx->d_ma_start, (size_t)n + 1) | dev_alloc(ctx, &d_rev, (size_t)n + 1) | dev_alloc(ctx, &ctx->d_ma_coff, (size_t)n + 1) |
-            dev_alloc(ctx, &ctx->d_ma_seq, (size_t)chars + 1) | dev_alloc(ctx, &d_smp, (size_t)chars + 1) | dev_alloc(ctx, &d_irec, (size_t)n_ins + 1) |
-            dev_alloc(ctx, &ctx->d_ma_ipos, (size_t)n_ins + 1) | dev_alloc(ctx, &ctx->d_ma_ioff, (size_t)n_ins + 1) |
-            dev_alloc(ctx, &ctx->d_ma_ib, (size_t)ins_chars + 1) | dev_alloc(ctx, &ctx->d_ma_gaps, (size_t)ref_len) |
-            dev_alloc(ctx, &ctx->d_ma_rec_ins, (size_t)n + 1) | dev_alloc(ctx, &ctx->d_ma_ins_list, (size_t)n_ins + 1) |
-            dev_alloc(ctx, &ctx->d_ma_colmap, (size_t)ref_len + 1) | dev_alloc(ctx, &ctx->d_ma_rows, (size_t)n + 1) |
-            dev_alloc(ctx, &ctx->d_ma_ctl, (size_t)MAR_STATE + (size_t)(n / MAR_PER_WG) + 2);
+  DevBuf<int32_t> d_irec;   // every temporary is released on any return
+  DevBuf<uint8_t> d_rev;
+  DevBuf<char> d_smp;
+  int rcx = dev_alloc(ctx, ctx->d_ma_start, n + 1) | dev_alloc(ctx, d_rev, n + 1) | dev_alloc(ctx, ctx->d_ma_coff, n + 1) |
+            dev_alloc(ctx, ctx->d_ma_seq, chars + 1) | dev_alloc(ctx, d_smp, chars + 1) | dev_alloc(ctx, d_irec, n_ins + 1) |
+            dev_alloc(ctx, ctx->d_ma_ipos, n_ins + 1) | dev_alloc(ctx, ctx->d_ma_ioff, n_ins + 1) |
+            dev_alloc(ctx, ctx->d_ma_ib, ins_chars + 1) | dev_alloc(ctx, ctx->d_ma_gaps, ref_len) |
+            dev_alloc(ctx, ctx->d_ma_rec_ins, n + 1) | dev_alloc(ctx, ctx->d_ma_ins_list, n_ins + 1) |
+            dev_alloc(ctx, ctx->d_ma_colmap, (int64_t)ref_len + 1) | dev_alloc(ctx, ctx->d_ma_rows, n + 1) |
+            dev_alloc(ctx, ctx->d_ma_ctl, (int64_t)MAR_STATE + n / MAR_PER_WG + 2);
   if (rcx) return MIA_HIP_ERR_NOMEM;
   int32_t* const d_start = ctx->d_ma_start; int32_t* const d_ipos = ctx->d_ma_ipos;
   int64_t* const d_coff = ctx->d_ma_coff; int64_t* const d_ioff = ctx->d_ma_ioff;
@@ -219,11 +205,7 @@ extern "C" int mia_hip_ma_region(mia_hip_ctx* ctx, int32_t first, int32_t last, 
   if (rows < 0 || rows > n || w < 0) { ctx->err = "ma_region: the selection came back inconsistent"; return MIA_HIP_ERR_DEVICE; }
   if (rows > 0 && w > 0) {
     if (w > INT64_MAX / rows) { ctx->err = "ma_region: the text does not fit"; return MIA_HIP_ERR_NOMEM; }
-    if (ctx->ma_text_cap < rows * w) {
-      ctx->ma_text_cap = 0;
-      if (dev_alloc(ctx, &ctx->d_ma_text, (size_t)(rows * w))) return MIA_HIP_ERR_NOMEM;
-      ctx->ma_text_cap = rows * w;
-    }
+    if (dev_ensure(ctx, ctx->d_ma_text, rows * w)) return MIA_HIP_ERR_NOMEM;
     if (stage_launch(ctx, STG_MA_RENDER, k_ma_region_render, dim3((unsigned)((rows + MAR_THREADS / 64 - 1) / (MAR_THREADS / 64))), dim3(MAR_THREADS), 0,
                      ctx->stream, v, ctx->d_ma_rows, rows, w, ctx->d_ma_text))
       return MIA_HIP_ERR_NOMEM;
@@ -259,16 +241,8 @@ extern "C" int mia_hip_ma_ace(mia_hip_ctx* ctx, int64_t* n_records, int64_t* bod
   ctx->ma_ace_done = false;
   const int64_t n = ctx->ma_n;
   const int32_t L = ctx->ma_L, n_wgs = (int32_t)((n + MAR_PER_WG - 1) / MAR_PER_WG);
-  if (ctx->ma_ace_g_cap < (int64_t)L + 2) {
-    ctx->ma_ace_g_cap = 0;
-    if (dev_alloc(ctx, &ctx->d_ace_g, (size_t)L + 2)) return MIA_HIP_ERR_NOMEM;
-    ctx->ma_ace_g_cap = (int64_t)L + 2;
-  }
-  if (ctx->ma_ace_rec_cap < n + 1) {
-    ctx->ma_ace_rec_cap = 0;
-    if (dev_alloc(ctx, &ctx->d_ace_af, (size_t)n + 1) || dev_alloc(ctx, &ctx->d_ace_len, (size_t)n + 1) || dev_alloc(ctx, &ctx->d_ace_off, (size_t)n + 1)) return MIA_HIP_ERR_NOMEM;
-    ctx->ma_ace_rec_cap = n + 1;
-  }
+  if (dev_ensure(ctx, ctx->d_ace_g, (int64_t)L + 2) || dev_ensure(ctx, ctx->d_ace_af, n + 1) || dev_ensure(ctx, ctx->d_ace_len, n + 1) || dev_ensure(ctx, ctx->d_ace_off, n + 1))
+    return MIA_HIP_ERR_NOMEM;
   MaAceView v{n, ctx->d_ma_start, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos, ctx->d_ma_ioff, ctx->d_ma_ib, ctx->d_ace_g};
   hipLaunchKernelGGL(k_ma_ace_gaps, dim3(1), dim3(MAA_SCAN_THREADS), 0, ctx->stream, (const int32_t*)ctx->d_ma_gaps, L, ctx->d_ace_g);
   HIPCHK(hipGetLastError());
@@ -286,11 +260,7 @@ extern "C" int mia_hip_ma_ace(mia_hip_ctx* ctx, int64_t* n_records, int64_t* bod
   const int64_t bytes = (int64_t)hdr[MAR_ROWS];
   if (bytes < n) { ctx->err = "ma_ace: the layout came back inconsistent"; return MIA_HIP_ERR_DEVICE; }   // (a record's text holds a newline at least)
   if (n > 0) {
-    if (ctx->ma_ace_cap < bytes) {
-      ctx->ma_ace_cap = 0;
-      if (dev_alloc(ctx, &ctx->d_ace_body, (size_t)bytes)) return MIA_HIP_ERR_NOMEM;
-      ctx->ma_ace_cap = bytes;
-    }
+    if (dev_ensure(ctx, ctx->d_ace_body, bytes)) return MIA_HIP_ERR_NOMEM;
     if (stage_launch(ctx, STG_MA_ACE_RENDER, k_ma_ace_render, dim3((unsigned)((n + MAR_THREADS / 64 - 1) / (MAR_THREADS / 64))), dim3(MAR_THREADS), 0, ctx->stream, v,
                      (const int64_t*)ctx->d_ace_off, ctx->d_ace_body))
       return MIA_HIP_ERR_NOMEM;
@@ -377,6 +347,8 @@ static void build_kmer_lists(const std::string& seq, int k, int soft_mask, std::
 }
 
 // Lets align_all run on a borrowed read set and reference (the anchored part of pass 1) and puts the context back as it was.
+// The lists and the reference are lent through their owners' .p (the blocks come from the pool, the owners' own blocks are put
+// back here): align_all only reads these five, nothing allocates them while they are lent.
 struct AlignBorrow {
   mia_hip_ctx* c;
   ReadSet rs; int32_t *bin_of, *list, *wide, *retry; int max_len; uint8_t* d_ref; int L, wrap, explicit_win, use_filter;
@@ -409,7 +381,7 @@ struct AlignBorrow {
       c->stg[k].pending.clear();
       c->stg[k].ms = stg_ms[k]; c->stg[k].launches = stg_launches[k];
     }
-    c->rs = rs; c->d_bin_of = bin_of; c->d_list = list; c->d_wide_list = wide; c->d_retry_list = retry; c->max_len = max_len; c->d_ref = d_ref;
+    c->rs = rs; c->d_bin_of.p = bin_of; c->d_list.p = list; c->d_wide_list.p = wide; c->d_retry_list.p = retry; c->max_len = max_len; c->d_ref.p = d_ref;
     c->L = L; c->wrap = wrap; c->explicit_win = explicit_win; c->use_filter = use_filter; c->aligned = aligned; c->culled = culled;
     c->tallied = tallied; c->pre_cull_valid = pre_cull_valid; c->ref_mostly_bases = ref_mostly_bases; c->kh_entries = kh_entries; c->diag_scripts_missing = diag_scripts_missing; c->plain_total = plain_total;
     c->plain_retried = plain_retried; c->filter_seen = filter_seen; c->filter_proven = filter_proven;
@@ -671,8 +643,8 @@ extern "C" int mia_hip_pass1(mia_hip_ctx* ctx, const char* ref, int32_t ref_len,
         ReadSet& r = ctx->rs;
         r.n = m; r.packed = d_packed; r.roff = w_roff; r.len = w_len; r.rc = w_rc; r.sk = w_sk; r.as = w_as; r.ae = w_ae; r.score = w_score;
         r.refstart = w_refstart; r.abr = w_abr; r.status = w_status; r.cols = w_cols; r.stride = stride;
-        ctx->d_bin_of = w_bin; ctx->d_list = w_list; ctx->d_wide_list = w_wide; ctx->d_retry_list = w_retry; ctx->max_len = max_len;
-        ctx->d_ref = d_ref2; ctx->L = 2 * len1; ctx->wrap = 2 * len1; ctx->explicit_win = 1; ctx->use_filter = 0;
+        ctx->d_bin_of.p = w_bin; ctx->d_list.p = w_list; ctx->d_wide_list.p = w_wide; ctx->d_retry_list.p = w_retry; ctx->max_len = max_len;
+        ctx->d_ref.p = d_ref2; ctx->L = 2 * len1; ctx->wrap = 2 * len1; ctx->explicit_win = 1; ctx->use_filter = 0;
         ctx->ref_mostly_bases = p1_other * 50 <= L; ctx->kh_entries = wild_entries;
         ctx->wide_to_caller = true;
         rc_inner = align_all(ctx);
@@ -1038,12 +1010,11 @@ extern "C" int mia_hip_measure_peaks(mia_hip_ctx* ctx, int64_t copy_bytes, doubl
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0));
   HIPCHK(hipEventCreate(&e1));
-  void *a = nullptr, *b = nullptr;
-  ScopeFree sf; sf.watch(&a); sf.watch(&b);
+  DevBuf<uint4> a, b;
   int rc = MIA_HIP_OK;
   if (hbm_copy_gbs) {
     const int64_t n16 = copy_bytes / 16;
-    if (hipMalloc(&a, (size_t)n16 * 16) != hipSuccess || hipMalloc(&b, (size_t)n16 * 16) != hipSuccess) { ctx->err = "measure_peaks: hipMalloc"; rc = MIA_HIP_ERR_NOMEM; }
+    if (dev_alloc(ctx, a, n16) || dev_alloc(ctx, b, n16)) rc = MIA_HIP_ERR_NOMEM;
     else {
       HIPCHK(hipMemsetAsync(a, 1, (size_t)n16 * 16, ctx->stream));
       float best = 1e30f;
@@ -1069,9 +1040,9 @@ extern "C" int mia_hip_measure_peaks(mia_hip_ctx* ctx, int64_t copy_bytes, doubl
     }
   }
   if (valu_ginst_s && rc == MIA_HIP_OK) {
-    int32_t* out = nullptr;
+    DevBuf<int32_t> out;
     const int wgs = ctx->cus * 8, iters = 4096;               // 8 waves per SIMD: enough to cover the issue latency
-    if (hipMalloc((void**)&out, (size_t)wgs * 256 * 4) != hipSuccess) { ctx->err = "measure_peaks: hipMalloc"; rc = MIA_HIP_ERR_NOMEM; }
+    if (dev_alloc(ctx, out, (int64_t)wgs * 256)) rc = MIA_HIP_ERR_NOMEM;
     else {
       float best = 1e30f;
       for (int rep = 0; rep < 4; rep++) {
@@ -1082,7 +1053,6 @@ extern "C" int mia_hip_measure_peaks(mia_hip_ctx* ctx, int64_t copy_bytes, doubl
         float ms = 0;
         if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && rep > 0 && ms < best) best = ms;
       }
-      (void)hipFree(out);
       *valu_ginst_s = (double)wgs * 4 * iters * PEAK_VALU_OPS_PER_ITER / (best * 1e-3) / 1e9;   // wave instructions per second
     }
   }
@@ -1096,10 +1066,9 @@ extern "C" int mia_hip_measure_issue(mia_hip_ctx* ctx, double* add_ginst_s, doub
   if (!ctx || (!add_ginst_s && !shader_clock_mhz)) return MIA_HIP_ERR_ARG;
   HIPCHK(hipSetDevice(ctx->device));
   const int wgs = ctx->cus * 8, iters = 4096;
-  int32_t* out = nullptr;
-  unsigned long long* clk = nullptr;
-  ScopeFree sf; sf.watch((void**)&out); sf.watch((void**)&clk);
-  if (hipMalloc((void**)&out, (size_t)wgs * 256 * 4) != hipSuccess || hipMalloc((void**)&clk, (size_t)wgs * 16) != hipSuccess) { ctx->err = "measure_issue: hipMalloc"; return MIA_HIP_ERR_NOMEM; }
+  DevBuf<int32_t> out;
+  DevBuf<unsigned long long> clk;
+  if (dev_alloc(ctx, out, (int64_t)wgs * 256) || dev_alloc(ctx, clk, (int64_t)wgs * 2)) return MIA_HIP_ERR_NOMEM;
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0));
   HIPCHK(hipEventCreate(&e1));
