@@ -331,6 +331,22 @@ int mia_hip_ma_ace(mia_hip_ctx *ctx, int64_t *n_records, int64_t *body_bytes);
  * cap_bytes = bytes body holds.  Any pointer may be NULL. */
 int mia_hip_get_ma_ace(mia_hip_ctx *ctx, int64_t *af_pos, int64_t *padded_len, int64_t *body_off, char *body, int64_t cap_bytes);
 
+/* CIGAR, SEQ and NM of a SAM line (ma_hip -f 8; the reference has no SAM output, the rule is this library's own) for the records of
+ * the last mia_hip_ma_tally, in record order.  ref_seq: the ref_len characters of the reference.  A record of columns start .. end
+ * (n of them) is walked c = 0 .. n-1: first the characters of the insert it has at position c (of several INS_POS pairs of one
+ * position the last one given counts, the string is not cut at gaps; pairs outside 0 .. n-1 are not looked at), then the column's
+ * own character.  An insert character other than '-' goes to SEQ as op I; a column character other than '-' goes to SEQ as op M;
+ * either is op S when start + c >= ref_len (the record of a circular assembly may end on column ref_len); a column's '-' is op D
+ * and no SEQ character, and nothing at all when start + c >= ref_len; an insert's '-' is nothing.  Equal neighbouring ops merge.
+ *   nm    = the D ops + the I ops + the M columns whose character differs from ref_seq[start + c], both upper-cased
+ *   body  = <CIGAR> "\t*\t0\t0\t" <SEQ>: fields 6-10 of the record's line; "*\t*\t0\t0\t*" when the walk yields no SEQ character
+ * body_bytes = the bytes of all bodies.  MIA_HIP_ERR_STATE without a mia_hip_ma_tally before; MIA_HIP_ERR_ARG for ref_seq == NULL
+ * or a negative gap (gaps[0] > 0 is fine here); the context stays usable. */
+int mia_hip_ma_sam(mia_hip_ctx *ctx, const char *ref_seq, int64_t *n_records, int64_t *body_bytes);
+/* nm[n], body_off[n+1] (record r's body is body[body_off[r] .. body_off[r+1])), body[body_bytes]; cap_bytes = bytes body holds.
+ * Any pointer may be NULL. */
+int mia_hip_get_ma_sam(mia_hip_ctx *ctx, int32_t *nm, int64_t *body_off, char *body, int64_t cap_bytes);
+
 /* ---- Myers edit distance -------------------------------------------------- */
 
 /* unsigned myers_diff(const char *seq_a, enum myers_align_mode mode, const char* seq_b, int maxd,
@@ -409,7 +425,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

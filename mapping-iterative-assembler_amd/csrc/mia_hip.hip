@@ -28,14 +28,16 @@
 #include "mia_iter_kernels.h"
 #include "mia_ma_region_kernels.h"
 #include "mia_ma_ace_kernels.h"
+#include "mia_ma_sam_kernels.h"
 
 using namespace mia;
 
 // timed stages (HIP events on the context's stream around the kernel launches of that kind)
-enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_COUNT };
+enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_COUNT };
 static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan",
                                                    "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select",
-                                                   "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render"};
+                                                   "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout",
+                                                   "k_ma_sam_render"};
 
 // One device block for every small counter of an iteration (planner bins and header, filter / band-pipeline counters, link
 // count, cull and tally flags, insert-event count): one memset at the start of the alignment clears them all, and one copy
@@ -247,7 +249,7 @@ struct mia_hip_ctx {
   int64_t trim_escapes = 0;   // reads of the last mia_hip_trim call that took the exact scalar path
   // the records of the last mia_hip_ma_tally stay on the device for mia_hip_ma_region: start, col_off, seq, the INS_POS pairs (and
   // which pairs each record owns), ref->gaps; the region's column map, selected records and text
-  bool ma_resident = false; int64_t ma_n = 0; int32_t ma_L = 0;
+  bool ma_resident = false; int64_t ma_n = 0, ma_n_ins = 0; int32_t ma_L = 0;
   DevBuf<int32_t> d_ma_start, d_ma_gaps, d_ma_ipos, d_ma_rec_ins, d_ma_ins_list;
   DevBuf<int64_t> d_ma_coff, d_ma_ioff, d_ma_colmap, d_ma_rows;
   DevBuf<char> d_ma_seq, d_ma_ib, d_ma_text;
@@ -257,6 +259,11 @@ struct mia_hip_ctx {
   // per record the AF position, the padded length and the offset of its text, the text
   bool ma_ace_gaps_ok = false, ma_ace_cols_ok = false, ma_ace_done = false; int64_t ma_ace_bytes = 0;
   DevBuf<int64_t> d_ace_g, d_ace_af, d_ace_len, d_ace_off; DevBuf<char> d_ace_body;
+  // ... and for mia_hip_ma_sam: whether GAPS is well-formed, the reference, the index of the records' inserts, per record NM, the bytes
+  // of its CIGAR and the offset of its body, the bodies, the layout's control words
+  bool ma_sam_gaps_ok = false, ma_sam_done = false; int64_t ma_sam_bytes = 0;
+  DevBuf<char> d_sam_ref, d_sam_body; DevBuf<int64_t> d_sam_cum, d_sam_cig, d_sam_off; DevBuf<int32_t> d_sam_nm;
+  DevBuf<unsigned long long> d_sam_ctl;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------

@@ -130,6 +130,8 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->ma_ace_done = false;
   ctx->ma_ace_gaps_ok = ma_ace_gaps_ok(gaps, ref_len);
   ctx->ma_ace_cols_ok = cols_ok;
+  ctx->ma_sam_done = false;
+  ctx->ma_sam_gaps_ok = ma_sam_gaps_ok(gaps, ref_len);
   DevBuf<int32_t> d_irec;   // every temporary is released on any return
   DevBuf<uint8_t> d_rev;
   DevBuf<char> d_smp;
@@ -178,6 +180,7 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->consensus_done = false;
   ctx->ma_resident = true;
   ctx->ma_n = n;
+  ctx->ma_n_ins = n_ins;
   ctx->ma_L = ref_len;
   return MIA_HIP_OK;
 }
@@ -284,6 +287,63 @@ extern "C" int mia_hip_get_ma_ace(mia_hip_ctx* ctx, int64_t* af_pos, int64_t* pa
   if (padded_len && n > 0) HIPCHK(hipMemcpyAsync(padded_len, ctx->d_ace_len, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (body_off) HIPCHK(hipMemcpyAsync(body_off, ctx->d_ace_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (body && ctx->ma_ace_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_ace_body, (size_t)ctx->ma_ace_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return MIA_HIP_OK;
+}
+
+// CIGAR, SEQ and NM of the SAM export (ma_hip -f 8) for the records of the last mia_hip_ma_tally: see mia_ma_sam_kernels.h
+extern "C" int mia_hip_ma_sam(mia_hip_ctx* ctx, const char* ref_seq, int64_t* n_records, int64_t* body_bytes) {
+  if (!ctx || !n_records || !body_bytes) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_sam"; return MIA_HIP_ERR_STATE; }
+  if (!ref_seq) { ctx->err = "ma_sam: no reference sequence"; return MIA_HIP_ERR_ARG; }
+  if (!ctx->ma_sam_gaps_ok) { ctx->err = "ma_sam: GAPS holds a negative value"; return MIA_HIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->ma_sam_done = false;
+  const int64_t n = ctx->ma_n;
+  const int32_t L = ctx->ma_L, n_wgs = (int32_t)((n + MAS_PER_WG - 1) / MAS_PER_WG);
+  if (dev_ensure(ctx, ctx->d_sam_ref, (int64_t)L) || dev_ensure(ctx, ctx->d_sam_cum, ctx->ma_n_ins + n + 1) || dev_ensure(ctx, ctx->d_sam_nm, n + 1) ||
+      dev_ensure(ctx, ctx->d_sam_cig, n + 1) || dev_ensure(ctx, ctx->d_sam_off, n + 1) || dev_ensure(ctx, ctx->d_sam_ctl, (int64_t)MAR_STATE + n_wgs + 1))
+    return MIA_HIP_ERR_NOMEM;
+  HIPCHK(hipMemcpyAsync(ctx->d_sam_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+  MaSamView v{n, L, ctx->d_ma_start, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos, ctx->d_ma_ioff, ctx->d_ma_ib,
+              ctx->d_sam_ref, ctx->d_sam_cum};
+  HIPCHK(hipMemsetAsync(ctx->d_sam_ctl, 0, ((size_t)MAR_STATE + (size_t)n_wgs) * 8, ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->d_sam_off, 0, 8, ctx->stream));         // (no records: the one offset there is)
+  if (n_wgs > 0) {
+    if (stage_launch(ctx, STG_MA_SAM_LAYOUT, k_ma_sam_layout, dim3((unsigned)n_wgs), dim3(MAS_THREADS), 0, ctx->stream, v, n_wgs, ctx->d_sam_ctl, ctx->d_sam_nm,
+                     ctx->d_sam_cig, ctx->d_sam_off))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+  }
+  unsigned long long hdr[MAR_STATE] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(hdr, ctx->d_sam_ctl, sizeof hdr, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const int64_t bytes = (int64_t)hdr[MAR_ROWS];
+  if (bytes < n * MA_SAM_EMPTY_BYTES) { ctx->err = "ma_sam: the layout came back inconsistent"; return MIA_HIP_ERR_DEVICE; }   // (no body is shorter than that of a record without SEQ)
+  if (n > 0) {
+    if (dev_ensure(ctx, ctx->d_sam_body, bytes)) return MIA_HIP_ERR_NOMEM;
+    if (stage_launch(ctx, STG_MA_SAM_RENDER, k_ma_sam_render, dim3((unsigned)((n + MAS_WAVES - 1) / MAS_WAVES)), dim3(MAS_THREADS), 0, ctx->stream, v,
+                     (const int64_t*)ctx->d_sam_cig, (const int64_t*)ctx->d_sam_off, ctx->d_sam_body))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  ctx->ma_sam_bytes = bytes;
+  ctx->ma_sam_done = true;
+  *n_records = n;
+  *body_bytes = bytes;
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_sam(mia_hip_ctx* ctx, int32_t* nm, int64_t* body_off, char* body, int64_t cap_bytes) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident || !ctx->ma_sam_done) { ctx->err = "ma_sam first"; return MIA_HIP_ERR_STATE; }
+  if (body && cap_bytes < ctx->ma_sam_bytes) { ctx->err = "get_ma_sam: buffer too small"; return MIA_HIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t n = ctx->ma_n;
+  if (nm && n > 0) HIPCHK(hipMemcpyAsync(nm, ctx->d_sam_nm, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (body_off) HIPCHK(hipMemcpyAsync(body_off, ctx->d_sam_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (body && ctx->ma_sam_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_sam_body, (size_t)ctx->ma_sam_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }

@@ -1,8 +1,9 @@
 // ma_hip -- the reference's `ma` report tool (/root/reference/src/map_assembler.c): -f 1 (clustalw, the default), -f 2 (line
 // format), -f 5 (assembled sequence as FASTA), -f 41 and -f 4 (per-column table), -f 6 and -f 61 (the fragments of a region,
-// -R), -f 7 (ACE export, every record in full) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
+// -R), -f 7 (ACE export, every record in full), -f 8 (SAM, which the reference does not have: the reads as aligned to the reference) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
 // find_ins_cons run on the GPU (mia_hip_ma_tally, every record counts, dropped or not), and so do the selection and the
-// rows of the region view (mia_hip_ma_region) and the padded reads of the ACE export (mia_hip_ma_ace); calling, phred score and
+// rows of the region view (mia_hip_ma_region), the padded reads of the ACE export (mia_hip_ma_ace) and CIGAR, SEQ and NM of the SAM
+// export (mia_hip_ma_sam); calling, phred score and
 // printing follow src/map_alignment.c:107-220, src/map_align.c:152-227,294-391,543-759 and src/io.c:756-913,929-1085.  Format 3
 // (show_consensus walks every record per column on the host and prints per-record lines no kernel here produces) stays outside.
 // No CPU fallback.
@@ -23,6 +24,7 @@
 #include "../../include/mia_hip.h"
 #include "maln_text.h"
 #include "../csrc/ma_ace_body.h"
+#include "../csrc/ma_sam_body.h"
 
 namespace {
 
@@ -31,14 +33,15 @@ using namespace maln_text;
 typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6, 61 or 7>\n   -R <REGION_START:REGION_END>\n"
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6, 61, 7 or 8>\n   -R <REGION_START:REGION_END>\n"
          "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
          "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
          "(-f 1 clustalw, the default; -f 2 one line each plus coverage), the per-column table (-f 41 all positions, -f 4\n"
          "positions that differ from the reference), the assembled sequence (-f 5), and the reference, the consensus and every\n"
          "fragment of a region (-f 6, as multi-FASTA -f 61; -R, default 90:109).  Tallies, the selection of the fragments and\n"
          "their rows are computed on the MI355X, and so are the padded reads of the ACE export (-f 7).  -m writes the .maln\n"
-         "again: records sorted, -c and -I applied.  Format 3 is outside the accelerated path.\n");
+         "again: records sorted, -c and -I applied.  -f 8 writes the records as SAM (one line each, aligned to the reference;\n"
+         "CIGAR, SEQ and NM come from the MI355X; the reference's ma has no such format).  Format 3 is outside the accelerated path.\n");
 }
 
 void read_ma(const char* fn, Maln* m) { read_maln_file(fn, m); }
@@ -188,6 +191,24 @@ void ace_print(const Maln& m, const std::string& cons, const std::vector<int64_t
   o.flush();
 }
 
+// SAM (-f 8): header, and per record everything in front of and behind the body the device made (fields 6-10)
+void sam_print(const Maln& m, const std::vector<int32_t>& nm, const std::vector<int64_t>& body_off, const std::string& body) {
+  Out o;
+  o.buf += "@HD\tVN:1.6\tSO:coordinate\n@SQ\tSN:" + m.ref_id;
+  o.fmt("\tLN:%d\n@PG\tID:ma_hip\tPN:ma_hip\n", m.L);
+  for (size_t r = 0; r < m.rec.size(); r++) {
+    const MalnRecord& a = m.rec[r];
+    o.buf += a.id;
+    o.fmt("\t%d\t", (a.rc ? 16 : 0) + (a.dropped ? 512 : 0) + (a.segment == 'b' ? 2048 : 0));
+    o.buf += m.ref_id;
+    o.fmt("\t%d\t255\t", a.start + 1);
+    o.buf.append(body, (size_t)body_off[r], (size_t)(body_off[r + 1] - body_off[r]));
+    o.fmt("\t*\tAS:i:%d\tNM:i:%d\tXN:i:%d\tXS:A:%c\tXT:i:%d\n", a.score, nm[r], a.num_inputs, a.segment, a.trimmed ? 1 : 0);
+    o.room();
+  }
+  o.flush();
+}
+
 void die(mia_hip_ctx* g, const char* what) {
   fprintf(stderr, "%s: %s\n", what, g ? mia_hip_last_error(g) : "no context");
   exit(1);
@@ -221,13 +242,17 @@ int main(int argc, char* argv[]) {
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61 && out_format != 7) {
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8) {
     fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are); use the reference's ma\n", out_format);
     exit(1);
   }
   Maln m;
   read_ma(ma_in_fn.c_str(), &m);
   if (id_assigned) m.ref_id = assign_id.substr(0, 256);
+  if (out_format == 8 && !mia::ma_sam_gaps_ok(m.gaps.data(), m.L)) {
+    fprintf(stderr, "ma_hip: %s has no SAM export: its GAPS line holds a negative value\n", ma_in_fn.c_str());
+    exit(1);
+  }
   if (out_format == 7 && !mia::ma_ace_gaps_ok(m.gaps.data(), m.L)) {
     fprintf(stderr, "ma_hip: %s has no ACE export: its GAPS line opens insert columns in front of column 0 or holds a negative value\n", ma_in_fn.c_str());
     exit(1);
@@ -247,6 +272,17 @@ int main(int argc, char* argv[]) {
                        m.ins_record.data(), m.ins_pos.data(), m.ins_off.data(), m.ins_bases.data()) != MIA_HIP_OK)
     die(g, "ma_tally");
   const int L = m.L;
+  if (out_format == 8) {
+    int64_t n_rec = 0, body_bytes = 0;
+    if (mia_hip_ma_sam(g, m.ref_seq.data(), &n_rec, &body_bytes) != MIA_HIP_OK) die(g, "ma_sam");
+    if (n_rec != n) { fprintf(stderr, "ma_hip: the export holds %lld records, the file %lld\n", (long long)n_rec, (long long)n); exit(1); }
+    std::vector<int32_t> nm((size_t)n_rec + 1);
+    std::vector<int64_t> body_off((size_t)n_rec + 1);
+    std::string body((size_t)body_bytes + 1, '\0');
+    if (mia_hip_get_ma_sam(g, nm.data(), body_off.data(), &body[0], body_bytes) != MIA_HIP_OK) die(g, "get_ma_sam");
+    sam_print(m, nm, body_off, body);
+    return finish(g);
+  }
   if (out_format == 5) {
     // fasta_print_cons of the called columns (src/io.c:929-951); '-' calls are not printed
     int64_t total_gaps = 0;
