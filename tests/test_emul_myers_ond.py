@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import myers_ref
 from conftest import GOLDEN, ROOT
 
 
@@ -61,32 +62,11 @@ def test_cap_below_the_distance_hands_the_pair_on(emu):
     assert seen[0] > 50
 
 
-def _host_distance(a, b, mode):
-    """plain dynamic programme over bitmaps (D[i][0] = i, D[0][j] = j)"""
-    bits = {c: v for c, v in zip(b"ACGTUSWRYKMBDHVN", [1, 2, 4, 8, 8, 6, 9, 5, 10, 12, 3, 14, 13, 11, 7, 15])}
-    A = np.array([bits.get(c & ~32, 0) for c in a], np.int64)
-    Bv = [bits.get(c & ~32, 0) for c in b]
-    col = np.arange(len(a) + 1)
-    best_last_row = col[-1]
-    for j, bj in enumerate(Bv, 1):
-        new = np.empty_like(col)
-        new[0] = j
-        sub = col[:-1] + ((A & bj) == 0)
-        up = col[1:] + 1
-        m = np.minimum(sub, up)
-        # the in-column dependency new[i] = min(m[i-1], new[i-1] + 1): a running minimum of (m - i) + i
-        run = np.minimum.accumulate(np.concatenate(([new[0]], m)) - np.arange(len(a) + 1)) + np.arange(len(a) + 1)
-        col = run
-        best_last_row = min(best_last_row, col[-1])
-    return int(col[-1]) if mode == 0 else int(col.min()) if mode == 1 else int(best_last_row)
-
-
-def test_long_pairs_against_a_plain_dp(emu):
-    """pairs of a few thousand characters (snakes of hundreds of characters, word-unaligned starts on both sides, IUPAC codes,
-    characters no bitmap knows): the distance against a plain O(len^2) programme, the rows against the distance"""
+def long_pairs():
+    """(mode, seq_a, seq_b) of test_long_pairs_against_a_plain_dp: pairs of a few thousand characters, up to forty edits"""
     rng = np.random.default_rng(5)
     alpha = np.frombuffer(b"ACGTACGTACGTACGTNRYKMSWBDHVX", np.uint8)
-    bits = {c: v for c, v in zip(b"ACGTUSWRYKMBDHVN", [1, 2, 4, 8, 8, 6, 9, 5, 10, 12, 3, 14, 13, 11, 7, 15])}
+    out = []
     for it in range(24):
         la = int(rng.integers(300, 3000))
         a = alpha[rng.integers(0, 16 if it % 2 else len(alpha), la)].copy()
@@ -105,8 +85,19 @@ def test_long_pairs_against_a_plain_dp(emu):
             a = np.concatenate([a, alpha[rng.integers(0, 16, 50)]])      # seq_b a prefix of seq_a
         if mode == 2:
             b = b + list(alpha[rng.integers(0, 16, 50)])                 # seq_a a prefix of seq_b
-        a, b = bytes(a), bytes(np.array(b, np.uint8))
-        want = _host_distance(a, b, mode)
+        out.append((mode, bytes(a), bytes(np.array(b, np.uint8))))
+    return out
+
+
+def test_long_pairs_against_a_plain_dp(emu):
+    """pairs of a few thousand characters (snakes of hundreds of characters, word-unaligned starts on both sides, IUPAC codes,
+    characters no bitmap knows): the distance against a plain O(len^2) programme (tests/myers_ref.py), the rows against the
+    distance"""
+    bits = {c: v for c, v in zip(b"ACGTUSWRYKMBDHVN", [1, 2, 4, 8, 8, 6, 9, 5, 10, 12, 3, 14, 13, 11, 7, 15])}
+    pairs = long_pairs()
+    wants = myers_ref.myers_distance([a for _, a, _ in pairs], [b for _, _, b in pairs], [m for m, _, _ in pairs])
+    for it, (mode, a, b) in enumerate(pairs):
+        want = int(wants[it])
         d, ra, rb = run(emu, a, mode, b, 100000, 1 << 20)
         assert d == want, (it, mode, len(a), len(b))
         if len(ra) == len(rb):
