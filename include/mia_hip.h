@@ -347,6 +347,27 @@ int mia_hip_ma_sam(mia_hip_ctx *ctx, const char *ref_seq, int64_t *n_records, in
  * Any pointer may be NULL. */
 int mia_hip_get_ma_sam(mia_hip_ctx *ctx, int32_t *nm, int64_t *body_off, char *body, int64_t cap_bytes);
 
+/* The substitution profile of the records of the last mia_hip_ma_tally (ma_hip -f 9, -f 91; the reference has no such report, the
+ * rule is this library's own).  ref_seq: the ref_len characters of the reference.  use: n bytes, 0 = the record is left out; NULL =
+ * every record counts.  Every column c = 0 .. n-1 of a record that counts is one event, on reference column p = start + c, with depth
+ * code d = smp[c] - 'A':
+ *   p >= ref_len (the record of a circular assembly may end on column ref_len)   -> beyond, and nowhere else
+ *   d outside 0 .. 30                                                            -> bad_code, and nowhere else
+ *   seq[c] == '-'                                                                -> del[d']
+ *   else                                                                         -> count[d'][i'][j']
+ * i, j = the class of toupper(ref_seq[p]) and of toupper(seq[c]): A, C, G, T -> 0 .. 3, anything else -> 4.  A record stored reverse-
+ * complemented is scored with RPSM[d][i][j] = FPSM[30-d][3-i][3-j], so for it d' = 30 - d, i' = 3 - i (4 stays 4), j' likewise; else
+ * d' = d, i' = i, j' = j.  INS_POS pairs are not looked at.  The counts are exact and do not depend on the order of the records.
+ * (mia_hip_ma_tally itself refuses a depth code outside 0 .. 30 on a column that holds a base or an INS_POS pair: behind a tally
+ * that succeeded bad_code counts '-' columns only.)
+ *   n_used   = the records that count;  n_events = their columns = sum(count) + sum(del) + bad_code + beyond.  Either may be NULL.
+ * MIA_HIP_ERR_STATE without a mia_hip_ma_tally before; MIA_HIP_ERR_ARG for ref_seq == NULL (and for records that were tallied with
+ * col_off[0] != 0); the context stays usable. */
+int mia_hip_ma_profile(mia_hip_ctx *ctx, const char *ref_seq, const uint8_t *use, int64_t *n_used, int64_t *n_events);
+/* count[31 * 5 * 5] ([d][ref class][read class]), del[31], *bad_code, *beyond of the last mia_hip_ma_profile.  Any pointer may be
+ * NULL.  MIA_HIP_ERR_STATE without a mia_hip_ma_profile since the last mia_hip_ma_tally. */
+int mia_hip_get_ma_profile(mia_hip_ctx *ctx, int64_t *count, int64_t *del, int64_t *bad_code, int64_t *beyond);
+
 /* ---- Myers edit distance -------------------------------------------------- */
 
 /* unsigned myers_diff(const char *seq_a, enum myers_align_mode mode, const char* seq_b, int maxd,
@@ -425,7 +446,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_profile, k_ma_tally), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

@@ -102,6 +102,9 @@ def _load(path=None):
     if hasattr(lib, "mia_hip_ma_sam"):
         lib.mia_hip_ma_sam.argtypes = [vp, vp, P(C.c_int64), P(C.c_int64)]
         lib.mia_hip_get_ma_sam.argtypes = [vp, vp, vp, vp, C.c_int64]
+    if hasattr(lib, "mia_hip_ma_profile"):
+        lib.mia_hip_ma_profile.argtypes = [vp, vp, vp, P(C.c_int64), P(C.c_int64)]
+        lib.mia_hip_get_ma_profile.argtypes = [vp, vp, vp, P(C.c_int64), P(C.c_int64)]
     lib.mia_hip_kernel_time.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_int64)]
     lib.mia_hip_stage_stats.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp, P(C.c_int32)]
     lib.mia_hip_set_stage_mask.argtypes = [vp, C.c_uint32]
@@ -146,7 +149,7 @@ def exported_symbols():
             "mia_hip_upload_reads", "mia_hip_pass1", "mia_hip_realign", "mia_hip_align_windows", "mia_hip_get_alignments", "mia_hip_get_scripts", "mia_hip_cull",
             "mia_hip_get_dropped", "mia_hip_set_slot_dropped", "mia_hip_score_cut", "mia_hip_num_records",
             "mia_hip_tally", "mia_hip_tally_buffers", "mia_hip_ins_events", "mia_hip_set_ins_events",
-            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
+            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
             "mia_hip_get_record_params", "mia_hip_set_read_base", "mia_hip_links", "mia_hip_set_links", "mia_hip_link_lengths",
             "mia_hip_finish_links", "mia_hip_plain_stats", "mia_hip_score_sums",
             "mia_hip_score_cut_from_sums", "mia_hip_stage_stats", "mia_hip_measure_peaks", "mia_hip_measure_issue", "mia_hip_set_tally", "mia_hip_iterate", "mia_hip_set_stage_mask", "mia_hip_comm_unique_id", "mia_hip_comm_init", "mia_hip_comm_destroy",
@@ -555,7 +558,7 @@ class MiaHip:
         self._chk(self._l.mia_hip_stage_stats(self._h, 1 if reset else 0, cap, names, ms, k, C.byref(n)))
         return {names[i].decode(): (ms[i], k[i]) for i in range(min(n.value, cap))}
 
-    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout", "k_ma_sam_render"]
+    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_profile", "k_ma_tally"]
 
     def comm_init(self, unique_id, n_ranks, rank):
         """attach an RCCL communicator (ncclCommInitRank on this context's GPU); unique_id: the 128 bytes of comm_unique_id()
@@ -648,6 +651,23 @@ class MiaHip:
         body = np.empty(b.value, dtype=np.uint8)
         self._chk(self._l.mia_hip_get_ma_sam(self._h, _ptr(nm) if n.value else None, _ptr(off), _ptr(body) if body.size else None, b.value))
         return nm, off, body
+
+    def ma_profile(self, ref_seq, use=None):
+        """the substitution profile (ma_hip -f 9, -f 91) over the records of the last ma_tally; ref_seq: the reference's characters
+        (str or bytes, ref_len of them); use: per record 0 = left out (None: every record counts).  (count[31, 5, 5], del[31],
+        bad_code, beyond): count[d, i, j] = columns at depth code d with reference class i and read class j (A, C, G, T, other), a
+        reverse-complemented record mirrored to its read's orientation; del[d] = '-' columns; bad_code = columns whose depth code is
+        outside 0 .. 30; beyond = columns behind the reference's last.  numpy int64 and ints."""
+        ref = ref_seq.encode("latin1") if isinstance(ref_seq, str) else bytes(ref_seq)
+        if len(ref) != self.L:
+            raise ValueError("ma_profile: the reference has %d characters, the tallied job %d columns" % (len(ref), self.L))
+        if use is not None:
+            use = np.ascontiguousarray(use, dtype=np.uint8)
+        count, dele = np.zeros((31, 5, 5), dtype=np.int64), np.zeros(31, dtype=np.int64)
+        bad, beyond = C.c_int64(), C.c_int64()
+        self._chk(self._l.mia_hip_ma_profile(self._h, C.c_char_p(ref), _ptr(use) if use is not None and use.size else None, None, None))
+        self._chk(self._l.mia_hip_get_ma_profile(self._h, _ptr(count), _ptr(dele), C.byref(bad), C.byref(beyond)))
+        return count, dele, bad.value, beyond.value
 
     def ins_tally(self):
         """(ins_off[L+1], ins_tally[slots][9]) of the insert columns, after consensus()."""

@@ -124,7 +124,8 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
       ma_ace_order_inserts(ins_list.data() + rec_ins[(size_t)r], rec_ins[(size_t)r + 1] - rec_ins[(size_t)r], ins_pos);
   }
   // The records stay on the device behind this call (mia_hip_ma_region reads them): buffers of the context, made here, before anything
-  // is queued.  Strand, depth codes and the pairs' record numbers are needed by the tally alone.
+  // is queued.  Strand and depth codes stay for mia_hip_ma_profile; the pairs' record numbers are needed by the tally alone.  SEQ and
+  // SMP are readable up to the next multiple of MA_PROF_LANE behind their last character (k_ma_profile loads them in words of that size).
   ctx->ma_resident = false;
   ctx->ma_region_done = false;
   ctx->ma_ace_done = false;
@@ -132,11 +133,10 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->ma_ace_cols_ok = cols_ok;
   ctx->ma_sam_done = false;
   ctx->ma_sam_gaps_ok = ma_sam_gaps_ok(gaps, ref_len);
+  ctx->ma_prof_done = false;
   DevBuf<int32_t> d_irec;   // every temporary is released on any return
-  DevBuf<uint8_t> d_rev;
-  DevBuf<char> d_smp;
-  int rcx = dev_alloc(ctx, ctx->d_ma_start, n + 1) | dev_alloc(ctx, d_rev, n + 1) | dev_alloc(ctx, ctx->d_ma_coff, n + 1) |
-            dev_alloc(ctx, ctx->d_ma_seq, chars + 1) | dev_alloc(ctx, d_smp, chars + 1) | dev_alloc(ctx, d_irec, n_ins + 1) |
+  int rcx = dev_alloc(ctx, ctx->d_ma_start, n + 1) | dev_alloc(ctx, ctx->d_ma_rev, n + 1) | dev_alloc(ctx, ctx->d_ma_coff, n + 1) |
+            dev_alloc(ctx, ctx->d_ma_seq, chars + MA_PROF_LANE) | dev_alloc(ctx, ctx->d_ma_smp, chars + MA_PROF_LANE) | dev_alloc(ctx, d_irec, n_ins + 1) |
             dev_alloc(ctx, ctx->d_ma_ipos, n_ins + 1) | dev_alloc(ctx, ctx->d_ma_ioff, n_ins + 1) |
             dev_alloc(ctx, ctx->d_ma_ib, ins_chars + 1) | dev_alloc(ctx, ctx->d_ma_gaps, ref_len) |
             dev_alloc(ctx, ctx->d_ma_rec_ins, n + 1) | dev_alloc(ctx, ctx->d_ma_ins_list, n_ins + 1) |
@@ -146,6 +146,7 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   int32_t* const d_start = ctx->d_ma_start; int32_t* const d_ipos = ctx->d_ma_ipos;
   int64_t* const d_coff = ctx->d_ma_coff; int64_t* const d_ioff = ctx->d_ma_ioff;
   char* const d_seq = ctx->d_ma_seq; char* const d_ib = ctx->d_ma_ib;
+  uint8_t* const d_rev = ctx->d_ma_rev; char* const d_smp = ctx->d_ma_smp;
   hipError_t e = hipSuccess;
   auto up = [&](void* d, const void* h, size_t b) { if (e == hipSuccess && b) e = hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream); };
   auto zero = [&](void* d, size_t b) { if (e == hipSuccess) e = hipMemsetAsync(d, 0, b, ctx->stream); };
@@ -162,7 +163,8 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   up(ctx->d_ma_ins_list, ins_list.data(), (size_t)n_ins * 4);
   if (e == hipSuccess && n > 0) {
     MaRecords mr{n, d_start, d_rev, d_coff, d_seq, d_smp};
-    hipLaunchKernelGGL(k_ma_tally, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, mr, ctx->d_pssm, ctx->tb);
+    if (stage_launch(ctx, STG_MA_TALLY, k_ma_tally, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, mr, (const int32_t*)ctx->d_pssm, ctx->tb))
+      return MIA_HIP_ERR_NOMEM;
     if (n_ins > 0)
       hipLaunchKernelGGL(k_ma_ins_events, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, ctx->stream, mr, n_ins, d_irec, d_ipos, d_ioff,
                          d_ib, ctx->tb);
@@ -182,6 +184,7 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->ma_n = n;
   ctx->ma_n_ins = n_ins;
   ctx->ma_L = ref_len;
+  ctx->ma_cols = n == 0 ? 0 : col_off[0] == 0 ? chars : -1;         // (mia_hip_ma_profile takes flat position 0 as record 0's first column)
   return MIA_HIP_OK;
 }
 
@@ -345,6 +348,52 @@ extern "C" int mia_hip_get_ma_sam(mia_hip_ctx* ctx, int32_t* nm, int64_t* body_o
   if (body_off) HIPCHK(hipMemcpyAsync(body_off, ctx->d_sam_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (body && ctx->ma_sam_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_sam_body, (size_t)ctx->ma_sam_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
+  return MIA_HIP_OK;
+}
+
+// The substitution profile (ma_hip -f 9, -f 91) of the records of the last mia_hip_ma_tally: see mia_ma_profile_kernels.h
+extern "C" int mia_hip_ma_profile(mia_hip_ctx* ctx, const char* ref_seq, const uint8_t* use, int64_t* n_used, int64_t* n_events) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_profile"; return MIA_HIP_ERR_STATE; }
+  if (!ref_seq) { ctx->err = "ma_profile: no reference sequence"; return MIA_HIP_ERR_ARG; }
+  if (ctx->ma_n > 0 && ctx->ma_cols < 0) { ctx->err = "ma_profile: col_off[0] of the tallied records is not 0"; return MIA_HIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->ma_prof_done = false;
+  const int64_t n = ctx->ma_n, T = ctx->ma_cols;
+  const int32_t L = ctx->ma_L;
+  if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, ctx->d_prof_use, n + 1) || dev_ensure(ctx, ctx->d_prof_bins, MA_PROF_BINS))
+    return MIA_HIP_ERR_NOMEM;
+  HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+  if (use && n > 0) HIPCHK(hipMemcpyAsync(ctx->d_prof_use, use, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->d_prof_bins, 0, (size_t)MA_PROF_BINS * 8, ctx->stream));
+  if (n > 0) {                                              // (records that all lack columns: one workgroup that finds no chunk)
+    MaProfView v{n, T, L, ctx->d_ma_start, ctx->d_ma_rev, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_smp, ctx->d_prof_ref, use ? (const uint8_t*)ctx->d_prof_use : nullptr};
+    // persistent grid: the workgroups that are resident at once, or one per chunk when there are fewer chunks
+    int64_t grid = (int64_t)ctx->cus * MAP_WGS_PER_CU;
+    if (grid > ma_prof_chunks(T)) grid = ma_prof_chunks(T);
+    if (grid < 1) grid = 1;
+    if (stage_launch(ctx, STG_MA_PROFILE, k_ma_profile, dim3((unsigned)grid), dim3(MAP_THREADS), 0, ctx->stream, v, (unsigned long long*)ctx->d_prof_bins))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(ctx->ma_prof_bins, ctx->d_prof_bins, (size_t)MA_PROF_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  int64_t events = 0, used = 0;
+  for (int b = 0; b < MA_PROF_BINS; b++) events += ctx->ma_prof_bins[b];
+  for (int64_t r = 0; r < n; r++) used += !use || use[r] ? 1 : 0;
+  ctx->ma_prof_done = true;
+  if (n_used) *n_used = used;
+  if (n_events) *n_events = events;
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_profile(mia_hip_ctx* ctx, int64_t* count, int64_t* del, int64_t* bad_code, int64_t* beyond) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident || !ctx->ma_prof_done) { ctx->err = "ma_profile first"; return MIA_HIP_ERR_STATE; }
+  if (count) memcpy(count, ctx->ma_prof_bins, sizeof(int64_t) * MA_PROF_COUNTS);
+  if (del) memcpy(del, ctx->ma_prof_bins + MA_PROF_DEL, sizeof(int64_t) * MA_PROF_DEPTHS);
+  if (bad_code) *bad_code = ctx->ma_prof_bins[MA_PROF_BAD];
+  if (beyond) *beyond = ctx->ma_prof_bins[MA_PROF_BEYOND];
   return MIA_HIP_OK;
 }
 

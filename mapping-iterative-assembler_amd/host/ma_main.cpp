@@ -1,11 +1,14 @@
 // ma_hip -- the reference's `ma` report tool (/root/reference/src/map_assembler.c): -f 1 (clustalw, the default), -f 2 (line
 // format), -f 5 (assembled sequence as FASTA), -f 41 and -f 4 (per-column table), -f 6 and -f 61 (the fragments of a region,
-// -R), -f 7 (ACE export, every record in full), -f 8 (SAM, which the reference does not have: the reads as aligned to the reference) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
+// -R), -f 7 (ACE export, every record in full), -f 8 (SAM, which the reference does not have: the reads as aligned to the reference), -f 9 and -f 91 (the substitution profile of the
+// assembly, which the reference does not have either: substitution counts by distance from the read's ends, and a -s matrix made
+// from them; -P pseudocount, -A dropped records too) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
 // find_ins_cons run on the GPU (mia_hip_ma_tally, every record counts, dropped or not), and so do the selection and the
 // rows of the region view (mia_hip_ma_region), the padded reads of the ACE export (mia_hip_ma_ace) and CIGAR, SEQ and NM of the SAM
-// export (mia_hip_ma_sam); calling, phred score and
+// export (mia_hip_ma_sam) and the counts of the substitution profile (mia_hip_ma_profile); calling, phred score and
 // printing follow src/map_alignment.c:107-220, src/map_align.c:152-227,294-391,543-759 and src/io.c:756-913,929-1085.  Format 3
-// (show_consensus walks every record per column on the host and prints per-record lines no kernel here produces) stays outside.
+// (the summary of format 2 plus a table per column: coverage, and the records that start and that end there on either strand,
+// src/map_align.c:761-849, src/map_alignment.c:635-653 -- counts no kernel here produces) stays outside.
 // No CPU fallback.
 #include <ctype.h>
 #include <float.h>
@@ -25,6 +28,7 @@
 #include "maln_text.h"
 #include "../csrc/ma_ace_body.h"
 #include "../csrc/ma_sam_body.h"
+#include "../csrc/ma_profile_body.h"
 
 namespace {
 
@@ -33,15 +37,22 @@ using namespace maln_text;
 typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6, 61, 7 or 8>\n   -R <REGION_START:REGION_END>\n"
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6, 61, 7, 8, 9 or 91>\n   -R <REGION_START:REGION_END>\n"
          "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
+         "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 9 and 91)\n"
          "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
          "(-f 1 clustalw, the default; -f 2 one line each plus coverage), the per-column table (-f 41 all positions, -f 4\n"
          "positions that differ from the reference), the assembled sequence (-f 5), and the reference, the consensus and every\n"
          "fragment of a region (-f 6, as multi-FASTA -f 61; -R, default 90:109).  Tallies, the selection of the fragments and\n"
          "their rows are computed on the MI355X, and so are the padded reads of the ACE export (-f 7).  -m writes the .maln\n"
          "again: records sorted, -c and -I applied.  -f 8 writes the records as SAM (one line each, aligned to the reference;\n"
-         "CIGAR, SEQ and NM come from the MI355X; the reference's ma has no such format).  Format 3 is outside the accelerated path.\n");
+         "CIGAR, SEQ and NM come from the MI355X; the reference's ma has no such format).  -f 9 prints the substitution profile of\n"
+         "the assembly: per distance from the read's 5' end (1..15), MIDDLE and distance from its 3' end (-15..-1) how often a\n"
+         "reference base was read as which base, the deletions, and the columns with an N or another code (C>T at the first\n"
+         "and G>A at the last positions is the damage of ancient DNA); -f 91 prints a substitution matrix made from these counts,\n"
+         "a file for mia -s (100 * log2 of the share of each read base per reference base over 0.25, -P added to every count).\n"
+         "Dropped records do not count unless -A is given; the counts come from the MI355X.  Format 3 (format 2's summary plus\n"
+         "a table of coverage and of the records that start and end at every column) is outside the accelerated path.\n");
 }
 
 void read_ma(const char* fn, Maln* m) { read_maln_file(fn, m); }
@@ -209,6 +220,45 @@ void sam_print(const Maln& m, const std::vector<int32_t>& nm, const std::vector<
   o.flush();
 }
 
+// -f 9: the counts as a table, a line per depth code
+void profile_table(int64_t n_used, int64_t n_events, const int64_t* count, const int64_t* del, int64_t bad_code, int64_t beyond) {
+  Out o;
+  o.fmt("# ma_hip substitution profile: %lld records, %lld columns, %lld bad depth codes, %lld columns beyond the reference\n", (long long)n_used,
+        (long long)n_events, (long long)bad_code, (long long)beyond);
+  o.buf += "# position";
+  for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) o.fmt("\t%c>%c", "ACGT"[i], "ACGT"[j]);
+  o.buf += "\tdel\tother\n";
+  for (int d = 0; d < mia::MA_PROF_DEPTHS; d++) {
+    char label[16];
+    mia::ma_prof_label(d, label);
+    o.buf += label;
+    const int64_t* c = count + d * 25;
+    int64_t other = 0;
+    for (int i = 0; i < 5; i++) for (int j = 0; j < 5; j++) {
+      if (i < 4 && j < 4) o.fmt("\t%lld", (long long)c[i * 5 + j]); else other += c[i * 5 + j];
+    }
+    o.fmt("\t%lld\t%lld\n", (long long)del[d], (long long)other);
+  }
+  o.flush();
+}
+
+// -f 91: the counts as a matrix file in the layout of matrices/ancient.submat.txt, which read_pssm (src/io.c:408-503) reads
+void profile_matrix(const int64_t* count, double alpha) {
+  Out o;
+  for (int d = 0; d < mia::MA_PROF_DEPTHS; d++) {
+    char label[16];
+    mia::ma_prof_label(d, label);
+    o.fmt("# Matrix for position: %s\n", label);
+    for (int i = 0; i < 4; i++) {
+      const int64_t* c = count + (d * 5 + i) * 5;
+      for (int j = 0; j < 4; j++) o.fmt("%d\t", mia::ma_prof_score(c, i, j, alpha));
+      o.buf += '\n';
+    }
+    o.buf += '\n';
+  }
+  o.flush();
+}
+
 void die(mia_hip_ctx* g, const char* what) {
   fprintf(stderr, "%s: %s\n", what, g ? mia_hip_last_error(g) : "no context");
   exit(1);
@@ -220,11 +270,11 @@ int main(int argc, char* argv[]) {
   std::string ma_in_fn, assign_id, ma_out_fn;
   bool id_assigned = false, in_ma = false, any_arg = false, out_ma = false;
   int cons_scheme = 1, out_format = 1, gpu = 0, reg_start = 90, reg_end = 109;
-  bool in_color = false;
-  double score_int = -1.0, score_slo = -1.0;
+  bool in_color = false, use_dropped = false;
+  double score_int = -1.0, score_slo = -1.0, alpha = 1.0;
   int ich;
-  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>
-  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:")) != -1) {
+  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount> and -A
+  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:A")) != -1) {
     switch (ich) {
       case 'I': assign_id = optarg; id_assigned = true; break;
       case 'c': cons_scheme = atoi(optarg); any_arg = true; break;
@@ -238,12 +288,18 @@ int main(int argc, char* argv[]) {
       case 'M': ma_in_fn = optarg; in_ma = true; any_arg = true; break;
       case 'd': any_arg = true; break;
       case 'g': gpu = atoi(optarg); break;
+      case 'P': { char* end = nullptr; alpha = strtod(optarg, &end); if (end == optarg || *end) alpha = NAN; } break;
+      case 'A': use_dropped = true; break;
       default: help(); exit(0);
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8) {
-    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are); use the reference's ma\n", out_format);
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91) {
+    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 8, 9 and 91, which the reference does not have); use the reference's ma\n", out_format);
+    exit(1);
+  }
+  if (out_format == 91 && !mia::ma_prof_alpha_ok(alpha)) {
+    fprintf(stderr, "ma_hip: -P must be a number from %g to %g\n", mia::MA_PROF_MIN_ALPHA, mia::MA_PROF_MAX_ALPHA);
     exit(1);
   }
   Maln m;
@@ -281,6 +337,17 @@ int main(int argc, char* argv[]) {
     std::string body((size_t)body_bytes + 1, '\0');
     if (mia_hip_get_ma_sam(g, nm.data(), body_off.data(), &body[0], body_bytes) != MIA_HIP_OK) die(g, "get_ma_sam");
     sam_print(m, nm, body_off, body);
+    return finish(g);
+  }
+  if (out_format == 9 || out_format == 91) {
+    std::vector<uint8_t> use((size_t)n + 1, 1);
+    for (int64_t r = 0; r < n; r++) use[(size_t)r] = use_dropped || !m.rec[(size_t)r].dropped ? 1 : 0;
+    int64_t n_used = 0, n_events = 0, bad_code = 0, beyond = 0;
+    std::vector<int64_t> count((size_t)mia::MA_PROF_COUNTS), del((size_t)mia::MA_PROF_DEPTHS);
+    if (mia_hip_ma_profile(g, m.ref_seq.data(), use.data(), &n_used, &n_events) != MIA_HIP_OK) die(g, "ma_profile");
+    if (mia_hip_get_ma_profile(g, count.data(), del.data(), &bad_code, &beyond) != MIA_HIP_OK) die(g, "get_ma_profile");
+    if (out_format == 9) profile_table(n_used, n_events, count.data(), del.data(), bad_code, beyond);
+    else profile_matrix(count.data(), alpha);
     return finish(g);
   }
   if (out_format == 5) {
