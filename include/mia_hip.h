@@ -368,6 +368,29 @@ int mia_hip_ma_profile(mia_hip_ctx *ctx, const char *ref_seq, const uint8_t *use
  * NULL.  MIA_HIP_ERR_STATE without a mia_hip_ma_profile since the last mia_hip_ma_tally. */
 int mia_hip_get_ma_profile(mia_hip_ctx *ctx, int64_t *count, int64_t *del, int64_t *bad_code, int64_t *beyond);
 
+/* Fragment-end context and read lengths of the records of the last mia_hip_ma_tally (ma_hip -f 92, -f 93; the reference has no
+ * such reports, the rule is this library's own: DESIGN.md, "Fragment ends and read lengths").  ref_seq: the ref_len characters of the
+ * reference.  segment: n bytes, the records' SEG characters; NULL = every record is whole.  use: n bytes, 0 = the record is left out;
+ * NULL = every record counts.  For a record that counts, s = START, n columns, e = s + n - 1, d = +1 (forward) or -1 (stored reverse-
+ * complemented):
+ *   5' end at anchor a = s (forward, unless SEG is 'b') or a = e (reverse, unless SEG is 'f')
+ *   3' end at anchor a = e (forward, unless SEG is 'f') or a = s (reverse, unless SEG is 'b')
+ * (of a read split at the origin only the front record's START and the back record's END are ends of the read).  Positions
+ * k = -10 .. -1, +1 .. +10, o = k + 10 for k < 0, k + 9 for k > 0.  5' end: k > 0 is column a + d (k - 1), k < 0 column a + d k;
+ * 3' end: k < 0 is column a + d (k + 1), k > 0 column a + d k.  Class of column p: 5 outside 0 .. ref_len - 1 (no wrap), else A, C, G,
+ * T -> 0 .. 3, anything else -> 4 of toupper(ref_seq[p]); on the reverse strand a class c < 4 becomes 3 - c.  Each event adds one to
+ * ctx[end][o][class], end 0 = 5', 1 = 3'.  A whole record (SEG neither 'f' nor 'b') adds one to len[rc][min(length, 512)], length = its
+ * columns that are not '-' plus the characters other than '-' of its INS_POS pairs with a position in 0 .. n-1 that no later pair of
+ * the record repeats: the SEQ characters mia_hip_ma_sam gives it.  A half adds one to halves and has no length.  The counts are exact
+ * and do not depend on the order of the records.
+ *   n_used = the records that count;  n_ends5, n_ends3 = their 5' and 3' ends.  Any of them may be NULL.
+ * MIA_HIP_ERR_STATE without a mia_hip_ma_tally before; MIA_HIP_ERR_ARG for ref_seq == NULL; the context stays usable. */
+int mia_hip_ma_ends(mia_hip_ctx *ctx, const char *ref_seq, const uint8_t *segment, const uint8_t *use, int64_t *n_used, int64_t *n_ends5,
+                    int64_t *n_ends3);
+/* ctx_count[2 * 20 * 6] ([end][o][class]), len_count[2 * 513] ([rc][length]), *halves of the last mia_hip_ma_ends.  Any pointer may
+ * be NULL.  MIA_HIP_ERR_STATE without a mia_hip_ma_ends since the last mia_hip_ma_tally. */
+int mia_hip_get_ma_ends(mia_hip_ctx *ctx, int64_t *ctx_count, int64_t *len_count, int64_t *halves);
+
 /* ---- Myers edit distance -------------------------------------------------- */
 
 /* unsigned myers_diff(const char *seq_a, enum myers_align_mode mode, const char* seq_b, int maxd,
@@ -446,7 +469,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_profile, k_ma_tally), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_profile, k_ma_tally, k_ma_ends), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

@@ -30,15 +30,16 @@
 #include "mia_ma_ace_kernels.h"
 #include "mia_ma_sam_kernels.h"
 #include "mia_ma_profile_kernels.h"
+#include "mia_ma_ends_kernels.h"
 
 using namespace mia;
 
 // timed stages (HIP events on the context's stream around the kernel launches of that kind)
-enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_PROFILE, STG_MA_TALLY, STG_COUNT };
+enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_PROFILE, STG_MA_TALLY, STG_MA_ENDS, STG_COUNT };
 static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan",
                                                    "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select",
                                                    "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout",
-                                                   "k_ma_sam_render", "k_ma_profile", "k_ma_tally"};
+                                                   "k_ma_sam_render", "k_ma_profile", "k_ma_tally", "k_ma_ends"};
 
 // One device block for every small counter of an iteration (planner bins and header, filter / band-pipeline counters, link
 // count, cull and tally flags, insert-event count): one memset at the start of the alignment clears them all, and one copy
@@ -269,6 +270,10 @@ struct mia_hip_ctx {
   // (ma_profile_body.h) on the device and, after the call, here
   DevBuf<uint8_t> d_ma_rev, d_prof_use; DevBuf<char> d_ma_smp, d_prof_ref; DevBuf<unsigned long long> d_prof_bins;
   bool ma_prof_done = false; int64_t ma_cols = 0; int64_t ma_prof_bins[MA_PROF_BINS] = {0};
+  // ... and for mia_hip_ma_ends, which shares the reference's and the selection's buffers with the profile (either call's results are on
+  // the host when it returns): the segment characters, the 1 267 bins (ma_ends_body.h) on the device and, after the call, here
+  DevBuf<uint8_t> d_ends_seg; DevBuf<unsigned long long> d_ends_bins;
+  bool ma_ends_done = false; int64_t ma_ends_bins[MA_ENDS_BINS] = {0};
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------

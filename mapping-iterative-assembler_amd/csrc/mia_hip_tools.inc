@@ -125,7 +125,8 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   }
   // The records stay on the device behind this call (mia_hip_ma_region reads them): buffers of the context, made here, before anything
   // is queued.  Strand and depth codes stay for mia_hip_ma_profile; the pairs' record numbers are needed by the tally alone.  SEQ and
-  // SMP are readable up to the next multiple of MA_PROF_LANE behind their last character (k_ma_profile loads them in words of that size).
+  // SMP are readable up to the next multiple of MA_PROF_LANE behind their last character (k_ma_profile loads them in words of that size),
+  // and so are the pairs' characters (k_ma_ends counts their '-' in such words too).
   ctx->ma_resident = false;
   ctx->ma_region_done = false;
   ctx->ma_ace_done = false;
@@ -134,11 +135,12 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->ma_sam_done = false;
   ctx->ma_sam_gaps_ok = ma_sam_gaps_ok(gaps, ref_len);
   ctx->ma_prof_done = false;
+  ctx->ma_ends_done = false;
   DevBuf<int32_t> d_irec;   // every temporary is released on any return
   int rcx = dev_alloc(ctx, ctx->d_ma_start, n + 1) | dev_alloc(ctx, ctx->d_ma_rev, n + 1) | dev_alloc(ctx, ctx->d_ma_coff, n + 1) |
             dev_alloc(ctx, ctx->d_ma_seq, chars + MA_PROF_LANE) | dev_alloc(ctx, ctx->d_ma_smp, chars + MA_PROF_LANE) | dev_alloc(ctx, d_irec, n_ins + 1) |
             dev_alloc(ctx, ctx->d_ma_ipos, n_ins + 1) | dev_alloc(ctx, ctx->d_ma_ioff, n_ins + 1) |
-            dev_alloc(ctx, ctx->d_ma_ib, ins_chars + 1) | dev_alloc(ctx, ctx->d_ma_gaps, ref_len) |
+            dev_alloc(ctx, ctx->d_ma_ib, ins_chars + MA_PROF_LANE) | dev_alloc(ctx, ctx->d_ma_gaps, ref_len) |
             dev_alloc(ctx, ctx->d_ma_rec_ins, n + 1) | dev_alloc(ctx, ctx->d_ma_ins_list, n_ins + 1) |
             dev_alloc(ctx, ctx->d_ma_colmap, (int64_t)ref_len + 1) | dev_alloc(ctx, ctx->d_ma_rows, n + 1) |
             dev_alloc(ctx, ctx->d_ma_ctl, (int64_t)MAR_STATE + n / MAR_PER_WG + 2);
@@ -394,6 +396,56 @@ extern "C" int mia_hip_get_ma_profile(mia_hip_ctx* ctx, int64_t* count, int64_t*
   if (del) memcpy(del, ctx->ma_prof_bins + MA_PROF_DEL, sizeof(int64_t) * MA_PROF_DEPTHS);
   if (bad_code) *bad_code = ctx->ma_prof_bins[MA_PROF_BAD];
   if (beyond) *beyond = ctx->ma_prof_bins[MA_PROF_BEYOND];
+  return MIA_HIP_OK;
+}
+
+// Fragment-end context and read lengths (ma_hip -f 92, -f 93) of the records of the last mia_hip_ma_tally: see mia_ma_ends_kernels.h.
+// Columns, strands and the INS_POS pairs by record are on the device already; the reference, the segments and the selection go up.
+extern "C" int mia_hip_ma_ends(mia_hip_ctx* ctx, const char* ref_seq, const uint8_t* segment, const uint8_t* use, int64_t* n_used,
+                               int64_t* n_ends5, int64_t* n_ends3) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_ends"; return MIA_HIP_ERR_STATE; }
+  if (!ref_seq) { ctx->err = "ma_ends: no reference sequence"; return MIA_HIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->ma_ends_done = false;
+  const int64_t n = ctx->ma_n;
+  const int32_t L = ctx->ma_L;
+  if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, ctx->d_prof_use, n + 1) || dev_ensure(ctx, ctx->d_ends_seg, n + 1) ||
+      dev_ensure(ctx, ctx->d_ends_bins, MA_ENDS_BINS))
+    return MIA_HIP_ERR_NOMEM;
+  HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+  if (segment && n > 0) HIPCHK(hipMemcpyAsync(ctx->d_ends_seg, segment, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (use && n > 0) HIPCHK(hipMemcpyAsync(ctx->d_prof_use, use, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->d_ends_bins, 0, (size_t)MA_ENDS_BINS * 8, ctx->stream));
+  if (n > 0) {
+    MaEndsView v{n, L, ctx->d_ma_start, ctx->d_ma_rev, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos, ctx->d_ma_ioff,
+                 ctx->d_ma_ib, ctx->d_prof_ref, segment ? (const uint8_t*)ctx->d_ends_seg : nullptr, use ? (const uint8_t*)ctx->d_prof_use : nullptr};
+    // persistent grid: the workgroups that are resident at once, or one per 256 records when there are fewer
+    int64_t grid = (int64_t)ctx->cus * MAE_WGS_PER_CU;
+    if (grid > ma_ends_chunks(n)) grid = ma_ends_chunks(n);
+    if (stage_launch(ctx, STG_MA_ENDS, k_ma_ends, dim3((unsigned)grid), dim3(MAE_THREADS), 0, ctx->stream, v, (unsigned long long*)ctx->d_ends_bins))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(ctx->ma_ends_bins, ctx->d_ends_bins, (size_t)MA_ENDS_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  int64_t used = 0, ends[2] = {0, 0};
+  for (int64_t r = 0; r < n; r++) used += !use || use[r] ? 1 : 0;
+  for (int end = 0; end < 2; end++)                          // every end adds one event to each of its 20 positions: count position 0
+    for (int c = 0; c < MA_ENDS_CLASSES; c++) ends[end] += ctx->ma_ends_bins[ma_ends_ctx_bin(end, 0, c)];
+  ctx->ma_ends_done = true;
+  if (n_used) *n_used = used;
+  if (n_ends5) *n_ends5 = ends[0];
+  if (n_ends3) *n_ends3 = ends[1];
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_ends(mia_hip_ctx* ctx, int64_t* ctx_count, int64_t* len_count, int64_t* halves) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident || !ctx->ma_ends_done) { ctx->err = "ma_ends first"; return MIA_HIP_ERR_STATE; }
+  if (ctx_count) memcpy(ctx_count, ctx->ma_ends_bins, sizeof(int64_t) * MA_ENDS_CTX);
+  if (len_count) memcpy(len_count, ctx->ma_ends_bins + MA_ENDS_LEN, sizeof(int64_t) * 2 * MA_ENDS_LENS);
+  if (halves) *halves = ctx->ma_ends_bins[MA_ENDS_HALVES];
   return MIA_HIP_OK;
 }
 

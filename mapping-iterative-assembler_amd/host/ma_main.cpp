@@ -2,10 +2,12 @@
 // format), -f 5 (assembled sequence as FASTA), -f 41 and -f 4 (per-column table), -f 6 and -f 61 (the fragments of a region,
 // -R), -f 7 (ACE export, every record in full), -f 8 (SAM, which the reference does not have: the reads as aligned to the reference), -f 9 and -f 91 (the substitution profile of the
 // assembly, which the reference does not have either: substitution counts by distance from the read's ends, and a -s matrix made
-// from them; -P pseudocount, -A dropped records too) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
+// from them; -P pseudocount, -A dropped records too), -f 92 and -f 93 (which the reference does not have either: the reference bases around the places where reads
+// begin and end, and the reads' lengths per strand) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
 // find_ins_cons run on the GPU (mia_hip_ma_tally, every record counts, dropped or not), and so do the selection and the
 // rows of the region view (mia_hip_ma_region), the padded reads of the ACE export (mia_hip_ma_ace) and CIGAR, SEQ and NM of the SAM
-// export (mia_hip_ma_sam) and the counts of the substitution profile (mia_hip_ma_profile); calling, phred score and
+// export (mia_hip_ma_sam) and the counts of the substitution profile (mia_hip_ma_profile) and of the two
+// fragment reports (mia_hip_ma_ends); calling, phred score and
 // printing follow src/map_alignment.c:107-220, src/map_align.c:152-227,294-391,543-759 and src/io.c:756-913,929-1085.  Format 3
 // (the summary of format 2 plus a table per column: coverage, and the records that start and that end there on either strand,
 // src/map_align.c:761-849, src/map_alignment.c:635-653 -- counts no kernel here produces) stays outside.
@@ -29,6 +31,7 @@
 #include "../csrc/ma_ace_body.h"
 #include "../csrc/ma_sam_body.h"
 #include "../csrc/ma_profile_body.h"
+#include "../csrc/ma_ends_body.h"
 
 namespace {
 
@@ -37,9 +40,9 @@ using namespace maln_text;
 typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6, 61, 7, 8, 9 or 91>\n   -R <REGION_START:REGION_END>\n"
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6, 61, 7, 8, 9, 91, 92 or 93>\n   -R <REGION_START:REGION_END>\n"
          "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
-         "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 9 and 91)\n"
+         "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 9, 91, 92 and 93)\n"
          "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
          "(-f 1 clustalw, the default; -f 2 one line each plus coverage), the per-column table (-f 41 all positions, -f 4\n"
          "positions that differ from the reference), the assembled sequence (-f 5), and the reference, the consensus and every\n"
@@ -51,6 +54,10 @@ void help() {
          "reference base was read as which base, the deletions, and the columns with an N or another code (C>T at the first\n"
          "and G>A at the last positions is the damage of ancient DNA); -f 91 prints a substitution matrix made from these counts,\n"
          "a file for mia -s (100 * log2 of the share of each read base per reference base over 0.25, -P added to every count).\n"
+         "-f 92 prints the fragmentation context: for the 5' and the 3' ends of the reads the reference bases at the ten positions\n"
+         "in front of (-10..-1) and behind (+1..+10) each end, in the read's orientation (an excess of purines at 5' -1 is the\n"
+         "depurination of ancient DNA); -f 93 prints the distribution of the reads' lengths per strand.  A read split at the\n"
+         "origin gives only its true ends and no length.\n"
          "Dropped records do not count unless -A is given; the counts come from the MI355X.  Format 3 (format 2's summary plus\n"
          "a table of coverage and of the records that start and end at every column) is outside the accelerated path.\n");
 }
@@ -259,6 +266,40 @@ void profile_matrix(const int64_t* count, double alpha) {
   o.flush();
 }
 
+// -f 92: the reference's classes around the reads' ends, a line per end and position
+void ends_table(int64_t n_used, int64_t n5, int64_t n3, const int64_t* ctx_count) {
+  Out o;
+  o.fmt("# ma_hip fragment ends: %lld records, %lld 5' ends, %lld 3' ends\n", (long long)n_used, (long long)n5, (long long)n3);
+  o.buf += "# end\tposition\tA\tC\tG\tT\tother\toutside\n";
+  for (int end = 0; end < 2; end++)
+    for (int p = 0; p < mia::MA_ENDS_POS; p++) {
+      o.fmt("%s\t%+d", end ? "3p" : "5p", mia::ma_ends_k(p));
+      for (int c = 0; c < mia::MA_ENDS_CLASSES; c++) o.fmt("\t%lld", (long long)ctx_count[mia::ma_ends_ctx_bin(end, p, c)]);
+      o.buf += '\n';
+    }
+  o.flush();
+}
+
+// -f 93: the lengths of the whole records per strand, from the shortest to the longest that occurs
+void lengths_table(const int64_t* len_count, int64_t halves) {
+  const int64_t* fwd = len_count;
+  const int64_t* rev = len_count + mia::MA_ENDS_LENS;
+  int64_t whole = 0;
+  int lo = mia::MA_ENDS_MAX_LEN, hi = -1;
+  for (int l = 0; l <= mia::MA_ENDS_MAX_LEN; l++) {
+    whole += fwd[l] + rev[l];
+    if (l < mia::MA_ENDS_MAX_LEN && fwd[l] + rev[l] > 0) { if (lo > l) lo = l; hi = l; }
+  }
+  const int64_t longer = fwd[mia::MA_ENDS_MAX_LEN] + rev[mia::MA_ENDS_MAX_LEN];
+  Out o;
+  o.fmt("# ma_hip read lengths: %lld whole records, %lld halves of reads split at the origin (not counted), %lld longer than %d\n", (long long)whole,
+        (long long)halves, (long long)longer, mia::MA_ENDS_MAX_LEN - 1);
+  o.buf += "# length\tforward\treverse\n";
+  for (int l = lo; l <= hi; l++) o.fmt("%d\t%lld\t%lld\n", l, (long long)fwd[l], (long long)rev[l]);
+  if (longer > 0) o.fmt(">%d\t%lld\t%lld\n", mia::MA_ENDS_MAX_LEN - 1, (long long)fwd[mia::MA_ENDS_MAX_LEN], (long long)rev[mia::MA_ENDS_MAX_LEN]);
+  o.flush();
+}
+
 void die(mia_hip_ctx* g, const char* what) {
   fprintf(stderr, "%s: %s\n", what, g ? mia_hip_last_error(g) : "no context");
   exit(1);
@@ -294,8 +335,8 @@ int main(int argc, char* argv[]) {
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91) {
-    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 8, 9 and 91, which the reference does not have); use the reference's ma\n", out_format);
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93) {
+    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 8, 9, 91, 92 and 93, which the reference does not have); use the reference's ma\n", out_format);
     exit(1);
   }
   if (out_format == 91 && !mia::ma_prof_alpha_ok(alpha)) {
@@ -348,6 +389,20 @@ int main(int argc, char* argv[]) {
     if (mia_hip_get_ma_profile(g, count.data(), del.data(), &bad_code, &beyond) != MIA_HIP_OK) die(g, "get_ma_profile");
     if (out_format == 9) profile_table(n_used, n_events, count.data(), del.data(), bad_code, beyond);
     else profile_matrix(count.data(), alpha);
+    return finish(g);
+  }
+  if (out_format == 92 || out_format == 93) {
+    std::vector<uint8_t> use((size_t)n + 1, 1), seg((size_t)n + 1, 'n');
+    for (int64_t r = 0; r < n; r++) {
+      use[(size_t)r] = use_dropped || !m.rec[(size_t)r].dropped ? 1 : 0;
+      seg[(size_t)r] = (uint8_t)m.rec[(size_t)r].segment;
+    }
+    int64_t n_used = 0, n5 = 0, n3 = 0, halves = 0;
+    std::vector<int64_t> ctx_count((size_t)mia::MA_ENDS_CTX), len_count((size_t)2 * mia::MA_ENDS_LENS);
+    if (mia_hip_ma_ends(g, m.ref_seq.data(), seg.data(), use.data(), &n_used, &n5, &n3) != MIA_HIP_OK) die(g, "ma_ends");
+    if (mia_hip_get_ma_ends(g, ctx_count.data(), len_count.data(), &halves) != MIA_HIP_OK) die(g, "get_ma_ends");
+    if (out_format == 92) ends_table(n_used, n5, n3, ctx_count.data());
+    else lengths_table(len_count.data(), halves);
     return finish(g);
   }
   if (out_format == 5) {
