@@ -391,6 +391,25 @@ int mia_hip_ma_ends(mia_hip_ctx *ctx, const char *ref_seq, const uint8_t *segmen
  * be NULL.  MIA_HIP_ERR_STATE without a mia_hip_ma_ends since the last mia_hip_ma_tally. */
 int mia_hip_get_ma_ends(mia_hip_ctx *ctx, int64_t *ctx_count, int64_t *len_count, int64_t *halves);
 
+/* The strand-split column table of the records of the last mia_hip_ma_tally (ma_hip -f 42; the rule is DESIGN.md's "Strand table
+ * (-f 42)"): sixteen 32-bit words per reference column p in 0 .. ref_len - 1.  segment: n bytes, the records' SEG characters; NULL =
+ * every record is whole.  use: n bytes, 0 = the record is left out; NULL = every record counts.  No reference characters are needed.
+ * For a record that counts, s = START, n columns, e = s + n - 1, rc = stored reverse-complemented:
+ *   column c = 0 .. n-1 on p = s + c adds one to word (rc ? 6 : 0) + class(seq[c]), class of the exact character: A, C, G, T -> 0 .. 3,
+ *   '-' -> 4, anything else (lower case too) -> 5; a column with p >= ref_len (a record of a circular assembly may end on column
+ *   ref_len) adds one to *beyond instead;
+ *   word 12 / 13: forward / reverse records that start on p = s, unless SEG is 'b'; word 14 / 15: forward / reverse records that end on
+ *   p = e, unless SEG is 'f' (columns 5-8 of the reference's ma -f 3); an anchor outside 0 .. ref_len - 1 adds one to *ends_outside
+ *   instead.  A record without columns is not special: e = s - 1.
+ * n_used = the records that count; n_events = the sum of words 0 .. 11 plus *beyond.  Any count may be NULL.  The counts are exact and
+ * do not depend on the order of the records.  Without records nothing is launched and the table is zero.
+ * MIA_HIP_ERR_STATE without a mia_hip_ma_tally before; the context stays usable. */
+int mia_hip_ma_cols(mia_hip_ctx *ctx, const uint8_t *segment, const uint8_t *use, int64_t *n_used, int64_t *n_events, int64_t *beyond,
+                    int64_t *ends_outside);
+/* cols[w * ref_len + p], w = 0 .. 15, of the last mia_hip_ma_cols; cols may be NULL.  MIA_HIP_ERR_STATE without a mia_hip_ma_cols since
+ * the last mia_hip_ma_tally. */
+int mia_hip_get_ma_cols(mia_hip_ctx *ctx, int32_t *cols);
+
 /* ---- Myers edit distance -------------------------------------------------- */
 
 /* unsigned myers_diff(const char *seq_a, enum myers_align_mode mode, const char* seq_b, int maxd,
@@ -469,7 +488,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_profile, k_ma_tally, k_ma_ends), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_profile, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

@@ -108,6 +108,9 @@ def _load(path=None):
     if hasattr(lib, "mia_hip_ma_ends"):
         lib.mia_hip_ma_ends.argtypes = [vp, vp, vp, vp, P(C.c_int64), P(C.c_int64), P(C.c_int64)]
         lib.mia_hip_get_ma_ends.argtypes = [vp, vp, vp, P(C.c_int64)]
+    if hasattr(lib, "mia_hip_ma_cols"):
+        lib.mia_hip_ma_cols.argtypes = [vp, vp, vp, P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int64)]
+        lib.mia_hip_get_ma_cols.argtypes = [vp, vp]
     lib.mia_hip_kernel_time.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_int64)]
     lib.mia_hip_stage_stats.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp, P(C.c_int32)]
     lib.mia_hip_set_stage_mask.argtypes = [vp, C.c_uint32]
@@ -152,7 +155,7 @@ def exported_symbols():
             "mia_hip_upload_reads", "mia_hip_pass1", "mia_hip_realign", "mia_hip_align_windows", "mia_hip_get_alignments", "mia_hip_get_scripts", "mia_hip_cull",
             "mia_hip_get_dropped", "mia_hip_set_slot_dropped", "mia_hip_score_cut", "mia_hip_num_records",
             "mia_hip_tally", "mia_hip_tally_buffers", "mia_hip_ins_events", "mia_hip_set_ins_events",
-            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
+            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
             "mia_hip_get_record_params", "mia_hip_set_read_base", "mia_hip_links", "mia_hip_set_links", "mia_hip_link_lengths",
             "mia_hip_finish_links", "mia_hip_plain_stats", "mia_hip_score_sums",
             "mia_hip_score_cut_from_sums", "mia_hip_stage_stats", "mia_hip_measure_peaks", "mia_hip_measure_issue", "mia_hip_set_tally", "mia_hip_iterate", "mia_hip_set_stage_mask", "mia_hip_comm_unique_id", "mia_hip_comm_init", "mia_hip_comm_destroy",
@@ -561,7 +564,7 @@ class MiaHip:
         self._chk(self._l.mia_hip_stage_stats(self._h, 1 if reset else 0, cap, names, ms, k, C.byref(n)))
         return {names[i].decode(): (ms[i], k[i]) for i in range(min(n.value, cap))}
 
-    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_profile", "k_ma_tally", "k_ma_ends"]
+    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_profile", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
 
     def comm_init(self, unique_id, n_ranks, rank):
         """attach an RCCL communicator (ncclCommInitRank on this context's GPU); unique_id: the 128 bytes of comm_unique_id()
@@ -694,6 +697,27 @@ class MiaHip:
                                           _ptr(use) if use is not None and use.size else None, None, None, None))
         self._chk(self._l.mia_hip_get_ma_ends(self._h, _ptr(ctx), _ptr(lens), C.byref(halves)))
         return ctx, lens, halves.value
+
+    def ma_cols(self, segment=None, use=None):
+        """the strand-split column table (ma_hip -f 42) over the records of the last ma_tally; segment: per record its SEG character
+        (bytes, str or uint8; None: every record is whole); use: per record 0 = left out (None: every record counts).
+        (cols[16, L], n_used, n_events, beyond, ends_outside): cols[w, p] for reference column p = A C G T gap other of the forward
+        records' columns (w = 0 .. 5) and of the reverse records' (6 .. 11), forward / reverse records that start there (12, 13) and
+        that end there (14, 15); n_events = the columns counted, `beyond` of them at or behind column L; ends_outside = starts and
+        ends on no reference column.  numpy int32 and ints."""
+        if segment is not None:
+            if isinstance(segment, str):
+                segment = segment.encode("latin1")
+            segment = np.frombuffer(segment, np.uint8) if isinstance(segment, (bytes, bytearray)) else np.ascontiguousarray(segment, dtype=np.uint8)
+        if use is not None:
+            use = np.ascontiguousarray(use, dtype=np.uint8)
+        cols = np.zeros((16, self.L), dtype=np.int32)
+        n_used, n_events, beyond, outside = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._l.mia_hip_ma_cols(self._h, _ptr(segment) if segment is not None and segment.size else None,
+                                          _ptr(use) if use is not None and use.size else None, C.byref(n_used), C.byref(n_events),
+                                          C.byref(beyond), C.byref(outside)))
+        self._chk(self._l.mia_hip_get_ma_cols(self._h, _ptr(cols)))
+        return cols, n_used.value, n_events.value, beyond.value, outside.value
 
     def ins_tally(self):
         """(ins_off[L+1], ins_tally[slots][9]) of the insert columns, after consensus()."""

@@ -31,15 +31,16 @@
 #include "mia_ma_sam_kernels.h"
 #include "mia_ma_profile_kernels.h"
 #include "mia_ma_ends_kernels.h"
+#include "mia_ma_cols_kernels.h"
 
 using namespace mia;
 
 // timed stages (HIP events on the context's stream around the kernel launches of that kind)
-enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_PROFILE, STG_MA_TALLY, STG_MA_ENDS, STG_COUNT };
+enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_PROFILE, STG_MA_TALLY, STG_MA_COLS, STG_MA_ENDS, STG_COUNT };
 static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan",
                                                    "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select",
                                                    "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout",
-                                                   "k_ma_sam_render", "k_ma_profile", "k_ma_tally", "k_ma_ends"};
+                                                   "k_ma_sam_render", "k_ma_profile", "k_ma_tally", "k_ma_cols", "k_ma_ends"};
 
 // One device block for every small counter of an iteration (planner bins and header, filter / band-pipeline counters, link
 // count, cull and tally flags, insert-event count): one memset at the start of the alignment clears them all, and one copy
@@ -274,6 +275,10 @@ struct mia_hip_ctx {
   // the host when it returns): the segment characters, the 1 267 bins (ma_ends_body.h) on the device and, after the call, here
   DevBuf<uint8_t> d_ends_seg; DevBuf<unsigned long long> d_ends_bins;
   bool ma_ends_done = false; int64_t ma_ends_bins[MA_ENDS_BINS] = {0};
+  // ... and for mia_hip_ma_cols, which takes the segments and the selection into the same buffers: the sixteen words per reference
+  // column (ma_cols_body.h) and the two counts of what lies on no column, on the device and, after the call, here
+  DevBuf<uint32_t> d_cols_tab; DevBuf<unsigned long long> d_cols_out;
+  bool ma_cols_done = false; std::vector<int32_t> ma_cols_tab;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------

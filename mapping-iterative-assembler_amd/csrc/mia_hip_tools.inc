@@ -136,6 +136,7 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->ma_sam_gaps_ok = ma_sam_gaps_ok(gaps, ref_len);
   ctx->ma_prof_done = false;
   ctx->ma_ends_done = false;
+  ctx->ma_cols_done = false;
   DevBuf<int32_t> d_irec;   // every temporary is released on any return
   int rcx = dev_alloc(ctx, ctx->d_ma_start, n + 1) | dev_alloc(ctx, ctx->d_ma_rev, n + 1) | dev_alloc(ctx, ctx->d_ma_coff, n + 1) |
             dev_alloc(ctx, ctx->d_ma_seq, chars + MA_PROF_LANE) | dev_alloc(ctx, ctx->d_ma_smp, chars + MA_PROF_LANE) | dev_alloc(ctx, d_irec, n_ins + 1) |
@@ -446,6 +447,57 @@ extern "C" int mia_hip_get_ma_ends(mia_hip_ctx* ctx, int64_t* ctx_count, int64_t
   if (ctx_count) memcpy(ctx_count, ctx->ma_ends_bins, sizeof(int64_t) * MA_ENDS_CTX);
   if (len_count) memcpy(len_count, ctx->ma_ends_bins + MA_ENDS_LEN, sizeof(int64_t) * 2 * MA_ENDS_LENS);
   if (halves) *halves = ctx->ma_ends_bins[MA_ENDS_HALVES];
+  return MIA_HIP_OK;
+}
+
+// The strand-split column table (ma_hip -f 42) of the records of the last mia_hip_ma_tally: see mia_ma_cols_kernels.h.  Columns and
+// strands are on the device already; only the segments and the selection go up (no reference characters: the pass does not need them).
+extern "C" int mia_hip_ma_cols(mia_hip_ctx* ctx, const uint8_t* segment, const uint8_t* use, int64_t* n_used, int64_t* n_events, int64_t* beyond,
+                               int64_t* ends_outside) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_cols"; return MIA_HIP_ERR_STATE; }
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->ma_cols_done = false;
+  const int64_t n = ctx->ma_n, words = (int64_t)MA_COLS_WORDS * ctx->ma_L;
+  const int32_t L = ctx->ma_L;
+  unsigned long long out[2] = {0, 0};
+  ctx->ma_cols_tab.assign((size_t)words, 0);
+  if (n > 0) {                                               // without records there is no launch and the table is zero
+    if (dev_ensure(ctx, ctx->d_prof_use, n + 1) || dev_ensure(ctx, ctx->d_ends_seg, n + 1) || dev_ensure(ctx, ctx->d_cols_tab, words) ||
+        dev_ensure(ctx, ctx->d_cols_out, 2))
+      return MIA_HIP_ERR_NOMEM;
+    if (segment) HIPCHK(hipMemcpyAsync(ctx->d_ends_seg, segment, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (use) HIPCHK(hipMemcpyAsync(ctx->d_prof_use, use, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_cols_tab, 0, (size_t)words * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->d_cols_out, 0, sizeof out, ctx->stream));
+    MaColsView v{n, L, ctx->d_ma_start, ctx->d_ma_rev, ctx->d_ma_coff, ctx->d_ma_seq, segment ? (const uint8_t*)ctx->d_ends_seg : nullptr,
+                 use ? (const uint8_t*)ctx->d_prof_use : nullptr};
+    // persistent grid over (tile, slice) jobs: the workgroups that are resident at once, or one per job when there are fewer
+    const int64_t wgs = (int64_t)ctx->cus * MAC_WGS_PER_CU, slices = ma_cols_slices(n, L, wgs), per_slice = (n + slices - 1) / slices;
+    const int64_t jobs = ma_cols_tiles(L) * slices, grid = jobs < wgs ? jobs : wgs;
+    if (stage_launch(ctx, STG_MA_COLS, k_ma_cols, dim3((unsigned)grid), dim3(MAC_THREADS), 0, ctx->stream, v, slices, per_slice, (uint32_t*)ctx->d_cols_tab,
+                     (unsigned long long*)ctx->d_cols_out))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ctx->ma_cols_tab.data(), ctx->d_cols_tab, (size_t)words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, ctx->d_cols_out, sizeof out, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  int64_t used = 0, events = (int64_t)out[0];
+  for (int64_t r = 0; r < n; r++) used += !use || use[r] ? 1 : 0;
+  for (int64_t i = 0; i < (int64_t)MA_COLS_STARTS * L; i++) events += ctx->ma_cols_tab[(size_t)i];       // words 0 .. 11 of every column
+  ctx->ma_cols_done = true;
+  if (n_used) *n_used = used;
+  if (n_events) *n_events = events;
+  if (beyond) *beyond = (int64_t)out[0];
+  if (ends_outside) *ends_outside = (int64_t)out[1];
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_cols(mia_hip_ctx* ctx, int32_t* cols) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident || !ctx->ma_cols_done) { ctx->err = "ma_cols first"; return MIA_HIP_ERR_STATE; }
+  if (cols) memcpy(cols, ctx->ma_cols_tab.data(), ctx->ma_cols_tab.size() * sizeof(int32_t));
   return MIA_HIP_OK;
 }
 

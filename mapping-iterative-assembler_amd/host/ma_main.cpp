@@ -3,14 +3,15 @@
 // -R), -f 7 (ACE export, every record in full), -f 8 (SAM, which the reference does not have: the reads as aligned to the reference), -f 9 and -f 91 (the substitution profile of the
 // assembly, which the reference does not have either: substitution counts by distance from the read's ends, and a -s matrix made
 // from them; -P pseudocount, -A dropped records too), -f 92 and -f 93 (which the reference does not have either: the reference bases around the places where reads
-// begin and end, and the reads' lengths per strand) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
+// begin and end, and the reads' lengths per strand), -f 42 (likewise this tool's own: -f 41's base counts per
+// strand, and the records that start and end on every column per strand, which are format 3's columns 5-8) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
 // find_ins_cons run on the GPU (mia_hip_ma_tally, every record counts, dropped or not), and so do the selection and the
 // rows of the region view (mia_hip_ma_region), the padded reads of the ACE export (mia_hip_ma_ace) and CIGAR, SEQ and NM of the SAM
 // export (mia_hip_ma_sam) and the counts of the substitution profile (mia_hip_ma_profile) and of the two
-// fragment reports (mia_hip_ma_ends); calling, phred score and
+// fragment reports (mia_hip_ma_ends) and the strand table (mia_hip_ma_cols); calling, phred score and
 // printing follow src/map_alignment.c:107-220, src/map_align.c:152-227,294-391,543-759 and src/io.c:756-913,929-1085.  Format 3
 // (the summary of format 2 plus a table per column: coverage, and the records that start and that end there on either strand,
-// src/map_align.c:761-849, src/map_alignment.c:635-653 -- counts no kernel here produces) stays outside.
+// src/map_align.c:761-849, src/map_alignment.c:635-653) stays outside; its four strand columns are part of -f 42.
 // No CPU fallback.
 #include <ctype.h>
 #include <float.h>
@@ -32,6 +33,7 @@
 #include "../csrc/ma_sam_body.h"
 #include "../csrc/ma_profile_body.h"
 #include "../csrc/ma_ends_body.h"
+#include "../csrc/ma_cols_body.h"
 
 namespace {
 
@@ -40,9 +42,9 @@ using namespace maln_text;
 typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 5, 6, 61, 7, 8, 9, 91, 92 or 93>\n   -R <REGION_START:REGION_END>\n"
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92 or 93>\n   -R <REGION_START:REGION_END>\n"
          "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
-         "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 9, 91, 92 and 93)\n"
+         "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 42, 9, 91, 92 and 93)\n"
          "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
          "(-f 1 clustalw, the default; -f 2 one line each plus coverage), the per-column table (-f 41 all positions, -f 4\n"
          "positions that differ from the reference), the assembled sequence (-f 5), and the reference, the consensus and every\n"
@@ -58,6 +60,9 @@ void help() {
          "in front of (-10..-1) and behind (+1..+10) each end, in the read's orientation (an excess of purines at 5' -1 is the\n"
          "depurination of ancient DNA); -f 93 prints the distribution of the reads' lengths per strand.  A read split at the\n"
          "origin gives only its true ends and no length.\n"
+         "-f 42 prints the strand table: a line per reference column (-R: of that region only) with the A, C, G, T, gap and other\n"
+         "columns of the forward (+) and of the reverse (-) records there, and the records that start and that end on it per strand\n"
+         "(damage shows as C>T on + and G>A on -; a variant shows on both; many starts on one column of one strand are duplicates).\n"
          "Dropped records do not count unless -A is given; the counts come from the MI355X.  Format 3 (format 2's summary plus\n"
          "a table of coverage and of the records that start and end at every column) is outside the accelerated path.\n");
 }
@@ -300,6 +305,21 @@ void lengths_table(const int64_t* len_count, int64_t halves) {
   o.flush();
 }
 
+// -f 42: the sixteen words of the reference columns first .. last
+void cols_table(const Maln& m, int64_t n_used, int64_t n_events, int64_t beyond, int64_t ends_outside, const int32_t* cols, int first, int last) {
+  Out o;
+  o.fmt("# ma_hip strand table: %lld records, %lld columns, %lld beyond the reference, %lld ends outside it\n", (long long)n_used, (long long)n_events,
+        (long long)beyond, (long long)ends_outside);
+  o.buf += "# position\treference\tA+\tC+\tG+\tT+\tgap+\tother+\tA-\tC-\tG-\tT-\tgap-\tother-\tstarts+\tstarts-\tends+\tends-\n";
+  for (int p = first; p <= last; p++) {
+    o.fmt("%d\t%c", p + 1, m.ref_seq[(size_t)p]);
+    for (int w = 0; w < mia::MA_COLS_WORDS; w++) o.fmt("\t%d", cols[(size_t)w * (size_t)m.L + (size_t)p]);
+    o.buf += '\n';
+    o.room();
+  }
+  o.flush();
+}
+
 void die(mia_hip_ctx* g, const char* what) {
   fprintf(stderr, "%s: %s\n", what, g ? mia_hip_last_error(g) : "no context");
   exit(1);
@@ -311,7 +331,7 @@ int main(int argc, char* argv[]) {
   std::string ma_in_fn, assign_id, ma_out_fn;
   bool id_assigned = false, in_ma = false, any_arg = false, out_ma = false;
   int cons_scheme = 1, out_format = 1, gpu = 0, reg_start = 90, reg_end = 109;
-  bool in_color = false, use_dropped = false;
+  bool in_color = false, use_dropped = false, region_given = false;
   double score_int = -1.0, score_slo = -1.0, alpha = 1.0;
   int ich;
   // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount> and -A
@@ -321,7 +341,7 @@ int main(int argc, char* argv[]) {
       case 'c': cons_scheme = atoi(optarg); any_arg = true; break;
       case 'i': any_arg = true; break;                 // parsed and never used by the reference either
       case 'f': out_format = atoi(optarg); any_arg = true; break;
-      case 'R': parse_region(optarg, &reg_start, &reg_end); any_arg = true; break;
+      case 'R': parse_region(optarg, &reg_start, &reg_end); region_given = true; any_arg = true; break;
       case 's': score_slo = atof(optarg); any_arg = true; break;
       case 'b': score_int = atof(optarg); any_arg = true; break;
       case 'C': in_color = true; break;
@@ -335,8 +355,8 @@ int main(int argc, char* argv[]) {
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93) {
-    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 8, 9, 91, 92 and 93, which the reference does not have); use the reference's ma\n", out_format);
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 42 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93) {
+    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 42, 8, 9, 91, 92 and 93, which the reference does not have); use the reference's ma\n", out_format);
     exit(1);
   }
   if (out_format == 91 && !mia::ma_prof_alpha_ok(alpha)) {
@@ -403,6 +423,21 @@ int main(int argc, char* argv[]) {
     if (mia_hip_get_ma_ends(g, ctx_count.data(), len_count.data(), &halves) != MIA_HIP_OK) die(g, "get_ma_ends");
     if (out_format == 92) ends_table(n_used, n5, n3, ctx_count.data());
     else lengths_table(len_count.data(), halves);
+    return finish(g);
+  }
+  if (out_format == 42) {
+    std::vector<uint8_t> use((size_t)n + 1, 1), seg((size_t)n + 1, 'n');
+    for (int64_t r = 0; r < n; r++) {
+      use[(size_t)r] = use_dropped || !m.rec[(size_t)r].dropped ? 1 : 0;
+      seg[(size_t)r] = (uint8_t)m.rec[(size_t)r].segment;
+    }
+    int64_t n_used = 0, n_events = 0, beyond = 0, ends_outside = 0;
+    std::vector<int32_t> cols((size_t)mia::MA_COLS_WORDS * (size_t)L);
+    if (mia_hip_ma_cols(g, seg.data(), use.data(), &n_used, &n_events, &beyond, &ends_outside) != MIA_HIP_OK) die(g, "ma_cols");
+    if (mia_hip_get_ma_cols(g, cols.data()) != MIA_HIP_OK) die(g, "get_ma_cols");
+    int first = 0, last = L - 1;                       // every column, unless -R names a region (format 6's default does not apply)
+    if (region_given) clamp_region(reg_start, reg_end, L, &first, &last);
+    cols_table(m, n_used, n_events, beyond, ends_outside, cols.data(), first, last);
     return finish(g);
   }
   if (out_format == 5) {
