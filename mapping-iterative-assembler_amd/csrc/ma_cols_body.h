@@ -17,29 +17,22 @@
 #pragma once
 #include <stdint.h>
 
-#ifndef MIA_HD
-#if defined(__HIPCC__)
-#define MIA_HD __host__ __device__
-#else
-#define MIA_HD
-#endif
-#endif
+#include "ma_records.h"
 
 namespace mia {
 
 constexpr int MA_COLS_TILE = 512;          // reference columns of one tile: 16 words x 512 x 4 bytes = 32 KiB of LDS
 constexpr int MA_COLS_WORDS = 16, MA_COLS_CLASSES = 6, MA_COLS_STARTS = 12, MA_COLS_ENDS = 14;
 
-// The records of a .maln as mia_hip_ma_tally keeps them, the segments and the selection.
-struct MaColsView {
-  int64_t n;
-  int32_t L;
-  const int32_t* start;      // [n]
-  const uint8_t* revcom;     // [n]
-  const int64_t* col_off;    // [n+1]: record r owns seq[col_off[r] .. col_off[r+1]) = columns start .. end
-  const char* seq;           // 4-byte aligned and readable up to the next multiple of four behind col_off[n]
+// The records (ma_records.h: seq is loaded in aligned words of four characters), the segments and the selection.
+struct MaColsView : MaRecords {
   const uint8_t* segment;    // [n]: the SEG character; NULL = every record is whole
   const uint8_t* use;        // [n]: 0 = the record is left out; NULL = every record counts
+  MaColsView(const MaRecords& recs, const uint8_t* segment, const uint8_t* use) : MaRecords(recs), segment(segment), use(use) {}
+  // ... or from the arrays this export reads alone, for a caller that holds no more (the host drivers): the rest of MaRecords is null
+  MaColsView(int64_t n, int32_t L, const int32_t* start, const uint8_t* revcom, const int64_t* col_off, const char* seq, const uint8_t* segment,
+             const uint8_t* use)
+      : MaRecords{n, L, start, revcom, col_off, seq, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, segment(segment), use(use) {}
 };
 
 MIA_HD inline int ma_cols_class(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : c == '-' ? 4 : 5; }

@@ -19,7 +19,8 @@
 #pragma once
 #include <stdint.h>
 
-#include "ma_profile_body.h"               // MIA_HD, MA_PROF_LANE and ma_prof_load: SEQ is read in the same 16-byte words
+#include "ma_profile_body.h"               // ma_prof_class, ma_prof_mirror and MA_PROF_UNROLL
+#include "ma_records.h"
 
 namespace mia {
 
@@ -28,22 +29,17 @@ constexpr int MA_ENDS_CTX = 2 * MA_ENDS_POS * MA_ENDS_CLASSES;                  
 constexpr int MA_ENDS_MAX_LEN = 512, MA_ENDS_LENS = MA_ENDS_MAX_LEN + 1;        // bin 512 holds everything longer than 511
 constexpr int MA_ENDS_LEN = MA_ENDS_CTX, MA_ENDS_HALVES = MA_ENDS_LEN + 2 * MA_ENDS_LENS, MA_ENDS_BINS = MA_ENDS_HALVES + 1;   // 240, 1 266, 1 267
 
-// The records of a .maln as mia_hip_ma_tally keeps them (MaSamView's arrays), the reference, the segments and the selection.
-struct MaEndsView {
-  int64_t n;
-  int32_t L;
-  const int32_t* start;      // [n]
-  const uint8_t* revcom;     // [n]
-  const int64_t* col_off;    // [n+1]: record r owns seq[col_off[r] .. col_off[r+1]) = columns start .. end
-  const char* seq;           // 16-byte aligned and readable up to the next multiple of MA_PROF_LANE behind col_off[n]
-  const int32_t* rec_ins;    // [n+1]: record r owns ins_list[rec_ins[r] .. rec_ins[r+1])
-  const int32_t* ins_list;   // pair numbers, by record, ascending ins_pos; pairs of one position in the order they were given
-  const int32_t* ins_pos;
-  const int64_t* ins_off;    // per pair (+1): its characters are ins_bases[ins_off[e] .. ins_off[e+1])
-  const char* ins_bases;     // 16-byte aligned and readable up to the next multiple of MA_PROF_LANE behind its last character, as seq is
+// The records (ma_records.h: seq and ins_bases are loaded in whole 16-byte words), the reference, the segments and the selection.
+struct MaEndsView : MaRecords {
   const char* ref;           // [L]
   const uint8_t* segment;    // [n]: the SEG character; NULL = every record is whole
   const uint8_t* use;        // [n]: 0 = the record is left out; NULL = every record counts
+  MaEndsView(const MaRecords& recs, const char* ref, const uint8_t* segment, const uint8_t* use) : MaRecords(recs), ref(ref), segment(segment), use(use) {}
+  // ... or from the arrays this export reads alone, for a caller that holds no more (the host drivers): the rest of MaRecords is null
+  MaEndsView(int64_t n, int32_t L, const int32_t* start, const uint8_t* revcom, const int64_t* col_off, const char* seq, const int32_t* rec_ins,
+             const int32_t* ins_list, const int32_t* ins_pos, const int64_t* ins_off, const char* ins_bases, const char* ref, const uint8_t* segment,
+             const uint8_t* use)
+      : MaRecords{n, L, start, revcom, col_off, seq, rec_ins, ins_list, ins_pos, ins_off, ins_bases, nullptr}, ref(ref), segment(segment), use(use) {}
 };
 
 // is the end there (end 0 = 5', 1 = 3'), and on which column
@@ -72,12 +68,12 @@ MIA_HD inline uint32_t ma_ends_dash_flags(uint32_t w) {
 MIA_HD inline int64_t ma_ends_bases(const char* seq, int64_t off, int64_t n) {
   int64_t dashes = 0;
   const int64_t end = off + n;
-  for (int64_t base = off & ~(int64_t)(MA_PROF_LANE - 1); base < end; base += MA_PROF_LANE) {
-    const MaProfWord x = ma_prof_load(seq + base);
+  for (int64_t base = off & ~(int64_t)(MA_REC_LANE - 1); base < end; base += MA_REC_LANE) {
+    const MaRecWord x = ma_rec_load(seq + base);
     uint32_t m = 0;                        // bit b: byte b of the word is '-'
     MA_PROF_UNROLL
-    for (int w = 0; w < MA_PROF_LANE / 4; w++) m |= (((ma_ends_dash_flags(x.w[w]) >> 7) * 0x00204081u >> 21) & 0xfu) << (4 * w);
-    const int lo = off > base ? (int)(off - base) : 0, hi = end - base < MA_PROF_LANE ? (int)(end - base) : MA_PROF_LANE;
+    for (int w = 0; w < MA_REC_LANE / 4; w++) m |= (((ma_ends_dash_flags(x.w[w]) >> 7) * 0x00204081u >> 21) & 0xfu) << (4 * w);
+    const int lo = off > base ? (int)(off - base) : 0, hi = end - base < MA_REC_LANE ? (int)(end - base) : MA_REC_LANE;
     dashes += __builtin_popcount(m & ((1u << hi) - 1u) & ~((1u << lo) - 1u));
   }
   return n - dashes;
@@ -85,14 +81,13 @@ MIA_HD inline int64_t ma_ends_bases(const char* seq, int64_t off, int64_t n) {
 
 // the characters other than '-' of the record's INS_POS pairs that count
 MIA_HD inline int64_t ma_ends_inserted(const MaEndsView& v, int64_t r, int64_t ncols) {
-  const int32_t lo = v.rec_ins[r], cnt = v.rec_ins[r + 1] - lo;
-  int64_t k = 0;
-  for (int32_t j = 0; j < cnt; j++) {
-    const int32_t e = v.ins_list[lo + j], pos = v.ins_pos[e];
-    if (pos < 0 || pos >= ncols || (j + 1 < cnt && v.ins_pos[v.ins_list[lo + j + 1]] == pos)) continue;
-    k += ma_ends_bases(v.ins_bases, v.ins_off[e], v.ins_off[e + 1] - v.ins_off[e]);
+  int64_t bases = 0;
+  for (int32_t k = v.rec_ins[r], hi = v.rec_ins[r + 1]; k < hi; k++) {
+    if (!ma_rec_pair_counts(v, k, hi, ncols)) continue;
+    const int32_t e = v.ins_list[k];
+    bases += ma_ends_bases(v.ins_bases, v.ins_off[e], v.ins_off[e + 1] - v.ins_off[e]);
   }
-  return k;
+  return bases;
 }
 
 MIA_HD inline int ma_ends_len_bin(bool rc, int64_t length) {

@@ -17,13 +17,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#ifndef MIA_HD
-#if defined(__HIPCC__)
-#define MIA_HD __host__ __device__
-#else
-#define MIA_HD
-#endif
-#endif
+#include "ma_records.h"
 
 #if defined(__clang__)
 #define MA_PROF_UNROLL _Pragma("unroll")
@@ -38,20 +32,19 @@ namespace mia {
 constexpr int MA_PROF_DEPTHS = 31, MA_PROF_CLASSES = 5, MA_PROF_MIDDLE = 15;
 constexpr int MA_PROF_COUNTS = MA_PROF_DEPTHS * MA_PROF_CLASSES * MA_PROF_CLASSES;                 // 775
 constexpr int MA_PROF_DEL = MA_PROF_COUNTS, MA_PROF_BAD = MA_PROF_DEL + MA_PROF_DEPTHS, MA_PROF_BEYOND = MA_PROF_BAD + 1, MA_PROF_BINS = MA_PROF_BEYOND + 1;   // 808
-constexpr int MA_PROF_LANE = 16;           // flat positions of one stretch: one 16-byte word of SEQ and one of SMP
+constexpr int MA_PROF_LANE = MA_REC_LANE;  // flat positions of one stretch: one 16-byte word of SEQ and one of SMP
 constexpr int MA_PROF_HOT = 4;             // (MIDDLE, X, X) for X in ACGT: where most events of a real assembly fall
 
-// The records of a .maln as mia_hip_ma_tally keeps them, the reference and the selection.
-struct MaProfView {
-  int64_t n, T;              // records; T = col_off[n] flat positions
-  int32_t L;
-  const int32_t* start;      // [n]
-  const uint8_t* revcom;     // [n]
-  const int64_t* col_off;    // [n+1]: record r owns seq / smp[col_off[r] .. col_off[r+1]) = columns start .. end
-  const char* seq;           // 16-byte aligned and readable up to the next multiple of MA_PROF_LANE behind T (what lies there is not looked at)
-  const char* smp;           // likewise
+// The records (ma_records.h: seq and smp are loaded in whole 16-byte words), the reference and the selection.
+struct MaProfView : MaRecords {
+  int64_t T;                 // col_off[n] flat positions
   const char* ref;           // [L]
   const uint8_t* use;        // [n]: 0 = the record is left out; NULL = every record counts
+  MaProfView(const MaRecords& recs, int64_t T, const char* ref, const uint8_t* use) : MaRecords(recs), T(T), ref(ref), use(use) {}
+  // ... or from the arrays this export reads alone, for a caller that holds no more (the host drivers): the rest of MaRecords is null
+  MaProfView(int64_t n, int64_t T, int32_t L, const int32_t* start, const uint8_t* revcom, const int64_t* col_off, const char* seq, const char* smp,
+             const char* ref, const uint8_t* use)
+      : MaRecords{n, L, start, revcom, col_off, seq, nullptr, nullptr, nullptr, nullptr, nullptr, smp}, T(T), ref(ref), use(use) {}
 };
 
 MIA_HD inline int ma_prof_class(char c) {
@@ -94,26 +87,19 @@ MIA_HD inline int64_t ma_prof_record_of(const MaProfView& v, int64_t pos) {
   return lo;
 }
 
-struct MaProfWord { uint32_t w[4]; };
-MIA_HD inline MaProfWord ma_prof_load(const char* p) {       // (p: 16-byte aligned)
-  MaProfWord x;
-  __builtin_memcpy(&x, __builtin_assume_aligned(p, 16), sizeof x);
-  return x;
-}
-
 // The stretch of flat positions base .. base + MA_PROF_LANE - 1 (base a multiple of MA_PROF_LANE): emit(bin) is called
 // MA_PROF_LANE times, in order, with the position's bin -- or with -1 for a position at or behind T and for a column of a record
 // that is left out.  One bisection per stretch, then forward from record to record.  Every caller makes all MA_PROF_LANE calls
 // whatever its base, so a wavefront's lanes reach each of them together.
 template <class Emit>
 MIA_HD inline void ma_prof_stretch(const MaProfView& v, int64_t base, Emit&& emit) {
-  MaProfWord sq{{0, 0, 0, 0}}, sm{{0, 0, 0, 0}};
+  MaRecWord sq{{0, 0, 0, 0}}, sm{{0, 0, 0, 0}};
   int64_t r = 0, end = 0, o0 = 0;
   int32_t start = 0;
   bool rc = false, used = false;
   if (base < v.T) {
-    sq = ma_prof_load(v.seq + base);
-    sm = ma_prof_load(v.smp + base);
+    sq = ma_rec_load(v.seq + base);
+    sm = ma_rec_load(v.smp + base);
     r = ma_prof_record_of(v, base);
     o0 = v.col_off[r]; end = v.col_off[r + 1];
     start = v.start[r]; rc = v.revcom[r] != 0; used = !v.use || v.use[r] != 0;

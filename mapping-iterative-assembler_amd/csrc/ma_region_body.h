@@ -6,32 +6,24 @@
 #include <stdint.h>
 #include <string.h>
 
-#ifndef MIA_HD
-#if defined(__HIPCC__)
-#define MIA_HD __host__ __device__
-#else
-#define MIA_HD
-#endif
-#endif
+#include "ma_records.h"
 
 namespace mia {
 
-// The records of a .maln as mia_hip_ma_tally receives them, the INS_POS pairs listed by record, and one region.
-struct MaRegionView {
-  int64_t n;
-  const int32_t* start;      // [n]
-  const int64_t* col_off;    // [n+1]: record r owns seq[col_off[r] .. col_off[r+1]) = columns start .. end
-  const char* seq;
-  const int32_t* rec_ins;    // [n+1]: record r owns ins_list[rec_ins[r] .. rec_ins[r+1])
-  const int32_t* ins_list;   // pair numbers, by record, ascending ins_pos; pairs of one position in the order they were given
-  const int32_t* ins_pos;    // per pair: the insert sits in front of column start + ins_pos
-  const int64_t* ins_off;    // per pair (+1): its bases are ins_bases[ins_off[e] .. ins_off[e+1])
-  const char* ins_bases;
+// The records (ma_records.h) and one region.
+struct MaRegionView : MaRecords {
   const int32_t* gaps;       // [L]: ref->gaps
   int32_t first, last;       // 0-based inclusive reference columns
   // colmap[k], k = 0 .. last - first + 1: text offset of the first insert column in front of reference column first + k
   // (every column p owns gaps[p] insert columns, p == 0 and p == first included); colmap[last - first + 1] = the row's width
   const int64_t* colmap;
+  MaRegionView(const MaRecords& recs, const int32_t* gaps, int32_t first, int32_t last, const int64_t* colmap)
+      : MaRecords(recs), gaps(gaps), first(first), last(last), colmap(colmap) {}
+  // ... or from the arrays this export reads alone, for a caller that holds no more (the host drivers): the rest of MaRecords is null, L 0
+  MaRegionView(int64_t n, const int32_t* start, const int64_t* col_off, const char* seq, const int32_t* rec_ins, const int32_t* ins_list,
+               const int32_t* ins_pos, const int64_t* ins_off, const char* ins_bases, const int32_t* gaps, int32_t first, int32_t last, const int64_t* colmap)
+      : MaRecords{n, 0, start, nullptr, col_off, seq, rec_ins, ins_list, ins_pos, ins_off, ins_bases, nullptr}, gaps(gaps), first(first), last(last),
+        colmap(colmap) {}
 };
 
 MIA_HD inline int ma_region_gap(int32_t g) { return g > 0 ? g : 0; }
@@ -40,16 +32,6 @@ MIA_HD inline int ma_region_gap(int32_t g) { return g > 0 ? g : 0; }
 MIA_HD inline bool ma_region_overlaps(int32_t start, int32_t end, int32_t first, int32_t last) { return start <= last && end >= first; }
 
 MIA_HD inline int32_t ma_region_end(const MaRegionView& v, int64_t r) { return v.start[r] + (int32_t)(v.col_off[r + 1] - v.col_off[r]) - 1; }
-
-// aln_seq->ins[pos]: read_ma lets a later pair of the same position replace an earlier one (src/map_alignment.c:602-605)
-MIA_HD inline int ma_region_insert(const MaRegionView& v, int64_t r, int32_t pos, const char** bases) {
-  for (int32_t k = v.rec_ins[r + 1] - 1; k >= v.rec_ins[r]; k--) {
-    const int32_t e = v.ins_list[k];
-    if (v.ins_pos[e] == pos) { *bases = v.ins_bases + v.ins_off[e]; return (int)(v.ins_off[e + 1] - v.ins_off[e]); }
-  }
-  *bases = nullptr;
-  return 0;
-}
 
 // '.' over row[a .. b): lane `lane` of `nlanes` takes its share; whole 16-byte words where the address allows
 MIA_HD inline void ma_region_dots(char* row, int64_t a, int64_t b, int lane, int nlanes) {
@@ -80,7 +62,7 @@ MIA_HD inline void ma_region_column(const MaRegionView& v, int64_t r, int32_t k,
       for (int i = 0; i < g; i++) out[i] = '.';
     } else {
       const char* bases = nullptr;
-      int len = ma_region_insert(v, r, p - s, &bases);
+      int len = ma_rec_insert(v, r, p - s, &bases);
       if (len > g) len = g;                      // (an insert longer than ref->gaps says: the reference writes past its row)
       for (int i = 0; i < len; i++) out[i] = bases[i];
       for (int i = len; i < g; i++) out[i] = '-';

@@ -15,13 +15,7 @@
 #pragma once
 #include <stdint.h>
 
-#ifndef MIA_HD
-#if defined(__HIPCC__)
-#define MIA_HD __host__ __device__
-#else
-#define MIA_HD
-#endif
-#endif
+#include "ma_records.h"
 
 namespace mia {
 
@@ -31,23 +25,17 @@ constexpr int MA_SAM_NONE = 0, MA_SAM_M = 1, MA_SAM_I = 2, MA_SAM_D = 3, MA_SAM_
 #define MA_SAM_EMPTY "*\t*\t0\t0\t*"
 constexpr int MA_SAM_MID_BYTES = 7, MA_SAM_EMPTY_BYTES = 9;
 
-// The records of a .maln as mia_hip_ma_tally keeps them (MaAceView's arrays), the reference, and the index of every record's
-// inserts that ma_sam_index writes.
-struct MaSamView {
-  int64_t n;
-  int32_t L;
-  const int32_t* start;      // [n]
-  const int64_t* col_off;    // [n+1]: record r owns seq[col_off[r] .. col_off[r+1]) = columns start .. end
-  const char* seq;
-  const int32_t* rec_ins;    // [n+1]: record r owns ins_list[rec_ins[r] .. rec_ins[r+1])
-  const int32_t* ins_list;   // pair numbers, by record, ascending ins_pos; pairs of one position in the order they were given
-  const int32_t* ins_pos;
-  const int64_t* ins_off;    // per pair (+1): its characters are ins_bases[ins_off[e] .. ins_off[e+1])
-  const char* ins_bases;
+// The records (ma_records.h), the reference, and the index of every record's inserts that ma_sam_index writes.
+struct MaSamView : MaRecords {
   const char* ref;           // [L]
   // [pairs + n + 1]: record r owns cum[rec_ins[r] + r .. rec_ins[r+1] + r], one word per listed pair and one behind them:
   // word j = the insert characters the walk holds in front of pair j's own (pairs that do not count hold none)
   int64_t* cum;
+  MaSamView(const MaRecords& recs, const char* ref, int64_t* cum) : MaRecords(recs), ref(ref), cum(cum) {}
+  // ... or from the arrays this export reads alone, for a caller that holds no more (the host drivers): the rest of MaRecords is null
+  MaSamView(int64_t n, int32_t L, const int32_t* start, const int64_t* col_off, const char* seq, const int32_t* rec_ins, const int32_t* ins_list,
+            const int32_t* ins_pos, const int64_t* ins_off, const char* ins_bases, const char* ref, int64_t* cum)
+      : MaRecords{n, L, start, nullptr, col_off, seq, rec_ins, ins_list, ins_pos, ins_off, ins_bases, nullptr}, ref(ref), cum(cum) {}
 };
 
 MIA_HD inline int64_t ma_sam_ncols(const MaSamView& v, int64_t r) { return v.col_off[r + 1] - v.col_off[r]; }
@@ -60,8 +48,8 @@ MIA_HD inline int64_t ma_sam_index(const MaSamView& v, int64_t r) {
   int64_t run = 0;
   for (int32_t j = 0; j < cnt; j++) {
     cum[j] = run;
-    const int32_t e = v.ins_list[lo + j], pos = v.ins_pos[e];
-    if (pos >= 0 && pos < ncols && (j + 1 == cnt || v.ins_pos[v.ins_list[lo + j + 1]] != pos)) run += v.ins_off[e + 1] - v.ins_off[e];
+    const int32_t e = v.ins_list[lo + j];
+    if (ma_rec_pair_counts(v, lo + j, lo + cnt, ncols)) run += v.ins_off[e + 1] - v.ins_off[e];
   }
   cum[cnt] = run;
   return ncols + run;

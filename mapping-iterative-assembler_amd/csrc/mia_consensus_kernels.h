@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ma_records.h"
 #include "mia_kernels.h"
 #include "mia_layout.h"
 
@@ -1971,15 +1972,7 @@ __global__ __launch_bounds__(256) void k_tally_reduce(TallyBuf tb, int32_t nb, c
 }
 
 // ---- ma: tally of stored AlnSeq records (show_consensus, src/map_alignment.c:139-170) -------------
-// One record per wavefront, one column per lane.  No `dropped` test: ma counts every record.
-struct MaRecords {
-  int64_t n;
-  const int32_t* start;
-  const uint8_t* revcom;
-  const int64_t* col_off;   // [n+1]
-  const char* seq;
-  const char* smp;
-};
+// One record per wavefront, one column per lane (MaRecords: ma_records.h).  No `dropped` test: ma counts every record.
 __device__ __forceinline__ int ma_code(char b) {   // add_base / base2inx (src/map_align.c:16-29,229-263)
   return b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : b == '-' ? 5 : 4;
 }

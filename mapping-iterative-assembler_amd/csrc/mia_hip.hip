@@ -257,28 +257,32 @@ struct mia_hip_ctx {
   DevBuf<int64_t> d_ma_coff, d_ma_ioff, d_ma_colmap, d_ma_rows;
   DevBuf<char> d_ma_seq, d_ma_ib, d_ma_text;
   DevBuf<unsigned long long> d_ma_ctl;
-  int32_t ma_first = 0, ma_last = -1; int64_t ma_rows = 0, ma_width = 0; bool ma_region_done = false;
+  // what the exports' calls found, per export (the big results are further down): mia_hip_ma_tally forgets all of it at once
+  struct MaOut {
+    bool region_done = false, ace_done = false, sam_done = false, prof_done = false, ends_done = false, cols_done = false;
+    int32_t first = 0, last = -1; int64_t rows = 0, width = 0, ace_bytes = 0, sam_bytes = 0;
+  } ma_out;
   // ... and for mia_hip_ma_ace: whether the job has an ACE export at all (GAPS, the records' columns), the running sum of ref->gaps,
   // per record the AF position, the padded length and the offset of its text, the text
-  bool ma_ace_gaps_ok = false, ma_ace_cols_ok = false, ma_ace_done = false; int64_t ma_ace_bytes = 0;
+  bool ma_ace_gaps_ok = false, ma_ace_cols_ok = false;
   DevBuf<int64_t> d_ace_g, d_ace_af, d_ace_len, d_ace_off; DevBuf<char> d_ace_body;
   // ... and for mia_hip_ma_sam: whether GAPS is well-formed, the reference, the index of the records' inserts, per record NM, the bytes
   // of its CIGAR and the offset of its body, the bodies, the layout's control words
-  bool ma_sam_gaps_ok = false, ma_sam_done = false; int64_t ma_sam_bytes = 0;
+  bool ma_sam_gaps_ok = false;
   DevBuf<char> d_sam_ref, d_sam_body; DevBuf<int64_t> d_sam_cum, d_sam_cig, d_sam_off; DevBuf<int32_t> d_sam_nm;
   DevBuf<unsigned long long> d_sam_ctl;
   // ... and for mia_hip_ma_profile: strands and depth codes stay behind the tally as well; the reference, the selection, the 808 bins
   // (ma_profile_body.h) on the device and, after the call, here
   DevBuf<uint8_t> d_ma_rev, d_prof_use; DevBuf<char> d_ma_smp, d_prof_ref; DevBuf<unsigned long long> d_prof_bins;
-  bool ma_prof_done = false; int64_t ma_cols = 0; int64_t ma_prof_bins[MA_PROF_BINS] = {0};
+  int64_t ma_cols = 0; int64_t ma_prof_bins[MA_PROF_BINS] = {0};
   // ... and for mia_hip_ma_ends, which shares the reference's and the selection's buffers with the profile (either call's results are on
   // the host when it returns): the segment characters, the 1 267 bins (ma_ends_body.h) on the device and, after the call, here
   DevBuf<uint8_t> d_ends_seg; DevBuf<unsigned long long> d_ends_bins;
-  bool ma_ends_done = false; int64_t ma_ends_bins[MA_ENDS_BINS] = {0};
+  int64_t ma_ends_bins[MA_ENDS_BINS] = {0};
   // ... and for mia_hip_ma_cols, which takes the segments and the selection into the same buffers: the sixteen words per reference
   // column (ma_cols_body.h) and the two counts of what lies on no column, on the device and, after the call, here
   DevBuf<uint32_t> d_cols_tab; DevBuf<unsigned long long> d_cols_out;
-  bool ma_cols_done = false; std::vector<int32_t> ma_cols_tab;
+  std::vector<int32_t> ma_cols_tab;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------

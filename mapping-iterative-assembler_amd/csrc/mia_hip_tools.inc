@@ -87,6 +87,25 @@ extern "C" int mia_hip_trim_stats(mia_hip_ctx* ctx, int64_t* exact_reruns) {
 }
 
 // ---- ma -------------------------------------------------------------------------------------
+// The records the last mia_hip_ma_tally left on the device (ma_records.h): every view of an export is built on this.
+static MaRecords ma_records(const mia_hip_ctx* ctx) {
+  return MaRecords{ctx->ma_n, ctx->ma_L, ctx->d_ma_start, ctx->d_ma_rev, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos,
+                   ctx->d_ma_ioff, ctx->d_ma_ib, ctx->d_ma_smp};
+}
+
+// What the statistics calls (profile, ends, cols) share: the segment characters and the selection `use` go up into the context's
+// buffers (NULL stays NULL: every record is whole, every record counts); used = the records that count.
+struct MaSelection { const uint8_t *segment, *use; int64_t used; };
+static int ma_selection(mia_hip_ctx* ctx, const uint8_t* segment, const uint8_t* use, MaSelection* sel) {
+  const int64_t n = ctx->ma_n;
+  if (dev_ensure(ctx, ctx->d_ends_seg, n + 1) || dev_ensure(ctx, ctx->d_prof_use, n + 1)) return MIA_HIP_ERR_NOMEM;
+  if (segment && n > 0) HIPCHK(hipMemcpyAsync(ctx->d_ends_seg, segment, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (use && n > 0) HIPCHK(hipMemcpyAsync(ctx->d_prof_use, use, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  *sel = MaSelection{segment ? (const uint8_t*)ctx->d_ends_seg : nullptr, use ? (const uint8_t*)ctx->d_prof_use : nullptr, 0};
+  for (int64_t r = 0; r < n; r++) sel->used += !use || use[r] ? 1 : 0;
+  return MIA_HIP_OK;
+}
+
 extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t* gaps, int64_t n, const int32_t* start,
                                 const uint8_t* revcom, const int64_t* col_off, const char* seq, const char* smp, int64_t n_ins,
                                 const int32_t* ins_record, const int32_t* ins_pos, const int64_t* ins_off, const char* ins_bases) {
@@ -111,45 +130,31 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   if (rc) return rc;
   const int Lp = ctx->tb.Lp;
   const int64_t chars = n ? col_off[n] : 0;
-  // the INS_POS pairs by record (mia_hip_ma_region and mia_hip_ma_ace fetch a record's own range): a stable counting sort of the
-  // pair numbers, and inside a record ascending positions (ma_ace_order_inserts: a record's pair is found by bisection)
+  // the INS_POS pairs by record (the exports fetch a record's own range, and its pair of a position by bisection)
   if (n > INT32_MAX - 1 || n_ins > INT32_MAX - 1) { ctx->err = "ma_tally: more than 2^31 records or INS_POS pairs"; return MIA_HIP_ERR_ARG; }
-  std::vector<int32_t> rec_ins((size_t)n + 1, 0), ins_list((size_t)n_ins);
-  for (int64_t e = 0; e < n_ins; e++) rec_ins[(size_t)ins_record[e] + 1]++;
-  for (int64_t r = 0; r < n; r++) rec_ins[(size_t)r + 1] += rec_ins[(size_t)r];
-  {
-    std::vector<int32_t> cursor(rec_ins.begin(), rec_ins.end() - 1);
-    for (int64_t e = 0; e < n_ins; e++) ins_list[(size_t)cursor[(size_t)ins_record[e]]++] = (int32_t)e;
-    for (int64_t r = 0; r < n; r++)
-      ma_ace_order_inserts(ins_list.data() + rec_ins[(size_t)r], rec_ins[(size_t)r + 1] - rec_ins[(size_t)r], ins_pos);
-  }
+  std::vector<int32_t> rec_ins, ins_list;
+  ma_list_pairs(n, n_ins, ins_record, ins_pos, &rec_ins, &ins_list);
   // The records stay on the device behind this call (mia_hip_ma_region reads them): buffers of the context, made here, before anything
   // is queued.  Strand and depth codes stay for mia_hip_ma_profile; the pairs' record numbers are needed by the tally alone.  SEQ and
-  // SMP are readable up to the next multiple of MA_PROF_LANE behind their last character (k_ma_profile loads them in words of that size),
+  // SMP are readable up to the next multiple of MA_REC_LANE behind their last character (k_ma_profile loads them in words of that size),
   // and so are the pairs' characters (k_ma_ends counts their '-' in such words too).
   ctx->ma_resident = false;
-  ctx->ma_region_done = false;
-  ctx->ma_ace_done = false;
+  ctx->ma_out = {};
   ctx->ma_ace_gaps_ok = ma_ace_gaps_ok(gaps, ref_len);
   ctx->ma_ace_cols_ok = cols_ok;
-  ctx->ma_sam_done = false;
   ctx->ma_sam_gaps_ok = ma_sam_gaps_ok(gaps, ref_len);
-  ctx->ma_prof_done = false;
-  ctx->ma_ends_done = false;
-  ctx->ma_cols_done = false;
   DevBuf<int32_t> d_irec;   // every temporary is released on any return
   int rcx = dev_alloc(ctx, ctx->d_ma_start, n + 1) | dev_alloc(ctx, ctx->d_ma_rev, n + 1) | dev_alloc(ctx, ctx->d_ma_coff, n + 1) |
-            dev_alloc(ctx, ctx->d_ma_seq, chars + MA_PROF_LANE) | dev_alloc(ctx, ctx->d_ma_smp, chars + MA_PROF_LANE) | dev_alloc(ctx, d_irec, n_ins + 1) |
+            dev_alloc(ctx, ctx->d_ma_seq, chars + MA_REC_LANE) | dev_alloc(ctx, ctx->d_ma_smp, chars + MA_REC_LANE) | dev_alloc(ctx, d_irec, n_ins + 1) |
             dev_alloc(ctx, ctx->d_ma_ipos, n_ins + 1) | dev_alloc(ctx, ctx->d_ma_ioff, n_ins + 1) |
-            dev_alloc(ctx, ctx->d_ma_ib, ins_chars + MA_PROF_LANE) | dev_alloc(ctx, ctx->d_ma_gaps, ref_len) |
+            dev_alloc(ctx, ctx->d_ma_ib, ins_chars + MA_REC_LANE) | dev_alloc(ctx, ctx->d_ma_gaps, ref_len) |
             dev_alloc(ctx, ctx->d_ma_rec_ins, n + 1) | dev_alloc(ctx, ctx->d_ma_ins_list, n_ins + 1) |
             dev_alloc(ctx, ctx->d_ma_colmap, (int64_t)ref_len + 1) | dev_alloc(ctx, ctx->d_ma_rows, n + 1) |
             dev_alloc(ctx, ctx->d_ma_ctl, (int64_t)MAR_STATE + n / MAR_PER_WG + 2);
   if (rcx) return MIA_HIP_ERR_NOMEM;
-  int32_t* const d_start = ctx->d_ma_start; int32_t* const d_ipos = ctx->d_ma_ipos;
-  int64_t* const d_coff = ctx->d_ma_coff; int64_t* const d_ioff = ctx->d_ma_ioff;
-  char* const d_seq = ctx->d_ma_seq; char* const d_ib = ctx->d_ma_ib;
-  uint8_t* const d_rev = ctx->d_ma_rev; char* const d_smp = ctx->d_ma_smp;
+  ctx->ma_n = n;                                   // (nothing reads them before ma_resident is set again)
+  ctx->ma_n_ins = n_ins;
+  ctx->ma_L = ref_len;
   hipError_t e = hipSuccess;
   auto up = [&](void* d, const void* h, size_t b) { if (e == hipSuccess && b) e = hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream); };
   auto zero = [&](void* d, size_t b) { if (e == hipSuccess) e = hipMemsetAsync(d, 0, b, ctx->stream); };
@@ -158,19 +163,22 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   zero(ctx->tb.n_events, 4);
   zero(ctx->tb.flags, 4);
   up(ctx->tb.gaps, gaps, (size_t)ref_len * 4);
-  up(d_start, start, (size_t)n * 4); up(d_rev, revcom, (size_t)n); up(d_coff, col_off, (size_t)(n + 1) * 8);
-  up(d_seq, seq, (size_t)chars); up(d_smp, smp, (size_t)chars);
-  if (n_ins) { up(d_irec, ins_record, (size_t)n_ins * 4); up(d_ipos, ins_pos, (size_t)n_ins * 4); up(d_ioff, ins_off, (size_t)(n_ins + 1) * 8); up(d_ib, ins_bases, (size_t)ins_chars); }
+  up(ctx->d_ma_start, start, (size_t)n * 4); up(ctx->d_ma_rev, revcom, (size_t)n); up(ctx->d_ma_coff, col_off, (size_t)(n + 1) * 8);
+  up(ctx->d_ma_seq, seq, (size_t)chars); up(ctx->d_ma_smp, smp, (size_t)chars);
+  if (n_ins) {
+    up(d_irec, ins_record, (size_t)n_ins * 4); up(ctx->d_ma_ipos, ins_pos, (size_t)n_ins * 4); up(ctx->d_ma_ioff, ins_off, (size_t)(n_ins + 1) * 8);
+    up(ctx->d_ma_ib, ins_bases, (size_t)ins_chars);
+  }
   up(ctx->d_ma_gaps, gaps, (size_t)ref_len * 4);
   up(ctx->d_ma_rec_ins, rec_ins.data(), (size_t)(n + 1) * 4);
   up(ctx->d_ma_ins_list, ins_list.data(), (size_t)n_ins * 4);
   if (e == hipSuccess && n > 0) {
-    MaRecords mr{n, d_start, d_rev, d_coff, d_seq, d_smp};
+    const MaRecords mr = ma_records(ctx);
     if (stage_launch(ctx, STG_MA_TALLY, k_ma_tally, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream, mr, (const int32_t*)ctx->d_pssm, ctx->tb))
       return MIA_HIP_ERR_NOMEM;
     if (n_ins > 0)
-      hipLaunchKernelGGL(k_ma_ins_events, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, ctx->stream, mr, n_ins, d_irec, d_ipos, d_ioff,
-                         d_ib, ctx->tb);
+      hipLaunchKernelGGL(k_ma_ins_events, dim3((unsigned)((n_ins + 255) / 256)), dim3(256), 0, ctx->stream, mr, n_ins, d_irec, mr.ins_pos, mr.ins_off,
+                         mr.ins_bases, ctx->tb);
     e = hipGetLastError();
   }
   uint32_t flags = 0;
@@ -184,9 +192,6 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->tallied = true;
   ctx->consensus_done = false;
   ctx->ma_resident = true;
-  ctx->ma_n = n;
-  ctx->ma_n_ins = n_ins;
-  ctx->ma_L = ref_len;
   ctx->ma_cols = n == 0 ? 0 : col_off[0] == 0 ? chars : -1;         // (mia_hip_ma_profile takes flat position 0 as record 0's first column)
   return MIA_HIP_OK;
 }
@@ -197,11 +202,10 @@ extern "C" int mia_hip_ma_region(mia_hip_ctx* ctx, int32_t first, int32_t last, 
   if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_region"; return MIA_HIP_ERR_STATE; }
   if (first <= last && (first < 0 || last >= ctx->ma_L)) { ctx->err = "ma_region: the region reaches outside the reference"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->ma_region_done = false;
+  ctx->ma_out.region_done = false;
   const int64_t n = ctx->ma_n;
   const int32_t n_wgs = (int32_t)((n + MAR_PER_WG - 1) / MAR_PER_WG);
-  MaRegionView v{n, ctx->d_ma_start, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos, ctx->d_ma_ioff, ctx->d_ma_ib,
-                 ctx->d_ma_gaps, first, last, ctx->d_ma_colmap};
+  MaRegionView v{ma_records(ctx), ctx->d_ma_gaps, first, last, ctx->d_ma_colmap};
   HIPCHK(hipMemsetAsync(ctx->d_ma_ctl, 0, ((size_t)MAR_STATE + (size_t)n_wgs) * 8, ctx->stream));
   if (stage_launch(ctx, STG_MA_SELECT, k_ma_region_select, dim3((unsigned)n_wgs + 1), dim3(MAR_THREADS), 0, ctx->stream, v, n_wgs, ctx->d_ma_ctl,
                    ctx->d_ma_colmap, ctx->d_ma_rows))
@@ -221,8 +225,8 @@ extern "C" int mia_hip_ma_region(mia_hip_ctx* ctx, int32_t first, int32_t last, 
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
-  ctx->ma_first = first; ctx->ma_last = last; ctx->ma_rows = rows; ctx->ma_width = w;
-  ctx->ma_region_done = true;
+  ctx->ma_out.first = first; ctx->ma_out.last = last; ctx->ma_out.rows = rows; ctx->ma_out.width = w;
+  ctx->ma_out.region_done = true;
   *n_rows = rows;
   *width = w;
   return MIA_HIP_OK;
@@ -230,12 +234,12 @@ extern "C" int mia_hip_ma_region(mia_hip_ctx* ctx, int32_t first, int32_t last, 
 
 extern "C" int mia_hip_get_ma_region(mia_hip_ctx* ctx, int64_t* rows, char* text, int64_t cap_rows) {
   if (!ctx) return MIA_HIP_ERR_ARG;
-  if (!ctx->ma_resident || !ctx->ma_region_done) { ctx->err = "ma_region first"; return MIA_HIP_ERR_STATE; }
-  if (cap_rows < ctx->ma_rows) { ctx->err = "get_ma_region: buffers too small"; return MIA_HIP_ERR_ARG; }
+  if (!ctx->ma_resident || !ctx->ma_out.region_done) { ctx->err = "ma_region first"; return MIA_HIP_ERR_STATE; }
+  if (cap_rows < ctx->ma_out.rows) { ctx->err = "get_ma_region: buffers too small"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
-  if (rows && ctx->ma_rows > 0) HIPCHK(hipMemcpyAsync(rows, ctx->d_ma_rows, (size_t)ctx->ma_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (text && ctx->ma_rows > 0 && ctx->ma_width > 0)
-    HIPCHK(hipMemcpyAsync(text, ctx->d_ma_text, (size_t)(ctx->ma_rows * ctx->ma_width), hipMemcpyDeviceToHost, ctx->stream));
+  if (rows && ctx->ma_out.rows > 0) HIPCHK(hipMemcpyAsync(rows, ctx->d_ma_rows, (size_t)ctx->ma_out.rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (text && ctx->ma_out.rows > 0 && ctx->ma_out.width > 0)
+    HIPCHK(hipMemcpyAsync(text, ctx->d_ma_text, (size_t)(ctx->ma_out.rows * ctx->ma_out.width), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }
@@ -247,12 +251,12 @@ extern "C" int mia_hip_ma_ace(mia_hip_ctx* ctx, int64_t* n_records, int64_t* bod
   if (!ctx->ma_ace_gaps_ok) { ctx->err = "ma_ace: GAPS opens insert columns in front of column 0, or holds a negative value: no ACE export"; return MIA_HIP_ERR_ARG; }
   if (!ctx->ma_ace_cols_ok) { ctx->err = "ma_ace: a record reaches past the reference"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->ma_ace_done = false;
+  ctx->ma_out.ace_done = false;
   const int64_t n = ctx->ma_n;
   const int32_t L = ctx->ma_L, n_wgs = (int32_t)((n + MAR_PER_WG - 1) / MAR_PER_WG);
   if (dev_ensure(ctx, ctx->d_ace_g, (int64_t)L + 2) || dev_ensure(ctx, ctx->d_ace_af, n + 1) || dev_ensure(ctx, ctx->d_ace_len, n + 1) || dev_ensure(ctx, ctx->d_ace_off, n + 1))
     return MIA_HIP_ERR_NOMEM;
-  MaAceView v{n, ctx->d_ma_start, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos, ctx->d_ma_ioff, ctx->d_ma_ib, ctx->d_ace_g};
+  MaAceView v{ma_records(ctx), ctx->d_ace_g};
   hipLaunchKernelGGL(k_ma_ace_gaps, dim3(1), dim3(MAA_SCAN_THREADS), 0, ctx->stream, (const int32_t*)ctx->d_ma_gaps, L, ctx->d_ace_g);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemsetAsync(ctx->d_ma_ctl, 0, ((size_t)MAR_STATE + (size_t)n_wgs) * 8, ctx->stream));
@@ -276,8 +280,8 @@ extern "C" int mia_hip_ma_ace(mia_hip_ctx* ctx, int64_t* n_records, int64_t* bod
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
-  ctx->ma_ace_bytes = bytes;
-  ctx->ma_ace_done = true;
+  ctx->ma_out.ace_bytes = bytes;
+  ctx->ma_out.ace_done = true;
   *n_records = n;
   *body_bytes = bytes;
   return MIA_HIP_OK;
@@ -285,14 +289,14 @@ extern "C" int mia_hip_ma_ace(mia_hip_ctx* ctx, int64_t* n_records, int64_t* bod
 
 extern "C" int mia_hip_get_ma_ace(mia_hip_ctx* ctx, int64_t* af_pos, int64_t* padded_len, int64_t* body_off, char* body, int64_t cap_bytes) {
   if (!ctx) return MIA_HIP_ERR_ARG;
-  if (!ctx->ma_resident || !ctx->ma_ace_done) { ctx->err = "ma_ace first"; return MIA_HIP_ERR_STATE; }
-  if (body && cap_bytes < ctx->ma_ace_bytes) { ctx->err = "get_ma_ace: buffer too small"; return MIA_HIP_ERR_ARG; }
+  if (!ctx->ma_resident || !ctx->ma_out.ace_done) { ctx->err = "ma_ace first"; return MIA_HIP_ERR_STATE; }
+  if (body && cap_bytes < ctx->ma_out.ace_bytes) { ctx->err = "get_ma_ace: buffer too small"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = ctx->ma_n;
   if (af_pos && n > 0) HIPCHK(hipMemcpyAsync(af_pos, ctx->d_ace_af, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (padded_len && n > 0) HIPCHK(hipMemcpyAsync(padded_len, ctx->d_ace_len, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (body_off) HIPCHK(hipMemcpyAsync(body_off, ctx->d_ace_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (body && ctx->ma_ace_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_ace_body, (size_t)ctx->ma_ace_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (body && ctx->ma_out.ace_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_ace_body, (size_t)ctx->ma_out.ace_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }
@@ -304,15 +308,14 @@ extern "C" int mia_hip_ma_sam(mia_hip_ctx* ctx, const char* ref_seq, int64_t* n_
   if (!ref_seq) { ctx->err = "ma_sam: no reference sequence"; return MIA_HIP_ERR_ARG; }
   if (!ctx->ma_sam_gaps_ok) { ctx->err = "ma_sam: GAPS holds a negative value"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->ma_sam_done = false;
+  ctx->ma_out.sam_done = false;
   const int64_t n = ctx->ma_n;
   const int32_t L = ctx->ma_L, n_wgs = (int32_t)((n + MAS_PER_WG - 1) / MAS_PER_WG);
   if (dev_ensure(ctx, ctx->d_sam_ref, (int64_t)L) || dev_ensure(ctx, ctx->d_sam_cum, ctx->ma_n_ins + n + 1) || dev_ensure(ctx, ctx->d_sam_nm, n + 1) ||
       dev_ensure(ctx, ctx->d_sam_cig, n + 1) || dev_ensure(ctx, ctx->d_sam_off, n + 1) || dev_ensure(ctx, ctx->d_sam_ctl, (int64_t)MAR_STATE + n_wgs + 1))
     return MIA_HIP_ERR_NOMEM;
   HIPCHK(hipMemcpyAsync(ctx->d_sam_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
-  MaSamView v{n, L, ctx->d_ma_start, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos, ctx->d_ma_ioff, ctx->d_ma_ib,
-              ctx->d_sam_ref, ctx->d_sam_cum};
+  MaSamView v{ma_records(ctx), ctx->d_sam_ref, ctx->d_sam_cum};
   HIPCHK(hipMemsetAsync(ctx->d_sam_ctl, 0, ((size_t)MAR_STATE + (size_t)n_wgs) * 8, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_sam_off, 0, 8, ctx->stream));         // (no records: the one offset there is)
   if (n_wgs > 0) {
@@ -334,8 +337,8 @@ extern "C" int mia_hip_ma_sam(mia_hip_ctx* ctx, const char* ref_seq, int64_t* n_
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
-  ctx->ma_sam_bytes = bytes;
-  ctx->ma_sam_done = true;
+  ctx->ma_out.sam_bytes = bytes;
+  ctx->ma_out.sam_done = true;
   *n_records = n;
   *body_bytes = bytes;
   return MIA_HIP_OK;
@@ -343,13 +346,13 @@ extern "C" int mia_hip_ma_sam(mia_hip_ctx* ctx, const char* ref_seq, int64_t* n_
 
 extern "C" int mia_hip_get_ma_sam(mia_hip_ctx* ctx, int32_t* nm, int64_t* body_off, char* body, int64_t cap_bytes) {
   if (!ctx) return MIA_HIP_ERR_ARG;
-  if (!ctx->ma_resident || !ctx->ma_sam_done) { ctx->err = "ma_sam first"; return MIA_HIP_ERR_STATE; }
-  if (body && cap_bytes < ctx->ma_sam_bytes) { ctx->err = "get_ma_sam: buffer too small"; return MIA_HIP_ERR_ARG; }
+  if (!ctx->ma_resident || !ctx->ma_out.sam_done) { ctx->err = "ma_sam first"; return MIA_HIP_ERR_STATE; }
+  if (body && cap_bytes < ctx->ma_out.sam_bytes) { ctx->err = "get_ma_sam: buffer too small"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = ctx->ma_n;
   if (nm && n > 0) HIPCHK(hipMemcpyAsync(nm, ctx->d_sam_nm, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (body_off) HIPCHK(hipMemcpyAsync(body_off, ctx->d_sam_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (body && ctx->ma_sam_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_sam_body, (size_t)ctx->ma_sam_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (body && ctx->ma_out.sam_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_sam_body, (size_t)ctx->ma_out.sam_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }
@@ -361,16 +364,16 @@ extern "C" int mia_hip_ma_profile(mia_hip_ctx* ctx, const char* ref_seq, const u
   if (!ref_seq) { ctx->err = "ma_profile: no reference sequence"; return MIA_HIP_ERR_ARG; }
   if (ctx->ma_n > 0 && ctx->ma_cols < 0) { ctx->err = "ma_profile: col_off[0] of the tallied records is not 0"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->ma_prof_done = false;
+  ctx->ma_out.prof_done = false;
   const int64_t n = ctx->ma_n, T = ctx->ma_cols;
   const int32_t L = ctx->ma_L;
-  if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, ctx->d_prof_use, n + 1) || dev_ensure(ctx, ctx->d_prof_bins, MA_PROF_BINS))
-    return MIA_HIP_ERR_NOMEM;
+  MaSelection sel;
+  if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, ctx->d_prof_bins, MA_PROF_BINS)) return MIA_HIP_ERR_NOMEM;
+  if (const int rc = ma_selection(ctx, nullptr, use, &sel)) return rc;
   HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
-  if (use && n > 0) HIPCHK(hipMemcpyAsync(ctx->d_prof_use, use, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_prof_bins, 0, (size_t)MA_PROF_BINS * 8, ctx->stream));
   if (n > 0) {                                              // (records that all lack columns: one workgroup that finds no chunk)
-    MaProfView v{n, T, L, ctx->d_ma_start, ctx->d_ma_rev, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_smp, ctx->d_prof_ref, use ? (const uint8_t*)ctx->d_prof_use : nullptr};
+    MaProfView v{ma_records(ctx), T, ctx->d_prof_ref, sel.use};
     // persistent grid: the workgroups that are resident at once, or one per chunk when there are fewer chunks
     int64_t grid = (int64_t)ctx->cus * MAP_WGS_PER_CU;
     if (grid > ma_prof_chunks(T)) grid = ma_prof_chunks(T);
@@ -381,18 +384,17 @@ extern "C" int mia_hip_ma_profile(mia_hip_ctx* ctx, const char* ref_seq, const u
   }
   HIPCHK(hipMemcpyAsync(ctx->ma_prof_bins, ctx->d_prof_bins, (size_t)MA_PROF_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  int64_t events = 0, used = 0;
+  int64_t events = 0;
   for (int b = 0; b < MA_PROF_BINS; b++) events += ctx->ma_prof_bins[b];
-  for (int64_t r = 0; r < n; r++) used += !use || use[r] ? 1 : 0;
-  ctx->ma_prof_done = true;
-  if (n_used) *n_used = used;
+  ctx->ma_out.prof_done = true;
+  if (n_used) *n_used = sel.used;
   if (n_events) *n_events = events;
   return MIA_HIP_OK;
 }
 
 extern "C" int mia_hip_get_ma_profile(mia_hip_ctx* ctx, int64_t* count, int64_t* del, int64_t* bad_code, int64_t* beyond) {
   if (!ctx) return MIA_HIP_ERR_ARG;
-  if (!ctx->ma_resident || !ctx->ma_prof_done) { ctx->err = "ma_profile first"; return MIA_HIP_ERR_STATE; }
+  if (!ctx->ma_resident || !ctx->ma_out.prof_done) { ctx->err = "ma_profile first"; return MIA_HIP_ERR_STATE; }
   if (count) memcpy(count, ctx->ma_prof_bins, sizeof(int64_t) * MA_PROF_COUNTS);
   if (del) memcpy(del, ctx->ma_prof_bins + MA_PROF_DEL, sizeof(int64_t) * MA_PROF_DEPTHS);
   if (bad_code) *bad_code = ctx->ma_prof_bins[MA_PROF_BAD];
@@ -408,19 +410,16 @@ extern "C" int mia_hip_ma_ends(mia_hip_ctx* ctx, const char* ref_seq, const uint
   if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_ends"; return MIA_HIP_ERR_STATE; }
   if (!ref_seq) { ctx->err = "ma_ends: no reference sequence"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->ma_ends_done = false;
+  ctx->ma_out.ends_done = false;
   const int64_t n = ctx->ma_n;
   const int32_t L = ctx->ma_L;
-  if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, ctx->d_prof_use, n + 1) || dev_ensure(ctx, ctx->d_ends_seg, n + 1) ||
-      dev_ensure(ctx, ctx->d_ends_bins, MA_ENDS_BINS))
-    return MIA_HIP_ERR_NOMEM;
+  MaSelection sel;
+  if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, ctx->d_ends_bins, MA_ENDS_BINS)) return MIA_HIP_ERR_NOMEM;
+  if (const int rc = ma_selection(ctx, segment, use, &sel)) return rc;
   HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
-  if (segment && n > 0) HIPCHK(hipMemcpyAsync(ctx->d_ends_seg, segment, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  if (use && n > 0) HIPCHK(hipMemcpyAsync(ctx->d_prof_use, use, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_ends_bins, 0, (size_t)MA_ENDS_BINS * 8, ctx->stream));
   if (n > 0) {
-    MaEndsView v{n, L, ctx->d_ma_start, ctx->d_ma_rev, ctx->d_ma_coff, ctx->d_ma_seq, ctx->d_ma_rec_ins, ctx->d_ma_ins_list, ctx->d_ma_ipos, ctx->d_ma_ioff,
-                 ctx->d_ma_ib, ctx->d_prof_ref, segment ? (const uint8_t*)ctx->d_ends_seg : nullptr, use ? (const uint8_t*)ctx->d_prof_use : nullptr};
+    MaEndsView v{ma_records(ctx), ctx->d_prof_ref, sel.segment, sel.use};
     // persistent grid: the workgroups that are resident at once, or one per 256 records when there are fewer
     int64_t grid = (int64_t)ctx->cus * MAE_WGS_PER_CU;
     if (grid > ma_ends_chunks(n)) grid = ma_ends_chunks(n);
@@ -430,12 +429,11 @@ extern "C" int mia_hip_ma_ends(mia_hip_ctx* ctx, const char* ref_seq, const uint
   }
   HIPCHK(hipMemcpyAsync(ctx->ma_ends_bins, ctx->d_ends_bins, (size_t)MA_ENDS_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  int64_t used = 0, ends[2] = {0, 0};
-  for (int64_t r = 0; r < n; r++) used += !use || use[r] ? 1 : 0;
+  int64_t ends[2] = {0, 0};
   for (int end = 0; end < 2; end++)                          // every end adds one event to each of its 20 positions: count position 0
     for (int c = 0; c < MA_ENDS_CLASSES; c++) ends[end] += ctx->ma_ends_bins[ma_ends_ctx_bin(end, 0, c)];
-  ctx->ma_ends_done = true;
-  if (n_used) *n_used = used;
+  ctx->ma_out.ends_done = true;
+  if (n_used) *n_used = sel.used;
   if (n_ends5) *n_ends5 = ends[0];
   if (n_ends3) *n_ends3 = ends[1];
   return MIA_HIP_OK;
@@ -443,7 +441,7 @@ extern "C" int mia_hip_ma_ends(mia_hip_ctx* ctx, const char* ref_seq, const uint
 
 extern "C" int mia_hip_get_ma_ends(mia_hip_ctx* ctx, int64_t* ctx_count, int64_t* len_count, int64_t* halves) {
   if (!ctx) return MIA_HIP_ERR_ARG;
-  if (!ctx->ma_resident || !ctx->ma_ends_done) { ctx->err = "ma_ends first"; return MIA_HIP_ERR_STATE; }
+  if (!ctx->ma_resident || !ctx->ma_out.ends_done) { ctx->err = "ma_ends first"; return MIA_HIP_ERR_STATE; }
   if (ctx_count) memcpy(ctx_count, ctx->ma_ends_bins, sizeof(int64_t) * MA_ENDS_CTX);
   if (len_count) memcpy(len_count, ctx->ma_ends_bins + MA_ENDS_LEN, sizeof(int64_t) * 2 * MA_ENDS_LENS);
   if (halves) *halves = ctx->ma_ends_bins[MA_ENDS_HALVES];
@@ -457,21 +455,18 @@ extern "C" int mia_hip_ma_cols(mia_hip_ctx* ctx, const uint8_t* segment, const u
   if (!ctx) return MIA_HIP_ERR_ARG;
   if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_cols"; return MIA_HIP_ERR_STATE; }
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->ma_cols_done = false;
+  ctx->ma_out.cols_done = false;
   const int64_t n = ctx->ma_n, words = (int64_t)MA_COLS_WORDS * ctx->ma_L;
   const int32_t L = ctx->ma_L;
   unsigned long long out[2] = {0, 0};
   ctx->ma_cols_tab.assign((size_t)words, 0);
+  MaSelection sel;
+  if (const int rc = ma_selection(ctx, segment, use, &sel)) return rc;
   if (n > 0) {                                               // without records there is no launch and the table is zero
-    if (dev_ensure(ctx, ctx->d_prof_use, n + 1) || dev_ensure(ctx, ctx->d_ends_seg, n + 1) || dev_ensure(ctx, ctx->d_cols_tab, words) ||
-        dev_ensure(ctx, ctx->d_cols_out, 2))
-      return MIA_HIP_ERR_NOMEM;
-    if (segment) HIPCHK(hipMemcpyAsync(ctx->d_ends_seg, segment, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    if (use) HIPCHK(hipMemcpyAsync(ctx->d_prof_use, use, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if (dev_ensure(ctx, ctx->d_cols_tab, words) || dev_ensure(ctx, ctx->d_cols_out, 2)) return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipMemsetAsync(ctx->d_cols_tab, 0, (size_t)words * 4, ctx->stream));
     HIPCHK(hipMemsetAsync(ctx->d_cols_out, 0, sizeof out, ctx->stream));
-    MaColsView v{n, L, ctx->d_ma_start, ctx->d_ma_rev, ctx->d_ma_coff, ctx->d_ma_seq, segment ? (const uint8_t*)ctx->d_ends_seg : nullptr,
-                 use ? (const uint8_t*)ctx->d_prof_use : nullptr};
+    MaColsView v{ma_records(ctx), sel.segment, sel.use};
     // persistent grid over (tile, slice) jobs: the workgroups that are resident at once, or one per job when there are fewer
     const int64_t wgs = (int64_t)ctx->cus * MAC_WGS_PER_CU, slices = ma_cols_slices(n, L, wgs), per_slice = (n + slices - 1) / slices;
     const int64_t jobs = ma_cols_tiles(L) * slices, grid = jobs < wgs ? jobs : wgs;
@@ -483,11 +478,10 @@ extern "C" int mia_hip_ma_cols(mia_hip_ctx* ctx, const uint8_t* segment, const u
     HIPCHK(hipMemcpyAsync(out, ctx->d_cols_out, sizeof out, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
-  int64_t used = 0, events = (int64_t)out[0];
-  for (int64_t r = 0; r < n; r++) used += !use || use[r] ? 1 : 0;
+  int64_t events = (int64_t)out[0];
   for (int64_t i = 0; i < (int64_t)MA_COLS_STARTS * L; i++) events += ctx->ma_cols_tab[(size_t)i];       // words 0 .. 11 of every column
-  ctx->ma_cols_done = true;
-  if (n_used) *n_used = used;
+  ctx->ma_out.cols_done = true;
+  if (n_used) *n_used = sel.used;
   if (n_events) *n_events = events;
   if (beyond) *beyond = (int64_t)out[0];
   if (ends_outside) *ends_outside = (int64_t)out[1];
@@ -496,7 +490,7 @@ extern "C" int mia_hip_ma_cols(mia_hip_ctx* ctx, const uint8_t* segment, const u
 
 extern "C" int mia_hip_get_ma_cols(mia_hip_ctx* ctx, int32_t* cols) {
   if (!ctx) return MIA_HIP_ERR_ARG;
-  if (!ctx->ma_resident || !ctx->ma_cols_done) { ctx->err = "ma_cols first"; return MIA_HIP_ERR_STATE; }
+  if (!ctx->ma_resident || !ctx->ma_out.cols_done) { ctx->err = "ma_cols first"; return MIA_HIP_ERR_STATE; }
   if (cols) memcpy(cols, ctx->ma_cols_tab.data(), ctx->ma_cols_tab.size() * sizeof(int32_t));
   return MIA_HIP_OK;
 }

@@ -3,8 +3,8 @@
 //   k_ma_ace_gaps     G[p] = gaps[0] + .. + gaps[p-1] in 64 bits for p = 0 .. L + 1 (gaps[L] = 0), one workgroup: sum_of_gaps for
 //                     every column at once
 //   k_ma_ace_layout   per record its AF position, the length of its padded read and the bytes of its text; the records'
-//                     offsets in the text buffer are an ordered scan of those bytes (the workgroups' sums by look-back, as
-//                     k_ma_region_select does: the order of the records is the order of the output, no atomic append)
+//                     offsets in the text buffer are an ordered scan of those bytes (the workgroups' sums by the scan of
+//                     ma_scan_dev.h: the order of the records is the order of the output)
 //   k_ma_ace_render   one wavefront per record, lanes over the bytes of its text (newlines included): every lane finds the
 //                     column of its characters by bisection over G inside the record's span; whole 32-bit words are stored
 //                     where the address allows
@@ -40,15 +40,14 @@ __global__ __launch_bounds__(MAA_SCAN_THREADS) void k_ma_ace_gaps(const int32_t*
   for (int64_t p = p0; p < p1; p++) { G[p] = at; at += gaps[p]; }
 }
 
-// The control words are those of k_ma_region_select (MAR_TICKET, MAR_ROWS = bytes of the whole text here, MAR_STATE ..), and so
-// is the scheme: workgroups take their place by ticket, so a workgroup only ever waits for workgroups that already run.
-// Workgroup t lays out records t * MAR_PER_WG .., MAR_ITEMS consecutive records per thread.
+// Workgroups take their place by ticket (ma_scan_dev.h; ctl[MAR_ROWS] = bytes of the whole text).  Workgroup t lays out records
+// t * MAR_PER_WG .., MAR_ITEMS consecutive records per thread.
 __global__ __launch_bounds__(MAR_THREADS) void k_ma_ace_layout(MaAceView v, int32_t n_wgs, unsigned long long* ctl, int64_t* af_pos,
                                                                 int64_t* padded_len, int64_t* body_off) {
   __shared__ unsigned long long s_first;
   __shared__ long long s_part[MAR_THREADS];
   const int tid = threadIdx.x;
-  if (tid == 0) s_first = atomicAdd(&ctl[MAR_TICKET], 1ull);
+  if (tid == 0) s_first = ma_scan_ticket(ctl);
   __syncthreads();
   const int64_t t = (int64_t)s_first;
   if (t >= n_wgs) return;
@@ -68,21 +67,10 @@ __global__ __launch_bounds__(MAR_THREADS) void k_ma_ace_layout(MaAceView v, int3
   s_part[tid] = sum;
   __syncthreads();
   if (tid == 0) {
-    unsigned long long own = 0, before = 0;
+    unsigned long long own = 0;
     for (int i = 0; i < MAR_THREADS; i++) { const long long x = s_part[i]; s_part[i] = (long long)own; own += (unsigned long long)x; }
-    unsigned long long* state = ctl + MAR_STATE;
-    if (t > 0) {
-      __hip_atomic_store(&state[t], MAR_OWN | own, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int64_t j = t - 1;;) {              // (workgroup 0 publishes MAR_UPTO and nothing else: j never passes it)
-        const unsigned long long x = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((x & ~MAR_VALUE) == 0) { __builtin_amdgcn_s_sleep(1); continue; }
-        before += x & MAR_VALUE;
-        if ((x & ~MAR_VALUE) == MAR_UPTO) break;
-        j--;
-      }
-    }
-    __hip_atomic_store(&state[t], MAR_UPTO | (before + own), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == n_wgs - 1) { ctl[MAR_ROWS] = before + own; body_off[v.n] = (int64_t)(before + own); }
+    const unsigned long long before = ma_scan_before(ctl, t, n_wgs, own);
+    if (t == n_wgs - 1) body_off[v.n] = (int64_t)(before + own);
     s_first = before;
   }
   __syncthreads();

@@ -1,7 +1,7 @@
 // mia_ma_region_kernels.h -- ma's region view (-f 6 / -f 61; print_region, reference src/map_align.c:543-759) over the
 // records mia_hip_ma_tally left on the device.  Two launches:
-//   k_ma_region_select   the records that overlap the region, in record order (ordered compaction: a scan of the
-//                        workgroups' counts by look-back, no atomic append), and beside them the region's column map
+//   k_ma_region_select   the records that overlap the region, in record order (ordered compaction: the scan of the
+//                        workgroups' counts of ma_scan_dev.h), and beside them the region's column map
 //   k_ma_region_render   one wavefront per selected record, lanes over the region's columns; bytes gathered and stored,
 //                        nothing else
 // What a record's row holds is ma_region_body.h, shared with the host.
@@ -11,16 +11,13 @@
 
 #include "mia_layout.h"
 #include "ma_region_body.h"
+#include "ma_scan_dev.h"
 
 namespace mia {
 
 constexpr int MAR_THREADS = 256, MAR_ITEMS = 4, MAR_PER_WG = MAR_THREADS * MAR_ITEMS;
-// the select launch's words (64 bits each): arrival tickets, number of rows, width of a row, then one state per workgroup
-constexpr int MAR_TICKET = 0, MAR_ROWS = 1, MAR_WIDTH = 2, MAR_STATE = 4;
-// state of workgroup t: its own count (MAR_OWN) or the count of workgroups 0 .. t (MAR_UPTO) in the low 62 bits
-constexpr unsigned long long MAR_OWN = 1ull << 62, MAR_UPTO = 2ull << 62, MAR_VALUE = (1ull << 62) - 1;
 
-// Workgroups take their place by ticket, so a workgroup only ever waits for workgroups that already run.  Tickets
+// Workgroups take their place by ticket (ma_scan_dev.h; ctl[MAR_ROWS] = number of rows, ctl[MAR_WIDTH] = width of a row).  Tickets
 // 0 .. n_wgs - 1 select MAR_PER_WG records each; ticket n_wgs writes the column map.
 __global__ __launch_bounds__(MAR_THREADS) void k_ma_region_select(MaRegionView v, int32_t n_wgs, unsigned long long* ctl, int64_t* colmap,
                                                                    int64_t* rows) {
@@ -28,7 +25,7 @@ __global__ __launch_bounds__(MAR_THREADS) void k_ma_region_select(MaRegionView v
   __shared__ long long s_part[MAR_THREADS];
   __shared__ int s_cnt[MAR_ITEMS * (MAR_THREADS / 64)];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_first = atomicAdd(&ctl[MAR_TICKET], 1ull);
+  if (tid == 0) s_first = ma_scan_ticket(ctl);
   __syncthreads();
   const int64_t t = (int64_t)s_first;
   if (t >= n_wgs) {
@@ -63,22 +60,9 @@ __global__ __launch_bounds__(MAR_THREADS) void k_ma_region_select(MaRegionView v
   }
   __syncthreads();
   if (tid == 0) {
-    unsigned long long own = 0, before = 0;
+    unsigned long long own = 0;
     for (int i = 0; i < MAR_ITEMS * (MAR_THREADS / 64); i++) own += (unsigned long long)s_cnt[i];
-    unsigned long long* state = ctl + MAR_STATE;
-    if (t > 0) {
-      __hip_atomic_store(&state[t], MAR_OWN | own, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int64_t j = t - 1;;) {              // (workgroup 0 publishes MAR_UPTO and nothing else: j never passes it)
-        const unsigned long long x = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((x & ~MAR_VALUE) == 0) { __builtin_amdgcn_s_sleep(1); continue; }
-        before += x & MAR_VALUE;
-        if ((x & ~MAR_VALUE) == MAR_UPTO) break;
-        j--;
-      }
-    }
-    __hip_atomic_store(&state[t], MAR_UPTO | (before + own), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == n_wgs - 1) ctl[MAR_ROWS] = before + own;
-    s_first = before;
+    s_first = ma_scan_before(ctl, t, n_wgs, own);
   }
   __syncthreads();
   const int64_t base = (int64_t)s_first;

@@ -2,8 +2,8 @@
 // Two launches:
 //   k_ma_sam_layout   per record the index of its inserts (ma_sam_index, one thread per record), then one wavefront per record
 //                     over its walk: the bytes of its CIGAR, the length of its SEQ, its NM.  The records' offsets in the text
-//                     buffer are an ordered scan of their bodies' bytes (the workgroups' sums by look-back over the control words
-//                     of k_ma_region_select and k_ma_ace_layout: the order of the records is the order of the output, no atomic append)
+//                     buffer are an ordered scan of their bodies' bytes (the workgroups' sums by the scan of ma_scan_dev.h: the
+//                     order of the records is the order of the output)
 //   k_ma_sam_render   one wavefront per record over the same walk, writing: every run of ops is written by the lane on which the
 //                     next run begins (the last one by lane 0), every SEQ character by the lane that holds it
 // Both walk a record in stretches of 64 positions (ma_sam_wave): the lanes' ops become ballots, a run begins where a lane's op
@@ -14,8 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mia_ma_region_kernels.h"
 #include "ma_sam_body.h"
+#include "ma_scan_dev.h"
 #include "wave_dev.h"
 
 namespace mia {
@@ -70,15 +70,14 @@ __device__ __forceinline__ void ma_sam_wave(const MaSamView& v, int64_t r, int64
   *nm = n_nm;
 }
 
-// Workgroups take their place by ticket (ctl[MAR_TICKET]), so a workgroup only ever waits for workgroups that already run;
-// ctl[MAR_ROWS] = bytes of the whole text, ctl[MAR_STATE + t] = the state of workgroup t.  Workgroup t lays out records
+// Workgroups take their place by ticket (ma_scan_dev.h; ctl[MAR_ROWS] = bytes of the whole text).  Workgroup t lays out records
 // t * MAS_PER_WG .., wavefront w of it records w, w + MAS_WAVES, ..  cigar_bytes[r] = 0 marks a record without SEQ ("*", "*").
 __global__ __launch_bounds__(MAS_THREADS) void k_ma_sam_layout(MaSamView v, int32_t n_wgs, unsigned long long* ctl, int32_t* nm, int64_t* cigar_bytes,
                                                                 int64_t* body_off) {
   __shared__ unsigned long long s_first;
   __shared__ long long s_walk[MAS_PER_WG], s_bytes[MAS_PER_WG];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) s_first = atomicAdd(&ctl[MAR_TICKET], 1ull);
+  if (tid == 0) s_first = ma_scan_ticket(ctl);
   __syncthreads();
   const int64_t t = (int64_t)s_first;
   if (t >= n_wgs) return;
@@ -100,21 +99,10 @@ __global__ __launch_bounds__(MAS_THREADS) void k_ma_sam_layout(MaSamView v, int3
   }
   __syncthreads();
   if (tid == 0) {
-    unsigned long long own = 0, before = 0;
+    unsigned long long own = 0;
     for (int i = 0; i < MAS_PER_WG; i++) { const long long x = s_bytes[i]; s_bytes[i] = (long long)own; own += (unsigned long long)x; }
-    unsigned long long* state = ctl + MAR_STATE;
-    if (t > 0) {
-      __hip_atomic_store(&state[t], MAR_OWN | own, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int64_t j = t - 1;;) {              // (workgroup 0 publishes MAR_UPTO and nothing else: j never passes it)
-        const unsigned long long x = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((x & ~MAR_VALUE) == 0) { __builtin_amdgcn_s_sleep(1); continue; }
-        before += x & MAR_VALUE;
-        if ((x & ~MAR_VALUE) == MAR_UPTO) break;
-        j--;
-      }
-    }
-    __hip_atomic_store(&state[t], MAR_UPTO | (before + own), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t == n_wgs - 1) { ctl[MAR_ROWS] = before + own; body_off[v.n] = (int64_t)(before + own); }
+    const unsigned long long before = ma_scan_before(ctl, t, n_wgs, own);
+    if (t == n_wgs - 1) body_off[v.n] = (int64_t)(before + own);
     s_first = before;
   }
   __syncthreads();

@@ -30,14 +30,8 @@ int main(int argc, char** argv) {
   std::vector<int64_t> G((size_t)m.L + 2, 0);
   for (int p = 0; p < m.L; p++) G[(size_t)p + 1] = G[(size_t)p] + m.gaps[(size_t)p];
   G[(size_t)m.L + 1] = G[(size_t)m.L];
-  std::vector<int32_t> rec_ins((size_t)n + 1, 0), ins_list((size_t)n_ins);
-  for (int64_t e = 0; e < n_ins; e++) rec_ins[(size_t)m.ins_record[(size_t)e] + 1]++;
-  for (int64_t r = 0; r < n; r++) rec_ins[(size_t)r + 1] += rec_ins[(size_t)r];
-  {
-    std::vector<int32_t> cursor(rec_ins.begin(), rec_ins.end() - 1);
-    for (int64_t e = 0; e < n_ins; e++) ins_list[(size_t)cursor[(size_t)m.ins_record[(size_t)e]]++] = (int32_t)e;
-    for (int64_t r = 0; r < n; r++) mia::ma_ace_order_inserts(ins_list.data() + rec_ins[(size_t)r], rec_ins[(size_t)r + 1] - rec_ins[(size_t)r], m.ins_pos.data());
-  }
+  std::vector<int32_t> rec_ins, ins_list;
+  mia::ma_list_pairs(n, n_ins, m.ins_record.data(), m.ins_pos.data(), &rec_ins, &ins_list);
   const mia::MaAceView v{n, m.start.data(), m.col_off.data(), m.seq.data(), rec_ins.data(), ins_list.data(), m.ins_pos.data(), m.ins_off.data(),
                          m.ins_bases.data(), G.data()};
   std::vector<int64_t> off((size_t)n + 1, 0);

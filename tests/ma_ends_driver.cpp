@@ -15,7 +15,6 @@
 #include <string>
 #include <vector>
 
-#include "../mapping-iterative-assembler_amd/csrc/ma_ace_body.h"
 #include "../mapping-iterative-assembler_amd/csrc/ma_ends_body.h"
 #include "../mapping-iterative-assembler_amd/host/maln_text.h"
 
@@ -42,14 +41,8 @@ int counts(const char* fn, bool use_dropped, bool back) {
   maln_text::read_maln_file(fn, &m);
   const int64_t n = (int64_t)m.start.size(), T = m.col_off[(size_t)n], n_ins = (int64_t)m.ins_record.size();
   // the pairs by record, as mia_hip_ma_tally lists them
-  std::vector<int32_t> rec_ins((size_t)n + 1, 0), ins_list((size_t)n_ins);
-  for (int64_t e = 0; e < n_ins; e++) rec_ins[(size_t)m.ins_record[(size_t)e] + 1]++;
-  for (int64_t r = 0; r < n; r++) rec_ins[(size_t)r + 1] += rec_ins[(size_t)r];
-  {
-    std::vector<int32_t> cursor(rec_ins.begin(), rec_ins.end() - 1);
-    for (int64_t e = 0; e < n_ins; e++) ins_list[(size_t)cursor[(size_t)m.ins_record[(size_t)e]]++] = (int32_t)e;
-    for (int64_t r = 0; r < n; r++) ma_ace_order_inserts(ins_list.data() + rec_ins[(size_t)r], rec_ins[(size_t)r + 1] - rec_ins[(size_t)r], m.ins_pos.data());
-  }
+  std::vector<int32_t> rec_ins, ins_list;
+  ma_list_pairs(n, n_ins, m.ins_record.data(), m.ins_pos.data(), &rec_ins, &ins_list);
   Aligned seq(padded(T)), ref((size_t)m.L), ib(padded((int64_t)m.ins_bases.size()));
   if ((T && !seq.p) || !ref.p || (!m.ins_bases.empty() && !ib.p)) { fprintf(stderr, "no memory\n"); return 2; }
   if (T) { memset(seq.p, '-', padded(T)); memcpy(seq.p, m.seq.data(), (size_t)T); }      // ('-' behind the end: counted there, it would show)

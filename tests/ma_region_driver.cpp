@@ -18,10 +18,9 @@ int main(int argc, char** argv) {
   if (argc > 2) maln_text::parse_region(argv[2], &reg_start, &reg_end);
   maln_text::clamp_region(reg_start, reg_end, m.L, &first, &last);
   const int64_t n = (int64_t)m.start.size();
-  // the pairs by record (what mia_hip_ma_tally builds for the device): they are in record order already
-  std::vector<int32_t> rec_ins((size_t)n + 1, 0), ins_list(m.ins_record.size());
-  for (size_t e = 0; e < m.ins_record.size(); e++) { rec_ins[(size_t)m.ins_record[e] + 1]++; ins_list[e] = (int32_t)e; }
-  for (int64_t r = 0; r < n; r++) rec_ins[(size_t)r + 1] += rec_ins[(size_t)r];
+  // the pairs by record, as mia_hip_ma_tally lists them for the device
+  std::vector<int32_t> rec_ins, ins_list;
+  mia::ma_list_pairs(n, (int64_t)m.ins_record.size(), m.ins_record.data(), m.ins_pos.data(), &rec_ins, &ins_list);
   std::vector<int64_t> colmap(1, 0);
   for (int p = first; p <= last; p++) colmap.push_back(colmap.back() + mia::ma_region_gap(m.gaps[(size_t)p]) + 1);
   mia::MaRegionView v{n, m.start.data(), m.col_off.data(), m.seq.data(), rec_ins.data(), ins_list.data(), m.ins_pos.data(), m.ins_off.data(),

@@ -10,7 +10,6 @@
 #include <string>
 #include <vector>
 
-#include "../mapping-iterative-assembler_amd/csrc/ma_ace_body.h"
 #include "../mapping-iterative-assembler_amd/csrc/ma_sam_body.h"
 #include "../mapping-iterative-assembler_amd/host/maln_text.h"
 
@@ -86,14 +85,8 @@ int main(int argc, char** argv) {
   maln_text::read_maln_file(argv[1], &m);
   if (!ma_sam_gaps_ok(m.gaps.data(), m.L)) { fprintf(stderr, "no SAM export\n"); return 1; }
   const int64_t n = (int64_t)m.start.size(), n_ins = (int64_t)m.ins_record.size();
-  std::vector<int32_t> rec_ins((size_t)n + 1, 0), ins_list((size_t)n_ins);
-  for (int64_t e = 0; e < n_ins; e++) rec_ins[(size_t)m.ins_record[(size_t)e] + 1]++;
-  for (int64_t r = 0; r < n; r++) rec_ins[(size_t)r + 1] += rec_ins[(size_t)r];
-  {
-    std::vector<int32_t> cursor(rec_ins.begin(), rec_ins.end() - 1);
-    for (int64_t e = 0; e < n_ins; e++) ins_list[(size_t)cursor[(size_t)m.ins_record[(size_t)e]]++] = (int32_t)e;
-    for (int64_t r = 0; r < n; r++) ma_ace_order_inserts(ins_list.data() + rec_ins[(size_t)r], rec_ins[(size_t)r + 1] - rec_ins[(size_t)r], m.ins_pos.data());
-  }
+  std::vector<int32_t> rec_ins, ins_list;
+  ma_list_pairs(n, n_ins, m.ins_record.data(), m.ins_pos.data(), &rec_ins, &ins_list);
   std::vector<int64_t> cum((size_t)(n_ins + n + 1), -1);
   const MaSamView v{n, m.L, m.start.data(), m.col_off.data(), m.seq.data(), rec_ins.data(), ins_list.data(), m.ins_pos.data(), m.ins_off.data(),
                     m.ins_bases.data(), m.ref_seq.data(), cum.data()};

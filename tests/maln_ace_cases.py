@@ -13,6 +13,10 @@
                                     maln_synth sets GAPS[0] = 3, which has no ACE export
                         fix_c.1, fix_c.2, fix_lin.1 of tests/golden/maln
   REFUSED             gaps0: GAPS[0] > 0, for the refusal only
+  SCAN_EDGES / make_records   recs_1023, recs_1024, recs_1025, recs_2049: that many short records -- one record less than, exactly and one
+                      more than the 1 024 a workgroup of k_ma_region_select and k_ma_ace_layout takes, and two such workgroups and one
+                      record (128 workgroups of k_ma_sam_layout less one record, 128, 128 and one record, 256 and one record).  They
+                      are held to the restatements only: no run of the reference is recorded for them, so they are not in CASES
   RUNS                the recorded runs: arguments behind `-M <file>`; "OUT" stands for the path -m writes
 """
 import copy
@@ -26,6 +30,8 @@ SYNTH = ("edge255", "edge256", "edge257", "scan16_4095", "scan16_4096", "scan16_
 FIXTURES = ("fix_c.1", "fix_c.2", "fix_lin.1")
 CASES = ("shapes", "column300", "empty") + SYNTH + FIXTURES
 REFUSED = ("gaps0",)
+SCAN_EDGES = ("recs_1023", "recs_1024", "recs_1025", "recs_2049")
+RECS_L, RECS_HOT = 300, {60: 2, 150: 3, 240: 1}           # make_records: reference columns; the columns that have insert columns
 RUNS = {
     "f7c1": ["-f", "7", "-c", "1"],
     "f7c2": ["-f", "7", "-c", "2"],
@@ -115,6 +121,26 @@ def make_column300():
     return m
 
 
+def make_records(n):
+    """n records of 20 .. 40 columns on RECS_L reference columns, GAPS[0] = 0; every fifth has one INS_POS pair, behind its first
+    column and in front of one of the RECS_HOT columns, of 1 .. GAPS bases"""
+    rng = ms.Rng(7100 + n)
+    m = _blank("recs_%d" % n, RECS_L, rng, RECS_HOT)
+    hot = sorted(RECS_HOT)
+    length = rng.integers(20, 41, n)
+    start = rng.integers(0, RECS_L - 40, n)
+    pos = rng.integers(1, 20, n)
+    which = rng.integers(0, len(hot), n)
+    for i in range(n):
+        if i % 5 == 0:
+            h = hot[int(which[i])]
+            ins = [(int(pos[i]), _bases(rng, 1 + i // 5 % RECS_HOT[h]))]
+            _record(m, rng, "s%d" % i, h - int(pos[i]), int(length[i]), rc=i & 1, seg="afbn"[i % 4], ins=ins)
+        else:
+            _record(m, rng, "s%d" % i, int(start[i]), int(length[i]), rc=i & 1, seg="afbn"[i % 4])
+    return m
+
+
 def make_empty():
     return _blank("empty", 120, ms.Rng(7003), {60: 2})
 
@@ -138,6 +164,8 @@ def make_case(name):
         m = copy.deepcopy(ms.make_case(name))
         m.gaps[0] = 0
         return m
+    if name in SCAN_EDGES:
+        return make_records(int(name[5:]))
     return {"shapes": make_shapes, "column300": make_column300, "empty": make_empty, "gaps0": make_gaps0}[name]()
 
 

@@ -15,6 +15,7 @@ an ordered scan over workgroups of 8 records) can go wrong.  Rebuilt from fixed 
   sam_lower    sam_shapes with the reference in lower case (NM must not change)
   sam_257, sam_4097   257 and 4 097 short records: 32 and 512 full workgroups of the layout and one record more
   sam_empty    no records
+  SCAN_EDGES   sam_8, sam_9: one workgroup of the layout, and one record more
 """
 import copy
 
@@ -24,6 +25,7 @@ import maln_ace_cases as mc
 import maln_synth as ms
 
 CASES = ("sam_shapes", "sam_lower", "sam_257", "sam_4097", "sam_empty")
+SCAN_EDGES = ("sam_8", "sam_9")
 L_SHAPES = 1500
 
 

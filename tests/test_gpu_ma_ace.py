@@ -37,7 +37,7 @@ def recorded():
 
 @pytest.fixture(scope="module")
 def cases():
-    return {name: mc.make_case(name) for name in ("shapes", "column300", "empty", "scan16_4096", "fix_lin.1", "fix_c.1")}
+    return {name: mc.make_case(name) for name in ("shapes", "column300", "empty", "scan16_4096", "fix_lin.1", "fix_c.1") + mc.SCAN_EDGES}
 
 
 @pytest.fixture(scope="module")
@@ -129,7 +129,7 @@ def check_ace(hip, m, name):
     assert at == len(body), name
 
 
-@pytest.mark.parametrize("name", ["shapes", "fix_c.1", "empty"])
+@pytest.mark.parametrize("name", ["shapes", "fix_c.1", "empty"] + list(mc.SCAN_EDGES))
 def test_library_call_matches_the_restatement(cases, name):
     import mia_amd
     hip = mia_amd.MiaHip(0)

@@ -14,6 +14,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import maln_ace_cases as mc
+import maln_synth as ms
 from conftest import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
@@ -179,3 +181,32 @@ def test_region_of_a_million_records_matches_the_row_rule():
             exp = expected_row(d, want[i], first, last, colmap)
             assert np.array_equal(text[i], exp), (first, last, int(i), int(want[i]))
         del text
+
+
+# ---- the ordered selection at the edges of a workgroup's 1 024 records -------------------------------------------------------------
+EDGE_REGION = (80, 190)                    # about half of make_records' records reach into it, and the insert columns of column 150 lie in it
+
+
+@pytest.mark.parametrize("name", mc.SCAN_EDGES)
+def test_region_around_one_workgroup_of_records_matches_the_row_rule(name):
+    import mia_amd
+    m = mc.make_case(name)
+    d = ms.flatten(m)
+    n = len(m.rec)
+    d["length"] = np.diff(d["col_off"])
+    d["by_record"] = {}
+    for e, r in enumerate(d["ins_record"]):
+        d["by_record"].setdefault(int(r), []).append(e)
+    first, last = EDGE_REGION
+    want = expected_rows(d, first, last)
+    assert 0.35 * n <= len(want) <= 0.65 * n and want[-1] >= n - 8                      # the ranks of the compaction matter, up to the last records
+    ins_col = d["start"][d["ins_record"]].astype(np.int64) + d["ins_pos"]
+    assert len(np.intersect1d(want, d["ins_record"][(ins_col >= first) & (ins_col <= last)])) >= 20
+    colmap = np.concatenate(([0], np.cumsum(d["gaps"][first:last + 1].astype(np.int64) + 1)))
+    hip = mia_amd.MiaHip(0)
+    hip.set_pssm(m.fpsm, m.rpsm)
+    hip.ma_tally(*ms.ma_tally_args(d))
+    rows, text = hip.ma_region(first, last)
+    assert text.shape == (len(want), int(colmap[-1])) and np.array_equal(rows, want)
+    for i in range(len(want)):
+        assert np.array_equal(text[i], expected_row(d, want[i], first, last, colmap)), (name, i, int(want[i]))

@@ -115,7 +115,8 @@ def check_sam(hip, m, name, want=None):
     assert at == len(body), name
 
 
-@pytest.mark.parametrize("name", ["sam:sam_shapes", "sam:sam_lower", "sam:sam_257", "sam:sam_4097", "sam:sam_empty", "ace:shapes", "ace:fix_c.1", "synth:edge257"])
+@pytest.mark.parametrize("name", ["sam:sam_shapes", "sam:sam_lower", "sam:sam_257", "sam:sam_4097", "sam:sam_empty", "ace:shapes", "ace:fix_c.1", "synth:edge257"] +
+                         ["ace:" + n for n in mc.SCAN_EDGES] + ["sam:" + n for n in sc.SCAN_EDGES])
 def test_library_call_matches_the_restatement(name):
     import mia_amd
     hip = mia_amd.MiaHip(0)

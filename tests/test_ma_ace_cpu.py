@@ -33,7 +33,7 @@ def recorded():
 
 @pytest.fixture(scope="module")
 def cases():
-    return {name: mc.make_case(name) for name in mc.CASES}
+    return {name: mc.make_case(name) for name in mc.CASES + mc.SCAN_EDGES}
 
 
 def sanitizer_flags(tmp):
@@ -113,7 +113,7 @@ def test_restatement_reproduces_the_reference(recorded, cases, name):
     assert checked == 5
 
 
-@pytest.mark.parametrize("name", mc.CASES)
+@pytest.mark.parametrize("name", mc.CASES + mc.SCAN_EDGES)
 def test_host_build_of_the_kernels_code_agrees(driver, cases, name, tmp_path):
     m = cases[name]
     path = str(tmp_path / "in.maln")

@@ -20,6 +20,8 @@ FILES = tuple(sorted(f for f in os.listdir(MALN) if not f.endswith(".json")))
 # (a case of maln_ace_cases that is a committed file is taken as that file)
 NAMES = tuple("ace:" + n for n in mc.CASES if n not in mc.FIXTURES) + tuple("synth:" + n for n in ms.CASES) + tuple("sam:" + n for n in sc.CASES) + \
     tuple("file:" + f for f in FILES)
+# one workgroup's worth of records of each layout kernel, and the sizes beside it: held to the restatement like the rest
+NAMES += tuple("ace:" + n for n in mc.SCAN_EDGES) + tuple("sam:" + n for n in sc.SCAN_EDGES)
 _made = {}
 
 
