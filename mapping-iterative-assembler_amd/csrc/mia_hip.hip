@@ -10,17 +10,21 @@
 #include <algorithm>
 #include <cmath>
 #include <chrono>
+#include <optional>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/mia_hip.h"
 #include "dev_buf.h"
+#include "dev_pool.h"
 #include "mia_comm.h"
 #include "mia_consensus_kernels.h"
 #include "mia_kernels.h"
 #include "bandx_kernels.h"
 #include "align_route.h"
+#include "pass1_route.h"
 #include "mia_pass1_kernels.h"
 #include "mia_myers_kernels.h"
 #include "mia_trim_kernels.h"
@@ -68,13 +72,16 @@ static inline const char* alt_env(const char* name) { return getenv(name); }
 static inline const char* alt_env(const char*) { return nullptr; }
 #define ALT_KERNEL(k) ((const void*)nullptr)        // (the one-lane band kernels are not part of the release build's code object)
 #endif
+static inline std::optional<int> alt_int(const char* name) {
+  const char* v = alt_env(name);
+  return v ? std::optional<int>(atoi(v)) : std::nullopt;
+}
 
 struct mia_hip_ctx {
   int device = 0;
   int cus = 1;
   std::string err;
-  struct PoolBlock { DevBuf<unsigned char> buf; bool lent; };
-  std::vector<PoolBlock> pool;             // device temporaries of the one-off calls (pool_alloc)
+  DevPool pool;                            // device temporaries of the one-off calls (dev_pool.h; pool_take)
   // pinned staging: small copies to and from pageable memory wait for the stream, pinned ones do not
   unsigned char* h_pin = nullptr; static constexpr size_t PIN_BYTES = 1 << 20, PIN_MISC = 64 << 10;
   DevBuf<int32_t> d_ctrl;                  // the control block (CTRL_*)
@@ -296,8 +303,9 @@ struct mia_hip_ctx {
 
 // The alternative routes and diagnostics of libmia_hip_alt.so (alt_env reads nothing in the release build), one line each.  What the
 // alignment's switches do to the route is decided in ONE place, align_route.h (align_route); these lines only set the fields.  The rest
-// are read where they apply: MIA_HIP_ITER_DEBUG and MIA_HIP_EV_PAD (mia_hip_iterate), MIA_HIP_P1_TIMING / _CPL / _PLAIN
-// (mia_hip_pass1), MIA_HIP_PEAK_DEBUG (mia_hip_peak).
+// are read where they apply: MIA_HIP_ITER_DEBUG and MIA_HIP_EV_PAD (mia_hip_iterate), MIA_HIP_P1_TIMING (mia_hip_pass1),
+// MIA_HIP_PEAK_DEBUG (mia_hip_peak).  MIA_HIP_P1_CPL and MIA_HIP_P1_PLAIN are parsed in one spot, with every call (pass1_route_input),
+// and handed to pass1_route.h, which decides what they do.
 static void read_alt_switches(mia_hip_ctx* ctx) {
   auto on = [](const char* name) { const char* v = alt_env(name); return v && atoi(v) != 0; };
   // alignment: which kernels take the reads
@@ -361,44 +369,9 @@ static int dev_ensure(mia_hip_ctx* ctx, DevBuf<T>& b, int64_t need, int64_t allo
 template <class T>
 static int dev_ensure(mia_hip_ctx* ctx, DevBuf<T>& b, int64_t need) { return dev_nomem(ctx, b.ensure(need, need)); }
 
-// Temporaries of the one-off calls (pass 1, adapter trimming) come from blocks the context keeps: hipMalloc/hipFree of
-// twenty-odd buffers per call cost more than the kernels between them.  A block is lent for the length of a scope.
+// A temporary of a one-off call (pass 1, Myers): a block of the context's pool, lent until the lease goes out of scope (dev_pool.h)
 template <class T>
-static int pool_alloc(mia_hip_ctx* ctx, T** p, size_t n) {
-  const int64_t bytes = (int64_t)((n ? n : 1) * sizeof(T));
-  int best = -1;
-  for (size_t k = 0; k < ctx->pool.size(); k++) {
-    auto& b = ctx->pool[k];
-    if (!b.lent && b.buf.cap >= bytes && (best < 0 || b.buf.cap < ctx->pool[best].buf.cap)) best = (int)k;
-  }
-  if (best < 0) {
-    // grow the largest idle block rather than keep one that nothing fits any more
-    int idle = -1;
-    for (size_t k = 0; k < ctx->pool.size(); k++)
-      if (!ctx->pool[k].lent && (idle < 0 || ctx->pool[k].buf.cap > ctx->pool[idle].buf.cap)) idle = (int)k;
-    if (idle >= 0) ctx->pool.erase(ctx->pool.begin() + idle);
-    DevBuf<unsigned char> q;
-    if (dev_alloc(ctx, q, bytes)) { *p = nullptr; return MIA_HIP_ERR_NOMEM; }
-    ctx->pool.push_back({std::move(q), false});
-    best = (int)ctx->pool.size() - 1;
-  }
-  ctx->pool[best].lent = true;
-  *p = (T*)ctx->pool[best].buf.p;
-  return MIA_HIP_OK;
-}
-struct PoolScope {
-  mia_hip_ctx* c;
-  std::vector<void**> w;
-  explicit PoolScope(mia_hip_ctx* ctx) : c(ctx) {}
-  void watch(void** pp) { w.push_back(pp); }
-  ~PoolScope() {
-    for (void** pp : w) {
-      if (!*pp) continue;
-      for (auto& b : c->pool) if (b.buf.p == *pp) b.lent = false;
-      *pp = nullptr;
-    }
-  }
-};
+static int pool_take(mia_hip_ctx* ctx, PoolLease<T>& lease, size_t n) { return dev_nomem(ctx, lease.take(ctx->pool, n)); }
 
 extern "C" const char* mia_hip_last_error(const mia_hip_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
@@ -594,45 +567,45 @@ extern "C" int mia_hip_upload_reads(mia_hip_ctx* ctx, int64_t n, const char* bas
   ctx->h_len.assign(len.begin(), len.end());
   for (int64_t i = 0; i < n; i++) if ((int)len[(size_t)i] < ctx->min_len) ctx->min_len = len[(size_t)i];
   const int stride = (max_len + 3) & ~3;
-  int rcx = 0;
-  rcx |= dev_alloc(ctx, ctx->d_packed, packed.size());
-  rcx |= dev_alloc(ctx, ctx->d_roff, n);
-  rcx |= dev_alloc(ctx, ctx->d_len, n);
-  rcx |= dev_alloc(ctx, ctx->d_rc, n);
-  rcx |= dev_alloc(ctx, ctx->d_sk, n);
-  rcx |= dev_alloc(ctx, ctx->d_as, n);
-  rcx |= dev_alloc(ctx, ctx->d_ae, n);
-  rcx |= dev_alloc(ctx, ctx->d_score, n);
-  rcx |= dev_alloc(ctx, ctx->d_refstart, n);
-  rcx |= dev_alloc(ctx, ctx->d_abr, n);
-  rcx |= dev_alloc(ctx, ctx->d_status, n);
-  rcx |= dev_alloc(ctx, ctx->d_cols, n * stride);
-  rcx |= dev_alloc(ctx, ctx->d_bin_of, n);
-  rcx |= dev_alloc(ctx, ctx->d_umax, n);
+  int nomem = 0;
+  nomem |= dev_alloc(ctx, ctx->d_packed, packed.size());
+  nomem |= dev_alloc(ctx, ctx->d_roff, n);
+  nomem |= dev_alloc(ctx, ctx->d_len, n);
+  nomem |= dev_alloc(ctx, ctx->d_rc, n);
+  nomem |= dev_alloc(ctx, ctx->d_sk, n);
+  nomem |= dev_alloc(ctx, ctx->d_as, n);
+  nomem |= dev_alloc(ctx, ctx->d_ae, n);
+  nomem |= dev_alloc(ctx, ctx->d_score, n);
+  nomem |= dev_alloc(ctx, ctx->d_refstart, n);
+  nomem |= dev_alloc(ctx, ctx->d_abr, n);
+  nomem |= dev_alloc(ctx, ctx->d_status, n);
+  nomem |= dev_alloc(ctx, ctx->d_cols, n * stride);
+  nomem |= dev_alloc(ctx, ctx->d_bin_of, n);
+  nomem |= dev_alloc(ctx, ctx->d_umax, n);
   ctx->rplane_words = (max_len + 63) >> 6;
-  rcx |= dev_alloc(ctx, ctx->d_rplanes, n * 2 * ctx->rplane_words + 2);      // (+ 2: k_tally_binned asks for a second word of every plane)
-  rcx |= dev_alloc(ctx, ctx->d_list, n + 4 * N_BINS);   // quad bins are padded to multiples of four
-  rcx |= dev_alloc(ctx, ctx->d_wide_list, n);
-  rcx |= dev_alloc(ctx, ctx->d_retry_list, n);
-  rcx |= dev_alloc(ctx, ctx->d_slot, n);
-  rcx |= dev_alloc(ctx, ctx->d_partial, (size_t)(n / 256 + n / 4096 + 8));      // per 256 reads, and behind them per 4 096 (k_slot_count)
-  rcx |= dev_alloc(ctx, ctx->d_drop_f, n);
-  rcx |= dev_alloc(ctx, ctx->d_drop_b, n);
-  rcx |= dev_alloc(ctx, ctx->d_slot_dropped, 2 * n + 16);
+  nomem |= dev_alloc(ctx, ctx->d_rplanes, n * 2 * ctx->rplane_words + 2);      // (+ 2: k_tally_binned asks for a second word of every plane)
+  nomem |= dev_alloc(ctx, ctx->d_list, n + 4 * N_BINS);   // quad bins are padded to multiples of four
+  nomem |= dev_alloc(ctx, ctx->d_wide_list, n);
+  nomem |= dev_alloc(ctx, ctx->d_retry_list, n);
+  nomem |= dev_alloc(ctx, ctx->d_slot, n);
+  nomem |= dev_alloc(ctx, ctx->d_partial, (size_t)(n / 256 + n / 4096 + 8));      // per 256 reads, and behind them per 4 096 (k_slot_count)
+  nomem |= dev_alloc(ctx, ctx->d_drop_f, n);
+  nomem |= dev_alloc(ctx, ctx->d_drop_b, n);
+  nomem |= dev_alloc(ctx, ctx->d_slot_dropped, 2 * n + 16);
   ctx->n_slots = ctx->d_slot_dropped.cap;
-  rcx |= dev_alloc(ctx, ctx->d_back_slot, n) | dev_alloc(ctx, ctx->d_front_slot0, n);
-  rcx |= dev_alloc(ctx, ctx->d_ri_flen, n) | dev_alloc(ctx, ctx->d_ri_blen, n) | dev_alloc(ctx, ctx->d_ri_actf, n) |
+  nomem |= dev_alloc(ctx, ctx->d_back_slot, n) | dev_alloc(ctx, ctx->d_front_slot0, n);
+  nomem |= dev_alloc(ctx, ctx->d_ri_flen, n) | dev_alloc(ctx, ctx->d_ri_blen, n) | dev_alloc(ctx, ctx->d_ri_actf, n) |
          dev_alloc(ctx, ctx->d_ri_trec, n * 16);
   const int64_t slot_cap = 2 * n + 16;
-  rcx |= dev_alloc(ctx, ctx->d_si_reclen, slot_cap) | dev_alloc(ctx, ctx->d_si_recact, slot_cap) | dev_alloc(ctx, ctx->d_si_writer, slot_cap) |
+  nomem |= dev_alloc(ctx, ctx->d_si_reclen, slot_cap) | dev_alloc(ctx, ctx->d_si_recact, slot_cap) | dev_alloc(ctx, ctx->d_si_writer, slot_cap) |
          dev_alloc(ctx, ctx->d_si_mult, slot_cap);
   ctx->lk.cap = (int32_t)std::min<int64_t>(n + 16, (int64_t)1 << 20);     // link index field of SlotInfo::writer: 20 bits
   if (ctx->lk.cap > (int32_t)LINK_NONE - 1) ctx->lk.cap = (int32_t)LINK_NONE - 1;
-  rcx |= dev_alloc(ctx, ctx->d_lk_rec, (size_t)ctx->lk.cap * 4);
+  nomem |= dev_alloc(ctx, ctx->d_lk_rec, (size_t)ctx->lk.cap * 4);
   ctx->ri.flen = ctx->d_ri_flen; ctx->ri.blen = ctx->d_ri_blen; ctx->ri.actf = ctx->d_ri_actf; ctx->ri.trec = ctx->d_ri_trec;
   ctx->si.reclen = ctx->d_si_reclen; ctx->si.recact = ctx->d_si_recact; ctx->si.writer = ctx->d_si_writer; ctx->si.mult = ctx->d_si_mult;
   ctx->lk.rec = ctx->d_lk_rec;
-  if (rcx) return MIA_HIP_ERR_NOMEM;
+  if (nomem) return MIA_HIP_ERR_NOMEM;
   HIPCHK(hipMemcpyAsync(ctx->d_packed, packed.data(), packed.size(), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(ctx->d_roff, roff.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemcpyAsync(ctx->d_len, len.data(), (size_t)n * 2, hipMemcpyHostToDevice, ctx->stream));
@@ -720,8 +693,11 @@ static int stage_launch(mia_hip_ctx* ctx, Stage st, void (*kernel)(KArgs...), di
   return 0;
 }
 
-static void drain_events(mia_hip_ctx* ctx) {
-  for (auto& t : ctx->stg) {
+// what the recorded event pairs measured goes into their stages' sums; `except`: one stage whose pairs stay pending (its end is not recorded yet)
+static void drain_events(mia_hip_ctx* ctx, int except = -1) {
+  for (int k = 0; k < STG_COUNT; k++) {
+    if (k == except) continue;
+    auto& t = ctx->stg[k];
     for (auto& e : t.pending) {
       float ms = 0;
       if (hipEventSynchronize(e.second) == hipSuccess && hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) {
@@ -982,6 +958,7 @@ static void align_counters_collect(mia_hip_ctx* ctx, const int32_t* hb, bool fil
 
 // ---- align_all: the route is decided in ONE place (align_route.h: align_route), the stages below follow it --------------------------
 static_assert(ROUTE_QCH == BX_QCH && ROUTE_MAXW == BX_MAXW, "align_route.h carries copies of the two");
+static_assert(P1_ROUTE_WILD == BX_WILD, "pass1_route.h carries a copy");
 
 // What the stages of one alignment hand each other.  Nothing of it outlives the call: the context keeps align_end_signalled and spec_*.
 struct AlignCall {

@@ -41,11 +41,11 @@ extern "C" int mia_hip_trim(mia_hip_ctx* ctx, const char* adapter, int64_t n, co
   DevBuf<uint32_t> d_status;
   DevBuf<unsigned char> d_slabs;
   DevBuf<int16_t> d_cols;
-  int rcx = dev_alloc(ctx, d_codes, chars + 8) | dev_alloc(ctx, d_ap, (int64_t)apacked.size()) | dev_alloc(ctx, d_ac, len2) |
+  int nomem = dev_alloc(ctx, d_codes, chars + 8) | dev_alloc(ctx, d_ap, (int64_t)apacked.size()) | dev_alloc(ctx, d_ac, len2) |
             dev_alloc(ctx, d_trimmed, n) | dev_alloc(ctx, d_off, n + 1) | dev_alloc(ctx, d_flat, PSSM_WORDS) |
             dev_alloc(ctx, d_tp, n) | dev_alloc(ctx, d_status, n) | dev_alloc(ctx, d_slabs, slab * grid) |
             dev_alloc(ctx, d_cols, grid * MAX_READ);
-  if (rcx) return MIA_HIP_ERR_NOMEM;
+  if (nomem) return MIA_HIP_ERR_NOMEM;
   hipError_t e = hipSuccess;
   auto up = [&](void* d, const void* h, size_t b) { if (e == hipSuccess && b) e = hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream); };
   up(d_codes, codes.data(), (size_t)chars); up(d_ap, apacked.data(), apacked.size()); up(d_ac, acodes.data(), (size_t)len2);
@@ -144,14 +144,14 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->ma_ace_cols_ok = cols_ok;
   ctx->ma_sam_gaps_ok = ma_sam_gaps_ok(gaps, ref_len);
   DevBuf<int32_t> d_irec;   // every temporary is released on any return
-  int rcx = dev_alloc(ctx, ctx->d_ma_start, n + 1) | dev_alloc(ctx, ctx->d_ma_rev, n + 1) | dev_alloc(ctx, ctx->d_ma_coff, n + 1) |
+  int nomem = dev_alloc(ctx, ctx->d_ma_start, n + 1) | dev_alloc(ctx, ctx->d_ma_rev, n + 1) | dev_alloc(ctx, ctx->d_ma_coff, n + 1) |
             dev_alloc(ctx, ctx->d_ma_seq, chars + MA_REC_LANE) | dev_alloc(ctx, ctx->d_ma_smp, chars + MA_REC_LANE) | dev_alloc(ctx, d_irec, n_ins + 1) |
             dev_alloc(ctx, ctx->d_ma_ipos, n_ins + 1) | dev_alloc(ctx, ctx->d_ma_ioff, n_ins + 1) |
             dev_alloc(ctx, ctx->d_ma_ib, ins_chars + MA_REC_LANE) | dev_alloc(ctx, ctx->d_ma_gaps, ref_len) |
             dev_alloc(ctx, ctx->d_ma_rec_ins, n + 1) | dev_alloc(ctx, ctx->d_ma_ins_list, n_ins + 1) |
             dev_alloc(ctx, ctx->d_ma_colmap, (int64_t)ref_len + 1) | dev_alloc(ctx, ctx->d_ma_rows, n + 1) |
             dev_alloc(ctx, ctx->d_ma_ctl, (int64_t)MAR_STATE + n / MAR_PER_WG + 2);
-  if (rcx) return MIA_HIP_ERR_NOMEM;
+  if (nomem) return MIA_HIP_ERR_NOMEM;
   ctx->ma_n = n;                                   // (nothing reads them before ma_resident is set again)
   ctx->ma_n_ins = n_ins;
   ctx->ma_L = ref_len;
@@ -511,15 +511,6 @@ extern "C" int mia_hip_get_ins_tally(mia_hip_ctx* ctx, int32_t* ins_off, int32_t
 }
 
 // ---- pass 1 ----------------------------------------------------------------------------
-static char revcom_char_host(char b) {   // src/map_align.c:418-432
-  static const char tbl[] = "TVGH\0\0CD\0\0M\0KN\0\0\0YSAABWXR\0";
-  char r = 0;
-  if (b == '-') return '-';
-  if (b >= 'A' && b <= 'Z') r = tbl[b - 'A'];
-  else if (b >= 'a' && b <= 'z') r = (char)(tbl[b - 'a'] + 32);
-  return r ? r : 'N';
-}
-
 // populate_kpa + add_kmer (src/kmer.c:65-107,153-168): the k-mers that occur in `seq`, each with its ascending
 // positions (at most 128; further ones are silently dropped, :75-77).  Only the occurring k-mers are listed -- the
 // dense 4^k table is zeroed and filled on the device.
@@ -553,350 +544,406 @@ static void build_kmer_lists(const std::string& seq, int k, int soft_mask, std::
   pos.push_back(0);
 }
 
-// Lets align_all run on a borrowed read set and reference (the anchored part of pass 1) and puts the context back as it was.
-// The lists and the reference are lent through their owners' .p (the blocks come from the pool, the owners' own blocks are put
-// back here): align_all only reads these five, nothing allocates them while they are lent.
+// What align_all reads, overwrites or counts in the context while it runs on a borrowed read set and reference (the anchored part of
+// pass 1): each field is named ONCE, here; AlignBorrow copies these out and assigns them back.
+//   RESTORED: the read set and its longest read; the four lists and the reference (lent through their owners' .p: the blocks come
+//   from the pool, the owners' own blocks are put back -- align_all only reads these five, nothing allocates them while they are
+//   lent); L, wrap, explicit_win, use_filter; what the context knows of its own alignment (aligned, culled, tallied, pre_cull_valid,
+//   diag_scripts_missing); ref_mostly_bases and kh_entries; the read counts of mia_hip_plain_stats, _filter_stats and _bx_stats; and,
+//   beside this list, every stage timer's sum and launch count but pass 1's (AlignBorrow itself).
+//   LEFT BEHIND by the borrowed run: bx_last, the band pipeline's counters of the last alignment -- the job's next alignment reads its
+//   rejects from them (AlignRouteIn::rejects), which moves reads between exact kernels and changes no result; bx_launches, band_done,
+//   direct_open_steps and quick_steps, which are statistics; align_end_signalled, which every alignment sets anew before anything
+//   reads it; and the buffers the borrowed run grows (trace slabs, the open list and the like), which every alignment sizes for itself.
+static auto align_lent_fields(mia_hip_ctx* c) {
+  return std::tie(c->rs, c->d_bin_of.p, c->d_list.p, c->d_wide_list.p, c->d_retry_list.p, c->max_len, c->d_ref.p, c->L, c->wrap, c->explicit_win,
+                  c->use_filter, c->aligned, c->culled, c->tallied, c->pre_cull_valid, c->ref_mostly_bases, c->diag_scripts_missing, c->kh_entries,
+                  c->plain_total, c->plain_retried, c->filter_seen, c->filter_proven, c->bx_seen, c->bx_done[0], c->bx_done[1], c->bx_done[2]);
+}
+template <class... T>
+static std::tuple<T...> tuple_values(const std::tuple<T&...>& refs) { return std::tuple<T...>(refs); }
+
+// Lets align_all run on a borrowed read set and reference and puts the context back as it was (align_lent_fields).  The stage
+// timers of the iteration path must not see what the borrowed run adds (bench.py's roofline reads them): what is pending goes into
+// their sums first, and what the borrowed run leaves pending is dropped with the sums put back.  Pass 1's own pair, whose end is not
+// recorded yet, stays pending.
 struct AlignBorrow {
   mia_hip_ctx* c;
-  ReadSet rs; int32_t *bin_of, *list, *wide, *retry; int max_len; uint8_t* d_ref; int L, wrap, explicit_win, use_filter;
-  bool aligned, culled, tallied, pre_cull_valid, ref_mostly_bases, diag_scripts_missing;
-  int64_t kh_entries;
-  int64_t plain_total, plain_retried, filter_seen, filter_proven, bx_seen, bx_done0, bx_done1, bx_done2;
-  double stg_ms[STG_COUNT]; int64_t stg_launches[STG_COUNT];
-  explicit AlignBorrow(mia_hip_ctx* ctx)
-      : c(ctx), rs(ctx->rs), bin_of(ctx->d_bin_of), list(ctx->d_list), wide(ctx->d_wide_list), retry(ctx->d_retry_list), max_len(ctx->max_len),
-        d_ref(ctx->d_ref), L(ctx->L), wrap(ctx->wrap), explicit_win(ctx->explicit_win), use_filter(ctx->use_filter), aligned(ctx->aligned),
-        culled(ctx->culled), tallied(ctx->tallied), pre_cull_valid(ctx->pre_cull_valid), ref_mostly_bases(ctx->ref_mostly_bases),
-        diag_scripts_missing(ctx->diag_scripts_missing), kh_entries(ctx->kh_entries), plain_total(ctx->plain_total), plain_retried(ctx->plain_retried), filter_seen(ctx->filter_seen), filter_proven(ctx->filter_proven),
-        bx_seen(ctx->bx_seen), bx_done0(ctx->bx_done[0]), bx_done1(ctx->bx_done[1]), bx_done2(ctx->bx_done[2]) {
-    // the stage timers of the iteration path must not see what the borrowed runs add (bench.py's roofline reads them)
-    for (int k = 0; k < STG_COUNT; k++) {
-      if (k == STG_PASS1) continue;
-      float ms = 0;
-      for (auto& e : ctx->stg[k].pending) {
-        if (hipEventSynchronize(e.second) == hipSuccess && hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) { ctx->stg[k].ms += ms; ctx->stg[k].launches++; }
-        ctx->ev_free.push_back(e);
-      }
-      ctx->stg[k].pending.clear();
-      stg_ms[k] = ctx->stg[k].ms; stg_launches[k] = ctx->stg[k].launches;
-    }
+  decltype(tuple_values(align_lent_fields(nullptr))) saved;
+  double stg_ms[STG_COUNT];
+  int64_t stg_launches[STG_COUNT];
+  explicit AlignBorrow(mia_hip_ctx* ctx) : c(ctx), saved(tuple_values(align_lent_fields(ctx))) {
+    drain_events(c, STG_PASS1);
+    for (int k = 0; k < STG_COUNT; k++) { stg_ms[k] = c->stg[k].ms; stg_launches[k] = c->stg[k].launches; }
   }
   ~AlignBorrow() {
-    for (int k = 0; k < STG_COUNT; k++) {
-      if (k == STG_PASS1) continue;
-      for (auto& e : c->stg[k].pending) { (void)hipEventSynchronize(e.second); c->ev_free.push_back(e); }
-      c->stg[k].pending.clear();
-      c->stg[k].ms = stg_ms[k]; c->stg[k].launches = stg_launches[k];
-    }
-    c->rs = rs; c->d_bin_of.p = bin_of; c->d_list.p = list; c->d_wide_list.p = wide; c->d_retry_list.p = retry; c->max_len = max_len; c->d_ref.p = d_ref;
-    c->L = L; c->wrap = wrap; c->explicit_win = explicit_win; c->use_filter = use_filter; c->aligned = aligned; c->culled = culled;
-    c->tallied = tallied; c->pre_cull_valid = pre_cull_valid; c->ref_mostly_bases = ref_mostly_bases; c->kh_entries = kh_entries; c->diag_scripts_missing = diag_scripts_missing; c->plain_total = plain_total;
-    c->plain_retried = plain_retried; c->filter_seen = filter_seen; c->filter_proven = filter_proven;
-    c->bx_seen = bx_seen; c->bx_done[0] = bx_done0; c->bx_done[1] = bx_done1; c->bx_done[2] = bx_done2;
+    drain_events(c, STG_PASS1);
+    for (int k = 0; k < STG_COUNT; k++)
+      if (k != STG_PASS1) { c->stg[k].ms = stg_ms[k]; c->stg[k].launches = stg_launches[k]; }
+    align_lent_fields(c) = saved;
   }
 };
+
+// One mia_hip_pass1 call: its arguments, the route (pass1_route.h), what the host prepares and the device temporaries, which go back
+// to the context's pool when the call ends, whichever way.  The stages below run in the order they are written in.
+struct Pass1Call {
+  mia_hip_ctx* ctx;
+  const char* ref; int L, circular, kmer_len, soft_mask;
+  int64_t n; const char* bases; const int64_t* offsets;
+  int32_t* score; uint8_t* rc; int32_t *as, *ae; uint8_t* flags;
+  PackParams pk;
+  Pass1Route r;
+  // host side
+  std::string fw, rcs;                           // both strands, wrapped: make_reverse_complement, add_ref_wrap -- src/mia_main.c:637-676
+  std::vector<uint8_t> cf, cr, packed;           // their codes; the reads' 4-bit codes
+  std::vector<uint32_t> roff; std::vector<uint16_t> len;
+  uint64_t total = 0; int max_len = 1;
+  int64_t p1_other = 0;                          // N columns of the forward strand
+  // device side
+  PoolLease<uint8_t> d_cf, d_cr, d_packed, d_rc, d_flags;
+  PoolLease<uint32_t> d_tab[2], d_kl[2], d_el[2], d_roff, d_status, d_ckpt, d_ntodo;
+  PoolLease<int32_t> d_pos[2], d_score, d_as, d_ae, d_todo, d_p1kcnt, d_p1kpos;
+  PoolLease<uint16_t> d_len;
+  PoolLease<unsigned char> d_trace;
+  PoolLease<uint64_t> d_p1planes;
+  KmerIndex kx{};
+  Pass1Reads pr{};
+  int64_t n_dp = 0;                              // reads no stage has decided yet
+  bool p1_timed = false;
+  // MIA_HIP_P1_TIMING: the tools read these lines
+  bool timing = false;
+  std::chrono::steady_clock::time_point t_start;
+  void lap(const char* what) {
+    if (!timing) return;
+    auto t = std::chrono::steady_clock::now();
+    fprintf(stderr, "[mia_hip_pass1] %-12s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_start).count());
+    t_start = t;
+  }
+  KmerOcc kocc(int strand) const { return KmerOcc{d_p1kcnt + strand * DF_KTAB, d_p1kpos + strand * DF_KTAB * DF_KCAP}; }
+};
+
+static void pass1_host_reference(Pass1Call& p) {
+  const int L = p.L, wl = p.circular ? (L < MAX_READ ? L : MAX_READ) : 0, wrap = L + wl;
+  p.fw.assign(p.ref, p.ref + L);
+  p.rcs.assign((size_t)L, 'N');
+  for (int i = 0; i < L; i++) p.rcs[i] = revcom_char_host(p.ref[L - 1 - i]);
+  p.fw += p.fw.substr(0, wl);
+  p.rcs += p.rcs.substr(0, wl);
+  p.cf.assign((size_t)wrap + 64, 4);
+  p.cr.assign((size_t)wrap + 64, 4);
+  for (int i = 0; i < wrap; i++) {
+    p.cf[i] = base_code((char)toupper((unsigned char)p.fw[i]));
+    p.cr[i] = base_code((char)toupper((unsigned char)p.rcs[i]));
+  }
+  for (int i = 0; i < L; i++) p.p1_other += p.cf[(size_t)i] > 3;
+}
+
+// reads (as sequenced); validated before anything is allocated on the device
+static int pass1_index_reads(Pass1Call& p) {
+  mia_hip_ctx* ctx = p.ctx;
+  p.roff.resize((size_t)p.n);
+  p.len.resize((size_t)p.n);
+  for (int64_t i = 0; i < p.n; i++) {
+    int64_t l = p.offsets[i + 1] - p.offsets[i];
+    if (l < 1 || l > MIA_HIP_MAX_READ) { ctx->err = "read length outside 1..256"; return MIA_HIP_ERR_ARG; }
+    p.roff[i] = (uint32_t)p.total; p.len[i] = (uint16_t)l;
+    if (l > p.max_len) p.max_len = (int)l;
+    p.total += (uint64_t)(((l + 1) / 2 + 3) & ~3);
+    if (p.total >= ((uint64_t)1 << 32)) { ctx->err = "packed read store exceeds 4 GiB per call"; return MIA_HIP_ERR_ARG; }
+  }
+  return MIA_HIP_OK;
+}
+
+static auto pass1_kernel(const Pass1Route& r) { return r.cpl == P1_CPL_WIDE ? k_pass1<P1_CPL_WIDE> : k_pass1<P1_CPL_NARROW>; }
+
+// everything pass1_route() reads; the walk over both strands for the N columns' spellings only where the route will use its answer
+static Pass1RouteIn pass1_route_input(const Pass1Call& p) {
+  const mia_hip_ctx* ctx = p.ctx;
+  Pass1RouteIn in;
+  in.n = p.n; in.max_len = p.max_len; in.L = p.L; in.circular = p.circular != 0; in.kmer_len = p.kmer_len;
+  in.max_pos = ctx->max_pos; in.flat = ctx->flat; in.bx_ok = ctx->bx_ok; in.use_bx = ctx->use_bx; in.use_filter = ctx->use_filter;
+  in.p1_other = p.p1_other;
+  in.alt_cpl = alt_int("MIA_HIP_P1_CPL"); in.alt_plain = alt_int("MIA_HIP_P1_PLAIN");
+  in.cus = ctx->cus;
+  if (pass1_wants_wild(in)) {
+    const int len1 = pass1_len1(in);
+    std::vector<uint8_t> both(p.cf.begin(), p.cf.begin() + len1);
+    both.insert(both.end(), p.cr.begin(), p.cr.begin() + len1);
+    in.wild_entries = kh_wild_entries(both.data(), (int64_t)both.size(), BX_WILD);
+  }
+  return in;
+}
+
+// the route, its refusals, and the persistent grid: the workgroups of k_pass1<cpl> that are resident at once with this call's LDS
+static int pass1_decide(Pass1Call& p) {
+  mia_hip_ctx* ctx = p.ctx;
+  p.r = pass1_route(pass1_route_input(p));
+  if (p.r.refusal != P1_REFUSE_NONE) { ctx->err = pass1_refusal_message(p.r.refusal); return pass1_refusal_code(p.r.refusal); }
+  HIPCHK(hipFuncSetAttribute((const void*)pass1_kernel(p.r), hipFuncAttributeMaxDynamicSharedMemorySize, P1_LDS_LIMIT));
+  int waves_cu = 0;
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_cu, (const void*)pass1_kernel(p.r), 64, (size_t)p.r.lds));
+  if (waves_cu < 1) { ctx->err = "pass-1 kernel does not fit a compute unit"; return MIA_HIP_ERR_RANGE; }
+  pass1_set_grid(p.r, waves_cu, ctx->cus, p.n);
+  return MIA_HIP_OK;
+}
+
+// mia -k: the dense 4^k tables of both strands, filled on the device from the lists of the k-mers that occur
+static int pass1_kmer_tables(Pass1Call& p) {
+  mia_hip_ctx* ctx = p.ctx;
+  if (pool_take(ctx, p.d_cf, p.cf.size()) || pool_take(ctx, p.d_cr, p.cr.size())) return MIA_HIP_ERR_NOMEM;
+  p.kx.k = p.kmer_len > 0 ? p.kmer_len : -1;
+  if (p.kx.k <= 0) return MIA_HIP_OK;
+  const size_t nk = (size_t)1 << (2 * p.kx.k);
+  for (int s = 0; s < 2; s++) {
+    std::vector<uint32_t> kmer, entry;
+    std::vector<int32_t> pos;
+    build_kmer_lists(s ? p.rcs : p.fw, p.kx.k, p.soft_mask, kmer, entry, pos);
+    const size_t ne = kmer.size();
+    if (pool_take(ctx, p.d_tab[s], nk) || pool_take(ctx, p.d_pos[s], pos.size()) || pool_take(ctx, p.d_kl[s], ne + 1) || pool_take(ctx, p.d_el[s], ne + 1))
+      return MIA_HIP_ERR_NOMEM;
+    hipError_t ke = hipMemsetAsync(p.d_tab[s], 0, nk * 4, ctx->stream);
+    if (ke == hipSuccess) ke = hipMemcpy(p.d_pos[s], pos.data(), pos.size() * 4, hipMemcpyHostToDevice);
+    if (ke == hipSuccess && ne) ke = hipMemcpy(p.d_kl[s], kmer.data(), ne * 4, hipMemcpyHostToDevice);
+    if (ke == hipSuccess && ne) ke = hipMemcpy(p.d_el[s], entry.data(), ne * 4, hipMemcpyHostToDevice);
+    if (ke == hipSuccess && ne) {
+      hipLaunchKernelGGL(k_kmer_fill, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream, (int32_t)ne, p.d_kl[s], p.d_el[s], p.d_tab[s]);
+      ke = hipGetLastError();
+    }
+    if (ke != hipSuccess) { ctx->err = std::string("pass1 k-mer table: ") + hipGetErrorString(ke); return MIA_HIP_ERR_DEVICE; }
+    p.kx.tab[s] = p.d_tab[s];
+    p.kx.pos[s] = p.d_pos[s];
+  }
+  return MIA_HIP_OK;
+}
+
+// (every allocation first: an early return leaves no copy in flight from the host vectors)
+static int pass1_allocate(Pass1Call& p) {
+  mia_hip_ctx* ctx = p.ctx;
+  const Pass1Route& r = p.r;
+  const size_t n = (size_t)p.n;
+  p.packed.assign((size_t)p.total + 8, 0);
+  pack_reads(p.n, p.bases, p.offsets, p.roff.data(), p.len.data(), p.packed.data());
+  if (p.timing) fprintf(stderr, "[mia_hip_pass1] cpl %d plain %d waves/CU %d lds %d\n", r.cpl, r.plain, r.waves_cu, r.lds);
+  if (pool_take(ctx, p.d_packed, p.packed.size()) || pool_take(ctx, p.d_roff, n) || pool_take(ctx, p.d_len, n) || pool_take(ctx, p.d_rc, n) ||
+      pool_take(ctx, p.d_flags, n) || pool_take(ctx, p.d_status, n) || pool_take(ctx, p.d_score, n) || pool_take(ctx, p.d_as, n) ||
+      pool_take(ctx, p.d_ae, n) || pool_take(ctx, p.d_trace, (size_t)(r.trace_bytes * r.grid)) || pool_take(ctx, p.d_ckpt, (size_t)(r.ckpt_words * r.grid)))
+    return MIA_HIP_ERR_NOMEM;
+  if (r.need_todo && (pool_take(ctx, p.d_todo, n) || pool_take(ctx, p.d_ntodo, 1))) return MIA_HIP_ERR_NOMEM;
+  if (r.need_ktab && (pool_take(ctx, p.d_p1kcnt, (size_t)DF_KTAB * 2) || pool_take(ctx, p.d_p1kpos, (size_t)DF_KTAB * DF_KCAP * 2))) return MIA_HIP_ERR_NOMEM;
+  if (r.filtered && pool_take(ctx, p.d_p1planes, (size_t)plane_words(r.len1) * 6)) return MIA_HIP_ERR_NOMEM;
+  p.pr = Pass1Reads{p.n, p.d_packed, p.d_roff, p.d_len, p.d_score, p.d_as, p.d_ae, p.d_rc, p.d_flags, p.d_status};
+  return MIA_HIP_OK;
+}
+
+// reference codes and reads go up; the call's device time (filter, anchored windows and DP) is measured from behind them
+static int pass1_upload(Pass1Call& p) {
+  mia_hip_ctx* ctx = p.ctx;
+  auto up = [&](void* d, const void* h, size_t b) { return hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream); };
+  HIPCHK(up(p.d_cf, p.cf.data(), p.cf.size()));
+  HIPCHK(up(p.d_cr, p.cr.data(), p.cr.size()));
+  HIPCHK(up(p.d_packed, p.packed.data(), p.packed.size()));
+  HIPCHK(up(p.d_roff, p.roff.data(), (size_t)p.n * 4));
+  HIPCHK(up(p.d_len, p.len.data(), (size_t)p.n * 2));
+  p.n_dp = p.n;
+  ctx->pass1_filtered = 0;
+  ctx->pass1_anchored = 0;
+  drain_events(ctx);                       // (nothing of an earlier call may sit in the pass-1 timer)
+  p.p1_timed = ((ctx->stage_mask >> STG_PASS1) & 1u) && stage_begin(ctx, STG_PASS1) == 0;
+  return MIA_HIP_OK;
+}
+
+static void pass1_kmer_occ(Pass1Call& p, int wild) {
+  const int len1 = p.r.len1;
+  hipStream_t s = p.ctx->stream;
+  hipLaunchKernelGGL(k_kmer_occ, dim3((unsigned)((len1 + 255) / 256)), dim3(256), 0, s, p.d_cf, (int64_t)len1, p.d_p1kcnt, p.d_p1kpos, wild);
+  hipLaunchKernelGGL(k_kmer_occ, dim3((unsigned)((len1 + 255) / 256)), dim3(256), 0, s, p.d_cr, (int64_t)len1, p.d_p1kcnt + DF_KTAB,
+                     p.d_p1kpos + DF_KTAB * DF_KCAP, wild);
+}
+
+// The diagonal filter (diag_filter.h) decides most reads by bit-parallel comparison against every diagonal of both strands; the
+// list of the reads it leaves goes to the stages behind it.
+static int pass1_filter_stage(Pass1Call& p) {
+  mia_hip_ctx* ctx = p.ctx;
+  const int len1 = p.r.len1;
+  const int64_t n = p.n, words = plane_words(len1);
+  uint64_t* pl = p.d_p1planes;
+  const unsigned planes_grid = (unsigned)((words + 3) / 4 < 4096 ? (words + 3) / 4 : 4096);
+  hipLaunchKernelGGL(k_ref_planes, dim3(planes_grid), dim3(256), 0, ctx->stream, p.d_cf, (int64_t)len1, words, pl, pl + words, pl + 2 * words);
+  hipLaunchKernelGGL(k_ref_planes, dim3(planes_grid), dim3(256), 0, ctx->stream, p.d_cr, (int64_t)len1, words, pl + 3 * words, pl + 4 * words, pl + 5 * words);
+  HIPCHK(hipMemsetAsync(p.d_ntodo, 0, 4, ctx->stream));
+  RefPlanes pf{pl, pl + words, pl + 2 * words}, prc{pl + 3 * words, pl + 4 * words, pl + 5 * words};
+  // 10-mer tables of both strands for rule (c) (diag_filter.h: KmerOcc)
+  KmerOcc kf{nullptr, nullptr}, kr{nullptr, nullptr};
+  if (p.r.need_ktab) {
+    HIPCHK(hipMemsetAsync(p.d_p1kcnt, 0, (size_t)DF_KTAB * 2 * 4, ctx->stream));
+    pass1_kmer_occ(p, 0);
+    kf = p.kocc(0); kr = p.kocc(1);
+  }
+  hipLaunchKernelGGL(k_pass1_filter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, p.pr, pf, prc, kf, kr, len1, p.L, p.d_todo, p.d_ntodo);
+  HIPCHK(hipGetLastError());
+  uint32_t h_ntodo = 0;
+  HIPCHK(hipMemcpyAsync(&h_ntodo, p.d_ntodo, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  p.n_dp = h_ntodo;
+  ctx->pass1_filtered = n - p.n_dp;
+  if (p.timing) fprintf(stderr, "[mia_hip_pass1] diagonal filter: %lld of %lld reads decided\n", (long long)(n - p.n_dp), (long long)n);
+  return MIA_HIP_OK;
+}
+
+// The anchored stage's temporaries: one allocation for all of them (twenty separate ones cost more than the stage)
+struct Pass1Arena {
+  PoolLease<unsigned char> block;
+  uint32_t *roff, *status, *nrest;
+  uint16_t* len;
+  uint8_t *rc, *sk, *ref2;
+  int32_t *as, *ae, *score, *refstart, *bin, *list, *wide, *retry, *rest, *bound, *budget, *u;
+  int16_t *abr, *cols;
+  int take(mia_hip_ctx* ctx, int64_t m, int64_t n_dp, int len1, int stride) {
+    size_t top = 0;
+    auto carve = [&](size_t bytes) { const size_t at = top; top += (bytes + 255) & ~(size_t)255; return at; };
+    const size_t o_roff = carve((size_t)m * 4), o_status = carve((size_t)m * 4), o_nrest = carve(64), o_len = carve((size_t)m * 2),
+                 o_rc = carve((size_t)m), o_sk = carve((size_t)m), o_ref2 = carve((size_t)2 * len1 + 64), o_as = carve((size_t)m * 4),
+                 o_ae = carve((size_t)m * 4), o_score = carve((size_t)m * 4), o_refstart = carve((size_t)m * 4), o_bin = carve((size_t)m * 4),
+                 o_list = carve(((size_t)m + 4 * N_BINS) * 4), o_wide = carve((size_t)m * 4), o_retry = carve((size_t)m * 4),
+                 o_rest = carve((size_t)n_dp * 4), o_abr = carve((size_t)m * 2), o_cols = carve((size_t)m * stride * 2),
+                 o_bound = carve((size_t)n_dp * 4), o_budget = carve((size_t)n_dp * 4), o_u = carve((size_t)n_dp * 4);
+    if (pool_take(ctx, block, top)) return MIA_HIP_ERR_NOMEM;
+    unsigned char* a = block;
+    roff = (uint32_t*)(a + o_roff); status = (uint32_t*)(a + o_status); nrest = (uint32_t*)(a + o_nrest);
+    len = (uint16_t*)(a + o_len);
+    rc = a + o_rc; sk = a + o_sk; ref2 = a + o_ref2;
+    as = (int32_t*)(a + o_as); ae = (int32_t*)(a + o_ae); score = (int32_t*)(a + o_score); refstart = (int32_t*)(a + o_refstart);
+    bin = (int32_t*)(a + o_bin); list = (int32_t*)(a + o_list); wide = (int32_t*)(a + o_wide); retry = (int32_t*)(a + o_retry);
+    rest = (int32_t*)(a + o_rest); bound = (int32_t*)(a + o_bound); budget = (int32_t*)(a + o_budget); u = (int32_t*)(a + o_u);
+    abr = (int16_t*)(a + o_abr); cols = (int16_t*)(a + o_cols);
+    return MIA_HIP_OK;
+  }
+};
+
+// align_all on the windows the anchors chose: the context is lent the arena's read set and the two strands as one reference
+static int pass1_align_windows(Pass1Call& p, Pass1Arena& w, int64_t m, int stride) {
+  mia_hip_ctx* ctx = p.ctx;
+  AlignBorrow borrow(ctx);
+  ReadSet& r = ctx->rs;
+  r.n = m; r.packed = p.d_packed; r.roff = w.roff; r.len = w.len; r.rc = w.rc; r.sk = w.sk; r.as = w.as; r.ae = w.ae; r.score = w.score;
+  r.refstart = w.refstart; r.abr = w.abr; r.status = w.status; r.cols = w.cols; r.stride = stride;
+  ctx->d_bin_of.p = w.bin; ctx->d_list.p = w.list; ctx->d_wide_list.p = w.wide; ctx->d_retry_list.p = w.retry; ctx->max_len = p.max_len;
+  ctx->d_ref.p = w.ref2; ctx->L = 2 * p.r.len1; ctx->wrap = 2 * p.r.len1; ctx->explicit_win = 1; ctx->use_filter = 0;
+  ctx->ref_mostly_bases = p.r.ref_mostly_bases; ctx->kh_entries = p.r.wild_entries;
+  ctx->wide_to_caller = true;
+  const int rc = align_all(ctx);
+  ctx->wide_to_caller = false;
+  return rc;
+}
+
+// Anchored stage (mia_pass1_kernels.h): what the filter left over is aligned in +-50 windows around the places where
+// six 10-mers of the read occur -- provably the same result as the whole-strand DP when the budget check of
+// k_pass1_select holds; everything else goes on to k_pass1.  Needs both strands free of N (a 10-mer with an N is not
+// in the table and an N column costs less than a mismatch), or tables that list the N columns under every spelling.
+static int pass1_anchor_stage(Pass1Call& p) {
+  mia_hip_ctx* ctx = p.ctx;
+  const int len1 = p.r.len1;
+  const int64_t n_dp = p.n_dp, m = n_dp * P1A_SLOTS;
+  const int stride = (p.max_len + 3) & ~3;
+  const unsigned per_read = (unsigned)((n_dp + 255) / 256);
+  if (!p.r.filtered) hipLaunchKernelGGL(k_iota, dim3(per_read), dim3(256), 0, ctx->stream, p.n, p.d_todo);      // no filter made the list: every read
+  if (p.r.rebuild_ktab_for_anchors) {
+    HIPCHK(hipMemsetAsync(p.d_p1kcnt, 0, (size_t)DF_KTAB * 2 * 4, ctx->stream));
+    pass1_kmer_occ(p, p.r.wild);
+  }
+  Pass1Arena w;
+  if (const int rc = w.take(ctx, m, n_dp, len1, stride)) return rc;
+  HIPCHK(hipMemsetAsync(w.rc, 0, (size_t)m, ctx->stream));
+  HIPCHK(hipMemsetAsync(w.abr, 0, (size_t)m * 2, ctx->stream));
+  HIPCHK(hipMemsetAsync(w.status, 0, (size_t)m * 4, ctx->stream));
+  HIPCHK(hipMemsetAsync(w.score, 0, (size_t)m * 4, ctx->stream));
+  HIPCHK(hipMemsetAsync(w.nrest, 0, 64, ctx->stream));
+  HIPCHK(hipMemsetAsync(w.ref2, 4, (size_t)2 * len1 + 64, ctx->stream));
+  HIPCHK(hipMemcpyAsync(w.ref2, p.d_cf, (size_t)len1, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(w.ref2 + len1, p.d_cr, (size_t)len1, hipMemcpyDeviceToDevice, ctx->stream));
+  BxTab p1tab;
+  p1tab.sub = ctx->d_bx_sub; p1tab.mrow = ctx->d_bx_mrow; p1tab.loss = ctx->d_bx_loss; p1tab.dl = ctx->d_bx_dl; p1tab.min_m = ctx->bx_min_m; p1tab.max_m = ctx->bx_max_m; p1tab.maxw = 32;
+  auto anchor = ctx->flat ? k_pass1_anchor<false> : k_pass1_anchor<true>;
+  hipLaunchKernelGGL(anchor, dim3(per_read), dim3(256), 0, ctx->stream, p.pr, p.d_todo, n_dp, p.kocc(0), p.kocc(1), len1, w.roff, w.len, w.sk, w.as, w.ae,
+                     w.bound, w.budget, w.u, p1tab);
+  HIPCHK(hipGetLastError());
+  if (const int rc = pass1_align_windows(p, w, m, stride)) return rc;
+  hipLaunchKernelGGL(k_pass1_select, dim3(per_read), dim3(256), 0, ctx->stream, p.pr, p.d_todo, n_dp, len1, p.L, w.sk, w.score, w.as, w.ae, w.abr, w.status,
+                     w.bound, w.budget, w.u, w.rest, w.nrest);
+  HIPCHK(hipGetLastError());
+  uint32_t h_rest[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(h_rest, w.nrest, 64, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const uint32_t h_nrest = h_rest[0];
+  if (p.timing) fprintf(stderr, "[mia_hip_pass1] left to the whole-strand DP: %u no cluster, %u unfinished windows, %u clipped, %u over budget, %u weak clusters\n",
+                        h_rest[1], h_rest[2], h_rest[3], h_rest[4], h_rest[5]);
+  if (p.timing) fprintf(stderr, "[mia_hip_pass1] no cluster: %u reads with N, %u too few blocks, %u too many clusters, %u too wide, %u too many strong, %u none strong, %u no room\n",
+                        h_rest[9], h_rest[10], h_rest[11], h_rest[12], h_rest[13], h_rest[14], h_rest[15]);
+  // the survivors' list replaces the filter's (d_todo is at least as long)
+  HIPCHK(hipMemcpyAsync(p.d_todo, w.rest, (size_t)h_nrest * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  ctx->pass1_anchored = n_dp - h_nrest;
+  if (p.timing) fprintf(stderr, "[mia_hip_pass1] anchored windows: %lld of %lld left-over reads decided\n", (long long)(n_dp - h_nrest), (long long)n_dp);
+  p.n_dp = h_nrest;
+  return MIA_HIP_OK;
+}
+
+// the whole-strand DP (k_pass1<CPL>) on what is left: all reads, or the list of the stages in front of it
+static int pass1_dp_stage(Pass1Call& p) {
+  mia_hip_ctx* ctx = p.ctx;
+  const Pass1Route& r = p.r;
+  const int64_t g = r.grid < p.n_dp ? r.grid : p.n_dp;
+  auto kfn = pass1_kernel(r);
+  hipLaunchKernelGGL(kfn, dim3((unsigned)g), dim3(64), r.lds, ctx->stream, p.pr, p.d_cf, p.d_cr, r.len1, p.L, ctx->d_pssm, p.pk, p.kx, p.d_trace,
+                     r.trace_bytes, p.d_ckpt, r.ckpt_words, r.rows_p, r.mask_words, r.plain, p.d_todo, p.n_dp);
+  HIPCHK(hipGetLastError());
+  return MIA_HIP_OK;
+}
+
+static int pass1_download(Pass1Call& p) {
+  mia_hip_ctx* ctx = p.ctx;
+  const size_t n = (size_t)p.n;
+  if (p.p1_timed) stage_end(ctx, STG_PASS1);
+  auto back = [&](void* h, const void* d, size_t b) { return hipMemcpyAsync(h, d, b, hipMemcpyDeviceToHost, ctx->stream); };
+  HIPCHK(back(p.score, p.d_score, n * 4));
+  HIPCHK(back(p.as, p.d_as, n * 4));
+  HIPCHK(back(p.ae, p.d_ae, n * 4));
+  HIPCHK(back(p.rc, p.d_rc, n));
+  HIPCHK(back(p.flags, p.d_flags, n));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  p.lap("h2d+kernel+d2h");
+  if (p.p1_timed && !ctx->stg[STG_PASS1].pending.empty()) {
+    // the whole call's device time (filter, anchored windows and DP), measured on the pair taken behind the upload
+    const auto pair = ctx->stg[STG_PASS1].pending.back();
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, pair.first, pair.second) == hipSuccess) ctx->pass1_ms = ms;
+  }
+  p.lap("done");
+  return MIA_HIP_OK;
+}
 
 extern "C" int mia_hip_pass1(mia_hip_ctx* ctx, const char* ref, int32_t ref_len, int circular, int kmer_len, int soft_mask,
                              int64_t n, const char* bases, const int64_t* offsets, int32_t* score, uint8_t* rc, int32_t* as,
                              int32_t* ae, uint8_t* flags) {
   if (!ctx || !ref || ref_len <= 0 || n < 0 || (n > 0 && (!bases || !offsets || !score || !rc || !as || !ae || !flags))) return MIA_HIP_ERR_ARG;
   if (!ctx->have_pssm) { ctx->err = "set_pssm must precede pass1"; return MIA_HIP_ERR_STATE; }
-  const bool timing = alt_env("MIA_HIP_P1_TIMING") != nullptr;
-  auto t_start = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "[mia_hip_pass1] %-12s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_start).count());
-    t_start = t;
-  };
   if (kmer_len > 14) { ctx->err = "Cannot use kmer length greater than 14"; return MIA_HIP_ERR_ARG; }   // MAX_KMER_LEN
   HIPCHK(hipSetDevice(ctx->device));
   if (n == 0) return MIA_HIP_OK;
-  PackParams pk;
-  if (!make_pack_params(1024, ctx->max_abs, &pk)) { ctx->err = "PSSM too large for the packed pass-1 kernel"; return MIA_HIP_ERR_RANGE; }
-  // reference strands: make_reverse_complement, add_ref_wrap, (k-mer tables), make_ref_upper -- src/mia_main.c:637-676
-  const int L = ref_len, wl = circular ? (L < MAX_READ ? L : MAX_READ) : 0, wrap = L + wl, len1 = circular ? wrap : L;
-  std::string fw(ref, ref + L), rcs((size_t)L, 'N');
-  for (int i = 0; i < L; i++) rcs[i] = revcom_char_host(ref[L - 1 - i]);
-  fw += fw.substr(0, wl);
-  rcs += rcs.substr(0, wl);
-  std::vector<uint8_t> cf((size_t)wrap + 64, 4), cr((size_t)wrap + 64, 4);
-  for (int i = 0; i < wrap; i++) { cf[i] = base_code((char)toupper((unsigned char)fw[i])); cr[i] = base_code((char)toupper((unsigned char)rcs[i])); }
-  // reads (as sequenced); validated before anything is allocated on the device
-  std::vector<uint32_t> roff((size_t)n);
-  std::vector<uint16_t> len((size_t)n);
-  uint64_t total = 0;
-  int max_len = 1;
-  for (int64_t i = 0; i < n; i++) {
-    int64_t l = offsets[i + 1] - offsets[i];
-    if (l < 1 || l > MIA_HIP_MAX_READ) { ctx->err = "read length outside 1..256"; return MIA_HIP_ERR_ARG; }
-    roff[i] = (uint32_t)total; len[i] = (uint16_t)l;
-    if (l > max_len) max_len = (int)l;
-    total += (uint64_t)(((l + 1) / 2 + 3) & ~3);
-    if (total >= ((uint64_t)1 << 32)) { ctx->err = "packed read store exceeds 4 GiB per call"; return MIA_HIP_ERR_ARG; }
-  }
-  // Chunk width.  Dropping candidates further left than the horizon `rel` is exact only if they can never beat a
-  // new start: a score is at most rows * max positive entry, a new start costs P(rows+1), a gap of >= rel-1 columns
-  // costs P(rel-1).  Wide chunks (768 columns, horizon 256) for the unmasked sweep when that holds, else narrow
-  // ones (256 columns, horizon 768), which also skip masked stretches at a finer grain.
-  auto horizon_ok = [&](int rel) {
-    return (int64_t)max_len * ctx->max_pos + (GOP + GEP * (max_len + 1)) < (int64_t)(GOP + GEP * (rel - 1));
-  };
-  int cpl = (kmer_len <= 0 && horizon_ok(p1_rel(P1_CPL_WIDE))) ? P1_CPL_WIDE : P1_CPL_NARROW;
-  if (const char* ev = alt_env("MIA_HIP_P1_CPL")) {
-    const int want = atoi(ev);
-    if ((want == P1_CPL_WIDE && horizon_ok(p1_rel(P1_CPL_WIDE))) || want == P1_CPL_NARROW) cpl = want;
-  }
-  if (!horizon_ok(p1_rel(cpl))) { ctx->err = "PSSM too large for the pass-1 candidate horizon"; return MIA_HIP_ERR_RANGE; }
-  const int P1_CH = p1_ch(cpl);
-  // the wide unmasked sweep runs on plain keys (pass1_body.h, run_plain); MIA_HIP_P1_PLAIN=0 keeps the packed sweep
-  int plain = 1;
-  if (const char* ev = alt_env("MIA_HIP_P1_PLAIN")) plain = atoi(ev) != 0;
-  if (kmer_len > 0 && (size_t)wrap >= ((size_t)1 << 24)) { ctx->err = "reference too long for the k-mer table"; return MIA_HIP_ERR_RANGE; }
-  uint8_t *d_cf = nullptr, *d_cr = nullptr;
-  uint32_t *d_tab[2] = {nullptr, nullptr}, *d_kl[2] = {nullptr, nullptr}, *d_el[2] = {nullptr, nullptr};
-  int32_t* d_pos[2] = {nullptr, nullptr};
-  uint8_t *d_packed = nullptr, *d_rc = nullptr, *d_flags = nullptr;
-  uint32_t *d_roff = nullptr, *d_status = nullptr;
-  uint16_t* d_len = nullptr;
-  int32_t *d_score = nullptr, *d_as = nullptr, *d_ae = nullptr;
-  unsigned char* d_trace = nullptr;
-  uint32_t* d_ckpt = nullptr;
-  uint64_t* d_p1planes = nullptr;
-  int32_t *d_p1kcnt = nullptr, *d_p1kpos = nullptr;
-  int32_t* d_todo = nullptr;
-  uint32_t* d_ntodo = nullptr;
-  PoolScope guard(ctx);   // every temporary below goes back to the context's pool on any return
-  guard.watch((void**)&d_p1planes); guard.watch((void**)&d_todo); guard.watch((void**)&d_ntodo); guard.watch((void**)&d_p1kcnt); guard.watch((void**)&d_p1kpos);
-  for (void** pp : {(void**)&d_cf, (void**)&d_cr, (void**)&d_tab[0], (void**)&d_tab[1], (void**)&d_kl[0], (void**)&d_kl[1], (void**)&d_el[0],
-                    (void**)&d_el[1], (void**)&d_pos[0], (void**)&d_pos[1], (void**)&d_packed, (void**)&d_rc, (void**)&d_flags, (void**)&d_roff,
-                    (void**)&d_status, (void**)&d_len, (void**)&d_score, (void**)&d_as, (void**)&d_ae, (void**)&d_trace, (void**)&d_ckpt})
-    guard.watch(pp);
-  int rcx = pool_alloc(ctx, &d_cf, cf.size()) | pool_alloc(ctx, &d_cr, cr.size());
-  KmerIndex kx{};
-  kx.k = kmer_len > 0 ? kmer_len : -1;
-  if (kx.k > 0 && !rcx) {
-    const size_t nk = (size_t)1 << (2 * kx.k);
-    for (int s = 0; s < 2 && !rcx; s++) {
-      std::vector<uint32_t> kmer, entry;
-      std::vector<int32_t> pos;
-      build_kmer_lists(s ? rcs : fw, kx.k, soft_mask, kmer, entry, pos);
-      const size_t ne = kmer.size();
-      rcx |= pool_alloc(ctx, &d_tab[s], nk) | pool_alloc(ctx, &d_pos[s], pos.size()) | pool_alloc(ctx, &d_kl[s], ne + 1) |
-             pool_alloc(ctx, &d_el[s], ne + 1);
-      if (rcx) break;
-      hipError_t ke = hipMemsetAsync(d_tab[s], 0, nk * 4, ctx->stream);
-      if (ke == hipSuccess) ke = hipMemcpy(d_pos[s], pos.data(), pos.size() * 4, hipMemcpyHostToDevice);
-      if (ke == hipSuccess && ne) ke = hipMemcpy(d_kl[s], kmer.data(), ne * 4, hipMemcpyHostToDevice);
-      if (ke == hipSuccess && ne) ke = hipMemcpy(d_el[s], entry.data(), ne * 4, hipMemcpyHostToDevice);
-      if (ke == hipSuccess && ne) {
-        hipLaunchKernelGGL(k_kmer_fill, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream, (int32_t)ne, d_kl[s], d_el[s], d_tab[s]);
-        ke = hipGetLastError();
-      }
-      if (ke != hipSuccess) { ctx->err = std::string("pass1 k-mer table: ") + hipGetErrorString(ke); rcx = 2; }
-      kx.tab[s] = d_tab[s];
-      kx.pos[s] = d_pos[s];
-    }
-  }
-  lap("ref+kmer");
-  std::vector<uint8_t> packed((size_t)total + 8, 0);
-  pack_reads(n, bases, offsets, roff.data(), len.data(), packed.data());
-  rcx |= pool_alloc(ctx, &d_packed, packed.size()) | pool_alloc(ctx, &d_roff, (size_t)n) | pool_alloc(ctx, &d_len, (size_t)n) |
-         pool_alloc(ctx, &d_rc, (size_t)n) | pool_alloc(ctx, &d_flags, (size_t)n) | pool_alloc(ctx, &d_status, (size_t)n) |
-         pool_alloc(ctx, &d_score, (size_t)n) | pool_alloc(ctx, &d_as, (size_t)n) | pool_alloc(ctx, &d_ae, (size_t)n);
-  // persistent grid; LDS: sub table + 5 carry arrays + 2 column masks
-  // (the column masks are only read when the k-mer filter is on)
-  const int nch = (len1 + P1_CH - 1) / P1_CH, mask_words = kmer_len > 0 ? nch * (P1_CH / 32) + 4 : 0;
-  const int lds = MAX_READ * 10 + 5 * MAX_READ * 4 + 2 * mask_words * 4;
-  const int rows_p = (max_len + 3) & ~3;
-  const int64_t trace_bytes = (int64_t)rows_p * P1_CH * 2, ckpt_words = (int64_t)2 * nch * 5 * rows_p;
-  if (lds > 160 * 1024) { ctx->err = "reference too long for the pass-1 LDS masks"; return MIA_HIP_ERR_RANGE; }
-  // persistent grid = exactly the waves that are resident at once (registers AND LDS): a wave that only starts
-  // when another has drained would run its whole share of the reads on a nearly idle GPU
-  auto kfn = (cpl == P1_CPL_WIDE) ? k_pass1<P1_CPL_WIDE> : k_pass1<P1_CPL_NARROW>;
-  HIPCHK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  int waves_cu = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&waves_cu, (const void*)kfn, 64, (size_t)lds));
-  if (waves_cu < 1) { ctx->err = "pass-1 kernel does not fit a compute unit"; return MIA_HIP_ERR_RANGE; }
-  // whole waves per SIMD only: an uneven remainder (13 = 4+3+3+3) measured slower than 12, the extra workgroups start late
-  if (waves_cu > 4) waves_cu &= ~3;
-  if (timing) fprintf(stderr, "[mia_hip_pass1] cpl %d plain %d waves/CU %d lds %d\n", cpl, plain, waves_cu, lds);
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, ctx->device));
-  int64_t grid = (int64_t)prop.multiProcessorCount * waves_cu;
-  if (grid > n) grid = n;
-  rcx |= pool_alloc(ctx, &d_trace, (size_t)(trace_bytes * grid)) | pool_alloc(ctx, &d_ckpt, (size_t)(ckpt_words * grid));
-  if (rcx) return rcx == 2 ? MIA_HIP_ERR_DEVICE : MIA_HIP_ERR_NOMEM;
-  lap("pack+alloc");
-  hipError_t e = hipSuccess;
-  bool p1_timed = false;
-  auto cp = [&](void* d, const void* h, size_t b) { if (e == hipSuccess) e = hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, ctx->stream); };
-  cp(d_cf, cf.data(), cf.size()); cp(d_cr, cr.data(), cr.size());
-  cp(d_packed, packed.data(), packed.size()); cp(d_roff, roff.data(), (size_t)n * 4); cp(d_len, len.data(), (size_t)n * 2);
-  // The diagonal filter (diag_filter.h) first, when its premises hold: flat matrix and no k-mer mask (a masked DP is a
-  // different recurrence).  It decides most reads by bit-parallel comparison against every diagonal of both strands;
-  // the whole-reference DP then runs on what is left.
-  int64_t p1_other = 0;
-  for (int i = 0; i < L; i++) p1_other += cf[(size_t)i] > 3;
-  const bool fast_ok = ctx->flat && ctx->use_filter && kmer_len <= 0 && len1 >= max_len;
-  // any other matrix the band pipeline has tables for: the anchored windows in losses (mia_pass1_kernels.h, GEN); the
-  // diagonal filter stays the flat matrix's
-  const bool gen_ok = !ctx->flat && ctx->bx_ok && ctx->use_bx && ctx->use_filter && kmer_len <= 0 && len1 >= max_len;
-  const bool filtered = fast_ok && p1_other * 50 <= L;
-  // the anchored stage behind it (or in its place: a reference full of ambiguity codes, mt311 itself, leaves the filter
-  // nothing to decide): the windows' 10-mer tables list the N columns under every spelling (bandx_body.h, N COLUMNS)
-  int64_t wild_entries = 0;
-  if ((fast_ok || gen_ok) && p1_other && len1 <= (1 << 22)) {
-    std::vector<uint8_t> both(cf.begin(), cf.begin() + len1);
-    both.insert(both.end(), cr.begin(), cr.begin() + len1);
-    wild_entries = kh_wild_entries(both.data(), (int64_t)both.size(), BX_WILD);
-    if (wild_entries > ((int64_t)1 << 24)) wild_entries = 0;
-  }
-  const bool anchored_ok = (fast_ok || gen_ok) && (p1_other == 0 || wild_entries > 0) && len1 <= (1 << 22);
-  int64_t n_dp = n;
-  ctx->pass1_filtered = 0;
-  ctx->pass1_anchored = 0;
-  if (e == hipSuccess) {
-    Pass1Reads pr{n, d_packed, d_roff, d_len, d_score, d_as, d_ae, d_rc, d_flags, d_status};
-    drain_events(ctx);                       // (nothing of an earlier call may sit in the pass-1 timer)
-    p1_timed = ((ctx->stage_mask >> STG_PASS1) & 1u) && stage_begin(ctx, STG_PASS1) == 0;
-    if (filtered || anchored_ok) {
-      if (pool_alloc(ctx, &d_todo, (size_t)n) || pool_alloc(ctx, &d_ntodo, 1)) return MIA_HIP_ERR_NOMEM;
-      if (len1 <= (1 << 22) && (pool_alloc(ctx, &d_p1kcnt, (size_t)DF_KTAB * 2) || pool_alloc(ctx, &d_p1kpos, (size_t)DF_KTAB * DF_KCAP * 2))) return MIA_HIP_ERR_NOMEM;
-    }
-    if (!filtered && anchored_ok) hipLaunchKernelGGL(k_iota, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, d_todo);
-    if (filtered) {
-      const int64_t words = plane_words(len1);
-      if (pool_alloc(ctx, &d_p1planes, (size_t)words * 6)) return MIA_HIP_ERR_NOMEM;
-      uint64_t* pl = d_p1planes;
-      hipLaunchKernelGGL(k_ref_planes, dim3((unsigned)((words + 3) / 4 < 4096 ? (words + 3) / 4 : 4096)), dim3(256), 0, ctx->stream, d_cf, (int64_t)len1, words, pl, pl + words, pl + 2 * words);
-      hipLaunchKernelGGL(k_ref_planes, dim3((unsigned)((words + 3) / 4 < 4096 ? (words + 3) / 4 : 4096)), dim3(256), 0, ctx->stream, d_cr, (int64_t)len1, words, pl + 3 * words, pl + 4 * words, pl + 5 * words);
-      e = hipMemsetAsync(d_ntodo, 0, 4, ctx->stream);
-      RefPlanes pf{pl, pl + words, pl + 2 * words}, prc{pl + 3 * words, pl + 4 * words, pl + 5 * words};
-      // 10-mer tables of both strands for rule (c) (diag_filter.h: KmerOcc)
-      KmerOcc kf{nullptr, nullptr}, kr{nullptr, nullptr};
-      if (d_p1kcnt) {
-        if (e == hipSuccess) e = hipMemsetAsync(d_p1kcnt, 0, (size_t)DF_KTAB * 2 * 4, ctx->stream);
-        hipLaunchKernelGGL(k_kmer_occ, dim3((unsigned)((len1 + 255) / 256)), dim3(256), 0, ctx->stream, d_cf, (int64_t)len1, d_p1kcnt, d_p1kpos, 0);
-        hipLaunchKernelGGL(k_kmer_occ, dim3((unsigned)((len1 + 255) / 256)), dim3(256), 0, ctx->stream, d_cr, (int64_t)len1, d_p1kcnt + DF_KTAB,
-                           d_p1kpos + DF_KTAB * DF_KCAP, 0);
-        kf.cnt = d_p1kcnt; kf.pos = d_p1kpos; kr.cnt = d_p1kcnt + DF_KTAB; kr.pos = d_p1kpos + DF_KTAB * DF_KCAP;
-      }
-      hipLaunchKernelGGL(k_pass1_filter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, pr, pf, prc, kf, kr, len1, L, d_todo, d_ntodo);
-      if (e == hipSuccess) e = hipGetLastError();
-      uint32_t h_ntodo = 0;
-      if (e == hipSuccess) e = hipMemcpyAsync(&h_ntodo, d_ntodo, 4, hipMemcpyDeviceToHost, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      n_dp = h_ntodo;
-      ctx->pass1_filtered = n - n_dp;
-      if (timing) fprintf(stderr, "[mia_hip_pass1] diagonal filter: %lld of %lld reads decided\n", (long long)(n - n_dp), (long long)n);
-    }
-    // Anchored stage (mia_pass1_kernels.h): what the filter left over is aligned in +-50 windows around the places where
-    // six 10-mers of the read occur -- provably the same result as the whole-strand DP when the budget check of
-    // k_pass1_select holds; everything else goes on to k_pass1.  Needs both strands free of N (a 10-mer with an N is not
-    // in the table and an N column costs less than a mismatch).
-    if (e == hipSuccess && anchored_ok && n_dp > 0 && d_p1kcnt) {
-      if (p1_other || !filtered) {            // the anchors' tables: with the N columns' spellings (the filter's rule (c) wants them without)
-        HIPCHK(hipMemsetAsync(d_p1kcnt, 0, (size_t)DF_KTAB * 2 * 4, ctx->stream));
-        const int wild = p1_other ? BX_WILD : 0;
-        hipLaunchKernelGGL(k_kmer_occ, dim3((unsigned)((len1 + 255) / 256)), dim3(256), 0, ctx->stream, d_cf, (int64_t)len1, d_p1kcnt, d_p1kpos, wild);
-        hipLaunchKernelGGL(k_kmer_occ, dim3((unsigned)((len1 + 255) / 256)), dim3(256), 0, ctx->stream, d_cr, (int64_t)len1, d_p1kcnt + DF_KTAB,
-                           d_p1kpos + DF_KTAB * DF_KCAP, wild);
-      }
-      const int64_t m = n_dp * P1A_SLOTS;
-      const int stride = (max_len + 3) & ~3;
-      // one allocation for all the temporaries of this stage (twenty separate ones cost more than the stage)
-      unsigned char* arena = nullptr;
-      PoolScope g2(ctx);
-      g2.watch((void**)&arena);
-      size_t top = 0;
-      auto carve = [&](size_t bytes) { const size_t at = top; top += (bytes + 255) & ~(size_t)255; return at; };
-      const size_t o_roff = carve((size_t)m * 4), o_status = carve((size_t)m * 4), o_nrest = carve(64), o_len = carve((size_t)m * 2),
-                   o_rc = carve((size_t)m), o_sk = carve((size_t)m), o_ref2 = carve((size_t)2 * len1 + 64), o_as = carve((size_t)m * 4),
-                   o_ae = carve((size_t)m * 4), o_score = carve((size_t)m * 4), o_refstart = carve((size_t)m * 4), o_bin = carve((size_t)m * 4),
-                   o_list = carve(((size_t)m + 4 * N_BINS) * 4), o_wide = carve((size_t)m * 4), o_retry = carve((size_t)m * 4),
-                   o_rest = carve((size_t)n_dp * 4), o_abr = carve((size_t)m * 2), o_cols = carve((size_t)m * stride * 2),
-                   o_bound = carve((size_t)n_dp * 4), o_budget = carve((size_t)n_dp * 4), o_u = carve((size_t)n_dp * 4);
-      if (pool_alloc(ctx, &arena, top)) return MIA_HIP_ERR_NOMEM;
-      uint32_t *w_roff = (uint32_t*)(arena + o_roff), *w_status = (uint32_t*)(arena + o_status), *d_nrest = (uint32_t*)(arena + o_nrest);
-      uint16_t* w_len = (uint16_t*)(arena + o_len);
-      uint8_t *w_rc = arena + o_rc, *w_sk = arena + o_sk, *d_ref2 = arena + o_ref2;
-      int32_t *w_as = (int32_t*)(arena + o_as), *w_ae = (int32_t*)(arena + o_ae), *w_score = (int32_t*)(arena + o_score),
-              *w_refstart = (int32_t*)(arena + o_refstart), *w_bin = (int32_t*)(arena + o_bin), *w_list = (int32_t*)(arena + o_list),
-              *w_wide = (int32_t*)(arena + o_wide), *w_retry = (int32_t*)(arena + o_retry), *d_rest = (int32_t*)(arena + o_rest),
-              *w_bound = (int32_t*)(arena + o_bound), *w_budget = (int32_t*)(arena + o_budget), *w_u = (int32_t*)(arena + o_u);
-      int16_t *w_abr = (int16_t*)(arena + o_abr), *w_cols = (int16_t*)(arena + o_cols);
-      HIPCHK(hipMemsetAsync(w_rc, 0, (size_t)m, ctx->stream));
-      HIPCHK(hipMemsetAsync(w_abr, 0, (size_t)m * 2, ctx->stream));
-      HIPCHK(hipMemsetAsync(w_status, 0, (size_t)m * 4, ctx->stream));
-      HIPCHK(hipMemsetAsync(w_score, 0, (size_t)m * 4, ctx->stream));
-      HIPCHK(hipMemsetAsync(d_nrest, 0, 64, ctx->stream));
-      HIPCHK(hipMemsetAsync(d_ref2, 4, (size_t)2 * len1 + 64, ctx->stream));
-      HIPCHK(hipMemcpyAsync(d_ref2, d_cf, (size_t)len1, hipMemcpyDeviceToDevice, ctx->stream));
-      HIPCHK(hipMemcpyAsync(d_ref2 + len1, d_cr, (size_t)len1, hipMemcpyDeviceToDevice, ctx->stream));
-      KmerOcc kf{d_p1kcnt, d_p1kpos}, kr{d_p1kcnt + DF_KTAB, d_p1kpos + DF_KTAB * DF_KCAP};
-      BxTab p1tab;
-      p1tab.sub = ctx->d_bx_sub; p1tab.mrow = ctx->d_bx_mrow; p1tab.loss = ctx->d_bx_loss; p1tab.dl = ctx->d_bx_dl; p1tab.min_m = ctx->bx_min_m; p1tab.max_m = ctx->bx_max_m; p1tab.maxw = 32;
-      if (ctx->flat)
-        hipLaunchKernelGGL(k_pass1_anchor<false>, dim3((unsigned)((n_dp + 255) / 256)), dim3(256), 0, ctx->stream, pr, d_todo, n_dp, kf, kr, len1, w_roff, w_len,
-                           w_sk, w_as, w_ae, w_bound, w_budget, w_u, p1tab);
-      else
-        hipLaunchKernelGGL(k_pass1_anchor<true>, dim3((unsigned)((n_dp + 255) / 256)), dim3(256), 0, ctx->stream, pr, d_todo, n_dp, kf, kr, len1, w_roff, w_len,
-                           w_sk, w_as, w_ae, w_bound, w_budget, w_u, p1tab);
-      HIPCHK(hipGetLastError());
-      int rc_inner;
-      {
-        AlignBorrow borrow(ctx);
-        ReadSet& r = ctx->rs;
-        r.n = m; r.packed = d_packed; r.roff = w_roff; r.len = w_len; r.rc = w_rc; r.sk = w_sk; r.as = w_as; r.ae = w_ae; r.score = w_score;
-        r.refstart = w_refstart; r.abr = w_abr; r.status = w_status; r.cols = w_cols; r.stride = stride;
-        ctx->d_bin_of.p = w_bin; ctx->d_list.p = w_list; ctx->d_wide_list.p = w_wide; ctx->d_retry_list.p = w_retry; ctx->max_len = max_len;
-        ctx->d_ref.p = d_ref2; ctx->L = 2 * len1; ctx->wrap = 2 * len1; ctx->explicit_win = 1; ctx->use_filter = 0;
-        ctx->ref_mostly_bases = p1_other * 50 <= L; ctx->kh_entries = wild_entries;
-        ctx->wide_to_caller = true;
-        rc_inner = align_all(ctx);
-        ctx->wide_to_caller = false;
-      }
-      if (rc_inner != MIA_HIP_OK) return rc_inner;
-      hipLaunchKernelGGL(k_pass1_select, dim3((unsigned)((n_dp + 255) / 256)), dim3(256), 0, ctx->stream, pr, d_todo, n_dp, len1, L, w_sk, w_score, w_as,
-                         w_ae, w_abr, w_status, w_bound, w_budget, w_u, d_rest, d_nrest);
-      HIPCHK(hipGetLastError());
-      uint32_t h_rest[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      HIPCHK(hipMemcpyAsync(h_rest, d_nrest, 64, hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      const uint32_t h_nrest = h_rest[0];
-      if (timing) fprintf(stderr, "[mia_hip_pass1] left to the whole-strand DP: %u no cluster, %u unfinished windows, %u clipped, %u over budget, %u weak clusters\n",
-                          h_rest[1], h_rest[2], h_rest[3], h_rest[4], h_rest[5]);
-      if (timing) fprintf(stderr, "[mia_hip_pass1] no cluster: %u reads with N, %u too few blocks, %u too many clusters, %u too wide, %u too many strong, %u none strong, %u no room\n",
-                          h_rest[9], h_rest[10], h_rest[11], h_rest[12], h_rest[13], h_rest[14], h_rest[15]);
-      // the survivors' list replaces the filter's (d_todo is at least as long)
-      HIPCHK(hipMemcpyAsync(d_todo, d_rest, (size_t)h_nrest * 4, hipMemcpyDeviceToDevice, ctx->stream));
-      ctx->pass1_anchored = n_dp - h_nrest;
-      if (timing) fprintf(stderr, "[mia_hip_pass1] anchored windows: %lld of %lld left-over reads decided\n", (long long)(n_dp - h_nrest), (long long)n_dp);
-      n_dp = h_nrest;
-    }
-    if (e == hipSuccess && n_dp > 0) {
-      const int64_t g = grid < n_dp ? grid : n_dp;
-      hipLaunchKernelGGL(kfn, dim3((unsigned)g), dim3(64), lds, ctx->stream, pr, d_cf, d_cr, len1, L, ctx->d_pssm, pk, kx, d_trace,
-                         trace_bytes, d_ckpt, ckpt_words, rows_p, mask_words, plain, (filtered || anchored_ok) ? d_todo : nullptr, n_dp);
-      e = hipGetLastError();
-    }
-    if (p1_timed) stage_end(ctx, STG_PASS1);
-  }
-  auto back = [&](void* h, const void* d, size_t b) { if (e == hipSuccess) e = hipMemcpyAsync(h, d, b, hipMemcpyDeviceToHost, ctx->stream); };
-  back(score, d_score, (size_t)n * 4); back(as, d_as, (size_t)n * 4); back(ae, d_ae, (size_t)n * 4);
-  back(rc, d_rc, (size_t)n); back(flags, d_flags, (size_t)n);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  lap("h2d+kernel+d2h");
-  if (p1_timed && !ctx->stg[STG_PASS1].pending.empty()) {
-    // the whole call's device time (filter, anchored windows and DP), measured on the pair taken above
-    const auto pr = ctx->stg[STG_PASS1].pending.back();
-    float ms = 0;
-    if (e == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) ctx->pass1_ms = ms;
-  }
-  lap("done");
-  if (e != hipSuccess) { ctx->err = std::string("pass1: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
-  return MIA_HIP_OK;
+  Pass1Call p{ctx, ref, ref_len, circular, kmer_len, soft_mask, n, bases, offsets, score, rc, as, ae, flags};
+  p.timing = alt_env("MIA_HIP_P1_TIMING") != nullptr;
+  p.t_start = std::chrono::steady_clock::now();
+  if (!make_pack_params(1024, ctx->max_abs, &p.pk)) { ctx->err = "PSSM too large for the packed pass-1 kernel"; return MIA_HIP_ERR_RANGE; }
+  int code = MIA_HIP_OK;      // the first stage that fails ends the call: its code, its message in ctx->err
+  pass1_host_reference(p);
+  if ((code = pass1_index_reads(p)) || (code = pass1_decide(p)) || (code = pass1_kmer_tables(p))) return code;
+  p.lap("ref+kmer");
+  if ((code = pass1_allocate(p))) return code;
+  p.lap("pack+alloc");
+  if ((code = pass1_upload(p))) return code;
+  if (p.r.filtered && (code = pass1_filter_stage(p))) return code;
+  if (p.r.anchored_ok && p.n_dp > 0 && (code = pass1_anchor_stage(p))) return code;
+  if (p.n_dp > 0 && (code = pass1_dp_stage(p))) return code;
+  return pass1_download(p);
 }
 
 // ---- Myers ------------------------------------------------------------------------------
@@ -1023,26 +1070,22 @@ static int myers_run(mia_hip_ctx* ctx, int64_t n, const char* const* seq_a, cons
         }
       });
   }
-  char* d_blob = nullptr;
-  MyersPair* d_pairs = nullptr;
-  MyersLanePair* d_lp = nullptr;
-  uint32_t *d_out = nullptr, *d_out_long = nullptr, *d_codes = nullptr;
-  int32_t *d_index = nullptr, *d_table = nullptr, *d_endk = nullptr;
-  PoolScope guard(ctx);
-  guard.watch((void**)&d_table); guard.watch((void**)&d_endk);
-  guard.watch((void**)&d_blob); guard.watch((void**)&d_pairs); guard.watch((void**)&d_out); guard.watch((void**)&d_lp); guard.watch((void**)&d_codes);
-  guard.watch((void**)&d_index); guard.watch((void**)&d_out_long);
+  PoolLease<char> d_blob;
+  PoolLease<MyersPair> d_pairs;
+  PoolLease<MyersLanePair> d_lp;
+  PoolLease<uint32_t> d_out, d_out_long, d_codes;
+  PoolLease<int32_t> d_index, d_table, d_endk;
   const size_t nl = lp.size(), ng = pairs.size();
-  if (pool_alloc(ctx, &d_out, (size_t)n)) return MIA_HIP_ERR_NOMEM;
+  if (pool_take(ctx, d_out, (size_t)n)) return MIA_HIP_ERR_NOMEM;
   hipError_t e = hipSuccess;
   // (every allocation first: an early return leaves no copy in flight from the host vectors and no event behind)
-  if (nl && (pool_alloc(ctx, &d_lp, nl) || pool_alloc(ctx, &d_index, nl))) return MIA_HIP_ERR_NOMEM;
-  if ((nl || n_ond) && pool_alloc(ctx, &d_codes, codes.size() + 8)) return MIA_HIP_ERR_NOMEM;
-  if (ng && (pool_alloc(ctx, &d_blob, blob.size() + 1) || pool_alloc(ctx, &d_pairs, ng) || pool_alloc(ctx, &d_out_long, ng))) return MIA_HIP_ERR_NOMEM;
+  if (nl && (pool_take(ctx, d_lp, nl) || pool_take(ctx, d_index, nl))) return MIA_HIP_ERR_NOMEM;
+  if ((nl || n_ond) && pool_take(ctx, d_codes, codes.size() + 8)) return MIA_HIP_ERR_NOMEM;
+  if (ng && (pool_take(ctx, d_blob, blob.size() + 1) || pool_take(ctx, d_pairs, ng) || pool_take(ctx, d_out_long, ng))) return MIA_HIP_ERR_NOMEM;
   const bool want_walk = walk && ng == 1 && nl == 0 && n_ond == 1;
   if (want_walk) {
     const size_t cells = ((size_t)pairs[0].cap + 1) * ((size_t)pairs[0].cap + 1);
-    if (pool_alloc(ctx, &d_table, cells) || pool_alloc(ctx, &d_endk, (size_t)1)) return MIA_HIP_ERR_NOMEM;
+    if (pool_take(ctx, d_table, cells) || pool_take(ctx, d_endk, (size_t)1)) return MIA_HIP_ERR_NOMEM;
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -1129,11 +1172,9 @@ extern "C" int mia_hip_myers_packed(mia_hip_ctx* ctx, int64_t n, const uint32_t*
     MyersLanePair& q = lp[(size_t)i];
     q.a_off = a_off[i]; q.b_off = b_off[i]; q.la = la[i]; q.lb = lb[i]; q.mode = mode[i]; q.maxd = maxd[i];
   }
-  MyersLanePair* d_lp = nullptr;
-  uint32_t *d_out = nullptr, *d_codes = nullptr;
-  PoolScope guard(ctx);
-  guard.watch((void**)&d_lp); guard.watch((void**)&d_out); guard.watch((void**)&d_codes);
-  if (pool_alloc(ctx, &d_out, (size_t)n) || pool_alloc(ctx, &d_lp, (size_t)n) || pool_alloc(ctx, &d_codes, (size_t)n_words + 8)) return MIA_HIP_ERR_NOMEM;
+  PoolLease<MyersLanePair> d_lp;
+  PoolLease<uint32_t> d_out, d_codes;
+  if (pool_take(ctx, d_out, (size_t)n) || pool_take(ctx, d_lp, (size_t)n) || pool_take(ctx, d_codes, (size_t)n_words + 8)) return MIA_HIP_ERR_NOMEM;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   hipError_t e = hipMemcpyAsync(d_lp, lp.data(), (size_t)n * sizeof(MyersLanePair), hipMemcpyHostToDevice, ctx->stream);
