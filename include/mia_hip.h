@@ -410,6 +410,27 @@ int mia_hip_ma_cols(mia_hip_ctx *ctx, const uint8_t *segment, const uint8_t *use
  * the last mia_hip_ma_tally. */
 int mia_hip_get_ma_cols(mia_hip_ctx *ctx, int32_t *cols);
 
+/* The duplicate filter (ma_hip -u, -t; the rule is DESIGN.md's "Duplicate filter": the reference's sort_fsdb + set_uniq_in_fsdb
+ * with just_outer_coords and a tolerance).  Independent of mia_hip_ma_tally.  Per record r: start[r], end[r] (its last column; start - 1
+ * for a record without columns), revcom[r], score[r] and mate[r]: -1 = a molecule of its own, -2 = a half of a read split at the origin
+ * whose other half is not there (an orphan: always kept, never clustered), otherwise the record number of its other half.  mate = NULL:
+ * no halves.  Of two halves the front is the one with the greater START (the lower record number if they are equal); the molecule is
+ * (revcom, a = start of the front, e = end of the back + ref_len) with the front's score, and its index is the lower record number.
+ * Molecules with equal (revcom, a, e) are a run, whose best molecule has the highest score, then the lowest index.  Runs are walked
+ * reverse strand first, then a ascending and e descending (reverse strand: e descending, a ascending); a run within `tolerance` of the
+ * latest anchor run in a and in e, on its strand, is a duplicate, any other run is the next anchor.  A cluster is an anchor run and
+ * the duplicate runs behind it; its representative is the best molecule of the ANCHOR run.
+ * n_molecules, n_clusters: the totals (either may be NULL).  n_records = 0 is valid: nothing is launched, every result is zero.
+ * MIA_HIP_ERR_ARG: tolerance outside 0 .. 100, ref_len < 1, start < 0, end < start - 1, end >= 2 * ref_len, a mate that is out of range,
+ * r itself or not mutual, a back half that ends at or behind column ref_len.  The context stays usable. */
+int mia_hip_ma_dedup(mia_hip_ctx *ctx, int32_t ref_len, int64_t n_records, const int32_t *start, const int32_t *end, const uint8_t *revcom,
+                     const int32_t *score, const int64_t *mate, int32_t tolerance, int64_t *n_molecules, int64_t *n_clusters);
+/* Of the last mia_hip_ma_dedup: keep[n] (1 = the record belongs to a representative or is an orphan), rep[n] (the index of the record's
+ * cluster's representative; an orphan's own number), size_hist[2 * 1025] ([strand: 0 forward, 1 reverse][molecules in the cluster]:
+ * bins 1 .. 1023, bin 1024 = more, bin 0 unused) and *orphans.  Any pointer may be NULL.  MIA_HIP_ERR_STATE without a successful
+ * mia_hip_ma_dedup before. */
+int mia_hip_get_ma_dedup(mia_hip_ctx *ctx, uint8_t *keep, int64_t *rep, int64_t *size_hist, int64_t *orphans);
+
 /* ---- Myers edit distance -------------------------------------------------- */
 
 /* unsigned myers_diff(const char *seq_a, enum myers_align_mode mode, const char* seq_b, int maxd,
@@ -488,7 +509,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_profile, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_profile, k_ma_dedup_keys, k_ma_dedup_sort, k_ma_dedup_runs, k_ma_dedup_next, k_ma_dedup_anchors, k_ma_dedup_clusters, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

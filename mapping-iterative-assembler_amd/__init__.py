@@ -111,6 +111,9 @@ def _load(path=None):
     if hasattr(lib, "mia_hip_ma_cols"):
         lib.mia_hip_ma_cols.argtypes = [vp, vp, vp, P(C.c_int64), P(C.c_int64), P(C.c_int64), P(C.c_int64)]
         lib.mia_hip_get_ma_cols.argtypes = [vp, vp]
+    if hasattr(lib, "mia_hip_ma_dedup"):
+        lib.mia_hip_ma_dedup.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, C.c_int32, P(C.c_int64), P(C.c_int64)]
+        lib.mia_hip_get_ma_dedup.argtypes = [vp, vp, vp, vp, P(C.c_int64)]
     lib.mia_hip_kernel_time.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_int64)]
     lib.mia_hip_stage_stats.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp, P(C.c_int32)]
     lib.mia_hip_set_stage_mask.argtypes = [vp, C.c_uint32]
@@ -155,7 +158,7 @@ def exported_symbols():
             "mia_hip_upload_reads", "mia_hip_pass1", "mia_hip_realign", "mia_hip_align_windows", "mia_hip_get_alignments", "mia_hip_get_scripts", "mia_hip_cull",
             "mia_hip_get_dropped", "mia_hip_set_slot_dropped", "mia_hip_score_cut", "mia_hip_num_records",
             "mia_hip_tally", "mia_hip_tally_buffers", "mia_hip_ins_events", "mia_hip_set_ins_events",
-            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
+            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
             "mia_hip_get_record_params", "mia_hip_set_read_base", "mia_hip_links", "mia_hip_set_links", "mia_hip_link_lengths",
             "mia_hip_finish_links", "mia_hip_plain_stats", "mia_hip_score_sums",
             "mia_hip_score_cut_from_sums", "mia_hip_stage_stats", "mia_hip_measure_peaks", "mia_hip_measure_issue", "mia_hip_set_tally", "mia_hip_iterate", "mia_hip_set_stage_mask", "mia_hip_comm_unique_id", "mia_hip_comm_init", "mia_hip_comm_destroy",
@@ -564,7 +567,7 @@ class MiaHip:
         self._chk(self._l.mia_hip_stage_stats(self._h, 1 if reset else 0, cap, names, ms, k, C.byref(n)))
         return {names[i].decode(): (ms[i], k[i]) for i in range(min(n.value, cap))}
 
-    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_profile", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
+    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs", "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
 
     def comm_init(self, unique_id, n_ranks, rank):
         """attach an RCCL communicator (ncclCommInitRank on this context's GPU); unique_id: the 128 bytes of comm_unique_id()
@@ -718,6 +721,33 @@ class MiaHip:
                                           C.byref(beyond), C.byref(outside)))
         self._chk(self._l.mia_hip_get_ma_cols(self._h, _ptr(cols)))
         return cols, n_used.value, n_events.value, beyond.value, outside.value
+
+    def ma_dedup(self, ref_len, start, end, revcom, score, mate=None, tolerance=0):
+        """the duplicate filter (ma_hip -u, -t) over records given by START, END, strand and SCORE; it needs no ma_tally.
+        mate: per record -1 (a molecule of its own), -2 (a half without its other half: kept, never clustered) or the record number
+        of its other half (None: no halves); tolerance 0 .. 100.  (keep[n] uint8, rep[n] int64, hist[2, 1025] int64, n_molecules,
+        n_clusters, orphans): keep = the record belongs to its cluster's representative or is an orphan; rep = the representative's
+        index; hist[strand, size] = clusters of that many molecules (0 forward, 1 reverse; 1024: more than 1023)."""
+        if not hasattr(self._l, "mia_hip_ma_dedup"):
+            raise RuntimeError("this libmia_hip has no mia_hip_ma_dedup")
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        end = np.ascontiguousarray(end, dtype=np.int32)
+        revcom = np.ascontiguousarray(revcom, dtype=np.uint8)
+        score = np.ascontiguousarray(score, dtype=np.int32)
+        n = len(start)
+        if not (len(end) == len(revcom) == len(score) == n):
+            raise ValueError("ma_dedup: the arrays differ in length")
+        if mate is not None:
+            mate = np.ascontiguousarray(mate, dtype=np.int64)
+            if len(mate) != n:
+                raise ValueError("ma_dedup: the arrays differ in length")
+        keep, rep, hist = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int64), np.zeros((2, 1025), dtype=np.int64)
+        n_mol, n_clu, orphans = C.c_int64(), C.c_int64(), C.c_int64()
+        opt = lambda a: _ptr(a) if n else None
+        self._chk(self._l.mia_hip_ma_dedup(self._h, int(ref_len), n, opt(start), opt(end), opt(revcom), opt(score),
+                                           _ptr(mate) if mate is not None and n else None, int(tolerance), C.byref(n_mol), C.byref(n_clu)))
+        self._chk(self._l.mia_hip_get_ma_dedup(self._h, opt(keep), opt(rep), _ptr(hist), C.byref(orphans)))
+        return keep, rep, hist, n_mol.value, n_clu.value, orphans.value
 
     def ins_tally(self):
         """(ins_off[L+1], ins_tally[slots][9]) of the insert columns, after consensus()."""

@@ -36,15 +36,17 @@
 #include "mia_ma_profile_kernels.h"
 #include "mia_ma_ends_kernels.h"
 #include "mia_ma_cols_kernels.h"
+#include "mia_ma_dedup_kernels.h"
 
 using namespace mia;
 
 // timed stages (HIP events on the context's stream around the kernel launches of that kind)
-enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_PROFILE, STG_MA_TALLY, STG_MA_COLS, STG_MA_ENDS, STG_COUNT };
+enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_PROFILE, STG_MA_DEDUP_KEYS, STG_MA_DEDUP_SORT, STG_MA_DEDUP_RUNS, STG_MA_DEDUP_NEXT, STG_MA_DEDUP_ANCHORS, STG_MA_DEDUP_CLUSTERS, STG_MA_TALLY, STG_MA_COLS, STG_MA_ENDS, STG_COUNT };
 static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan",
                                                    "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select",
                                                    "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout",
-                                                   "k_ma_sam_render", "k_ma_profile", "k_ma_tally", "k_ma_cols", "k_ma_ends"};
+                                                   "k_ma_sam_render", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs",
+                                                   "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"};
 
 // One device block for every small counter of an iteration (planner bins and header, filter / band-pipeline counters, link
 // count, cull and tally flags, insert-event count): one memset at the start of the alignment clears them all, and one copy
@@ -290,6 +292,16 @@ struct mia_hip_ctx {
   // column (ma_cols_body.h) and the two counts of what lies on no column, on the device and, after the call, here
   DevBuf<uint32_t> d_cols_tab; DevBuf<unsigned long long> d_cols_out;
   std::vector<int32_t> ma_cols_tab;
+  // ... and mia_hip_ma_dedup, which needs no tally in front of it: the records' coordinates, strands, scores and mates, the two sides
+  // of the radix sort and its counts, runs, jumps, marks, clusters (mia_ma_dedup_kernels.h); keep and rep stay on the device until
+  // mia_hip_get_ma_dedup, the histogram and the totals are here
+  struct MaDedup {
+    bool done = false; int64_t n = 0, molecules = 0, clusters = 0, orphans = 0;
+    DevBuf<int32_t> d_start, d_end, d_score; DevBuf<uint8_t> d_rc, d_keep; DevBuf<int64_t> d_mate, d_rep;
+    DevBuf<unsigned long long> d_key[2], d_runkey, d_best, d_ctl, d_hist;
+    DevBuf<uint32_t> d_val[2], d_jump[2], d_counts, d_runid, d_first, d_mark, d_cluster, d_anchor;
+    int64_t hist[MA_DEDUP_HIST] = {0};
+  } dedup;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------

@@ -495,6 +495,132 @@ extern "C" int mia_hip_get_ma_cols(mia_hip_ctx* ctx, int32_t* cols) {
   return MIA_HIP_OK;
 }
 
+// The duplicate filter (ma_hip -u, -t): see mia_ma_dedup_kernels.h.  Independent of mia_hip_ma_tally: it takes the records'
+// coordinates, strands, scores and the pairing of the halves, and leaves keep, rep and the size histogram in buffers of its own.
+extern "C" int mia_hip_ma_dedup(mia_hip_ctx* ctx, int32_t ref_len, int64_t n_records, const int32_t* start, const int32_t* end, const uint8_t* revcom,
+                                const int32_t* score, const int64_t* mate, int32_t tolerance, int64_t* n_molecules, int64_t* n_clusters) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  auto& dd = ctx->dedup;
+  dd.done = false;
+  if (tolerance < 0 || tolerance > MA_DEDUP_MAX_TOL) { ctx->err = "ma_dedup: the tolerance must lie in 0 .. 100"; return MIA_HIP_ERR_ARG; }
+  if (ref_len < 1 || ref_len > MA_DEDUP_MAX_L) { ctx->err = "ma_dedup: reference length out of range"; return MIA_HIP_ERR_ARG; }
+  if (n_records < 0 || n_records >= ((int64_t)1 << 31)) { ctx->err = "ma_dedup: record count out of range"; return MIA_HIP_ERR_ARG; }
+  const int64_t n = n_records;
+  const int32_t L = ref_len;
+  if (n > 0 && (!start || !end || !revcom || !score)) { ctx->err = "ma_dedup: null array"; return MIA_HIP_ERR_ARG; }
+  int64_t M = 0, orphans = 0;
+  for (int64_t r = 0; r < n; r++) {
+    if (start[r] < 0 || (int64_t)end[r] < (int64_t)start[r] - 1 || (int64_t)end[r] >= 2ll * L) { ctx->err = "ma_dedup: a record's START or END is out of range"; return MIA_HIP_ERR_ARG; }
+    const int64_t m = mate ? mate[r] : MA_DEDUP_NONE;
+    if (m == MA_DEDUP_ORPHAN) { orphans++; continue; }
+    if (m == MA_DEDUP_NONE) { M++; continue; }
+    if (m < 0 || m >= n || m == r || mate[m] != r) { ctx->err = "ma_dedup: mate is out of range, the record itself or not mutual"; return MIA_HIP_ERR_ARG; }
+    if (ma_dedup_front(start, r, m)) { M++; continue; }
+    if (end[r] >= L) { ctx->err = "ma_dedup: the back half of a pair ends behind the reference"; return MIA_HIP_ERR_ARG; }
+  }
+  dd.n = n; dd.molecules = M; dd.orphans = orphans; dd.clusters = 0;
+  memset(dd.hist, 0, sizeof dd.hist);
+  if (n > 0) {
+    HIPCHK(hipSetDevice(ctx->device));
+    const int W = ma_dedup_width(L), passes = ma_dedup_passes(L);
+    const int64_t sort_wgs = ma_dedup_sort_wgs(n), scan_wgs = ma_dedup_wgs(n);
+    int rc = dev_ensure(ctx, dd.d_start, n) | dev_ensure(ctx, dd.d_end, n) | dev_ensure(ctx, dd.d_score, n) | dev_ensure(ctx, dd.d_rc, n);
+    rc |= dev_ensure(ctx, dd.d_keep, n) | dev_ensure(ctx, dd.d_rep, n) | dev_ensure(ctx, dd.d_hist, MA_DEDUP_HIST);
+    if (mate) rc |= dev_ensure(ctx, dd.d_mate, n);
+    for (int b = 0; b < 2; b++) rc |= dev_ensure(ctx, dd.d_key[b], n) | dev_ensure(ctx, dd.d_val[b], n) | dev_ensure(ctx, dd.d_jump[b], n + 1);
+    rc |= dev_ensure(ctx, dd.d_counts, MAD_RADIX * sort_wgs) | dev_ensure(ctx, dd.d_ctl, MAR_STATE + scan_wgs);
+    rc |= dev_ensure(ctx, dd.d_runid, n) | dev_ensure(ctx, dd.d_first, n + 1) | dev_ensure(ctx, dd.d_runkey, n) | dev_ensure(ctx, dd.d_best, n);
+    rc |= dev_ensure(ctx, dd.d_mark, n) | dev_ensure(ctx, dd.d_cluster, n) | dev_ensure(ctx, dd.d_anchor, n + 1);
+    if (rc) return MIA_HIP_ERR_NOMEM;
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(dd.d_start, start, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dd.d_end, end, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dd.d_score, score, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dd.d_rc, revcom, (size_t)n, hipMemcpyHostToDevice, s));
+    if (mate) HIPCHK(hipMemcpyAsync(dd.d_mate, mate, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dd.d_hist, 0, (size_t)MA_DEDUP_HIST * 8, s));
+    const int64_t* d_mate = mate ? (const int64_t*)dd.d_mate : nullptr;
+    const int64_t wide = (int64_t)ctx->cus * MAD_WGS_PER_CU;
+    auto grid_for = [&](int64_t items) { const int64_t g = ma_dedup_wgs(items); return dim3((unsigned)(g < 1 ? 1 : (g < wide ? g : wide))); };
+    if (stage_launch(ctx, STG_MA_DEDUP_KEYS, k_ma_dedup_keys, grid_for(n), dim3(MAD_THREADS), 0, s, n, L, W, (const int32_t*)dd.d_start, (const int32_t*)dd.d_end,
+                     (const uint8_t*)dd.d_rc, d_mate, (unsigned long long*)dd.d_key[0], (uint32_t*)dd.d_val[0], (uint8_t*)dd.d_keep, (int64_t*)dd.d_rep))
+      return MIA_HIP_ERR_NOMEM;
+    int cur = 0;
+    for (int p = 0; p < passes; p++, cur ^= 1) {
+      if (stage_launch(ctx, STG_MA_DEDUP_SORT, k_ma_dedup_sort_count, dim3((unsigned)sort_wgs), dim3(MAD_THREADS), 0, s, (const unsigned long long*)dd.d_key[cur], n,
+                       8 * p, (uint32_t*)dd.d_counts, sort_wgs) ||
+          stage_launch(ctx, STG_MA_DEDUP_SORT, k_ma_dedup_sort_scan, dim3(1), dim3(MAD_THREADS), 0, s, (uint32_t*)dd.d_counts, (int64_t)MAD_RADIX * sort_wgs) ||
+          stage_launch(ctx, STG_MA_DEDUP_SORT, k_ma_dedup_sort_scatter, dim3((unsigned)sort_wgs), dim3(MAD_THREADS), 0, s, (const unsigned long long*)dd.d_key[cur],
+                       (const uint32_t*)dd.d_val[cur], (unsigned long long*)dd.d_key[cur ^ 1], (uint32_t*)dd.d_val[cur ^ 1], n, 8 * p,
+                       (const uint32_t*)dd.d_counts, sort_wgs))
+        return MIA_HIP_ERR_NOMEM;
+    }
+    HIPCHK(hipGetLastError());
+    const unsigned long long* sk = dd.d_key[cur];
+    const uint32_t* sm = dd.d_val[cur];
+    if (M > 0) {
+      const int64_t run_wgs = ma_dedup_wgs(M);
+      HIPCHK(hipMemsetAsync(dd.d_ctl, 0, (size_t)(MAR_STATE + run_wgs) * 8, s));
+      HIPCHK(hipMemsetAsync(dd.d_best, 0, (size_t)M * 8, s));
+      if (stage_launch(ctx, STG_MA_DEDUP_RUNS, k_ma_dedup_runs, dim3((unsigned)run_wgs), dim3(MAD_THREADS), 0, s, sk, sm, M, (const int32_t*)dd.d_score, d_mate,
+                       (unsigned long long*)dd.d_ctl, (int32_t)run_wgs, (uint32_t*)dd.d_runid, (uint32_t*)dd.d_first, (unsigned long long*)dd.d_runkey,
+                       (unsigned long long*)dd.d_best))
+        return MIA_HIP_ERR_NOMEM;
+      unsigned long long runs = 0;
+      HIPCHK(hipMemcpyAsync(&runs, dd.d_ctl + MAR_ROWS, 8, hipMemcpyDeviceToHost, s));     // the one read-back: the round count hangs on it
+      HIPCHK(hipStreamSynchronize(s));
+      const int64_t R = (int64_t)runs;
+      if (R < 1 || R > M) { ctx->err = "ma_dedup: the run count came back inconsistent"; return MIA_HIP_ERR_DEVICE; }
+      if (stage_launch(ctx, STG_MA_DEDUP_NEXT, k_ma_dedup_next, grid_for(R + 1), dim3(MAD_THREADS), 0, s, (const unsigned long long*)dd.d_runkey, R, W, tolerance,
+                       (uint32_t*)dd.d_jump[0], (uint32_t*)dd.d_mark))
+        return MIA_HIP_ERR_NOMEM;
+      int jc = 0;
+      for (int round = 0; round < ma_dedup_rounds(R); round++, jc ^= 1)
+        if (stage_launch(ctx, STG_MA_DEDUP_ANCHORS, k_ma_dedup_double, grid_for(R + 1), dim3(MAD_THREADS), 0, s, (const uint32_t*)dd.d_jump[jc],
+                         (uint32_t*)dd.d_jump[jc ^ 1], (uint32_t*)dd.d_mark, R))
+          return MIA_HIP_ERR_NOMEM;
+      const int64_t cl_wgs = ma_dedup_wgs(R);
+      HIPCHK(hipMemsetAsync(dd.d_ctl, 0, (size_t)(MAR_STATE + cl_wgs) * 8, s));
+      if (stage_launch(ctx, STG_MA_DEDUP_CLUSTERS, k_ma_dedup_cluster_scan, dim3((unsigned)cl_wgs), dim3(MAD_THREADS), 0, s, (const uint32_t*)dd.d_mark, R,
+                       (unsigned long long*)dd.d_ctl, (int32_t)cl_wgs, (uint32_t*)dd.d_cluster, (uint32_t*)dd.d_anchor) ||
+          stage_launch(ctx, STG_MA_DEDUP_CLUSTERS, k_ma_dedup_hist, grid_for(R), dim3(MAD_THREADS), 0, s, (const uint32_t*)dd.d_anchor,
+                       (const unsigned long long*)dd.d_ctl, (const uint32_t*)dd.d_first, (const unsigned long long*)dd.d_runkey, W, (unsigned long long*)dd.d_hist) ||
+          stage_launch(ctx, STG_MA_DEDUP_CLUSTERS, k_ma_dedup_scatter, grid_for(M), dim3(MAD_THREADS), 0, s, sm, M, (const uint32_t*)dd.d_runid,
+                       (const uint32_t*)dd.d_cluster, (const uint32_t*)dd.d_anchor, (const unsigned long long*)dd.d_best, d_mate, (uint8_t*)dd.d_keep,
+                       (int64_t*)dd.d_rep))
+        return MIA_HIP_ERR_NOMEM;
+      HIPCHK(hipGetLastError());
+      unsigned long long clusters = 0;
+      HIPCHK(hipMemcpyAsync(&clusters, dd.d_ctl + MAR_ROWS, 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(dd.hist, dd.d_hist, sizeof dd.hist, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      dd.clusters = (int64_t)clusters;
+    } else {
+      HIPCHK(hipStreamSynchronize(s));
+    }
+    drain_events(ctx);                      // (some forty launches a call: their event pairs go back to the free list now)
+  }
+  dd.done = true;
+  if (n_molecules) *n_molecules = dd.molecules;
+  if (n_clusters) *n_clusters = dd.clusters;
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_dedup(mia_hip_ctx* ctx, uint8_t* keep, int64_t* rep, int64_t* size_hist, int64_t* orphans) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  auto& dd = ctx->dedup;
+  if (!dd.done) { ctx->err = "ma_dedup first"; return MIA_HIP_ERR_STATE; }
+  if (dd.n > 0 && (keep || rep)) {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (keep) HIPCHK(hipMemcpyAsync(keep, dd.d_keep, (size_t)dd.n, hipMemcpyDeviceToHost, ctx->stream));
+    if (rep) HIPCHK(hipMemcpyAsync(rep, dd.d_rep, (size_t)dd.n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  if (size_hist) memcpy(size_hist, dd.hist, sizeof dd.hist);
+  if (orphans) *orphans = dd.orphans;
+  return MIA_HIP_OK;
+}
+
 extern "C" int mia_hip_get_ins_tally(mia_hip_ctx* ctx, int32_t* ins_off, int32_t* ins_tally, int64_t cap_slots, int64_t* n_slots) {
   if (!ctx) return MIA_HIP_ERR_ARG;
   if (!ctx->tallied || !ctx->consensus_done) { ctx->err = "consensus first"; return MIA_HIP_ERR_STATE; }

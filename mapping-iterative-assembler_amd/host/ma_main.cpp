@@ -12,6 +12,9 @@
 // printing follow src/map_alignment.c:107-220, src/map_align.c:152-227,294-391,543-759 and src/io.c:756-913,929-1085.  Format 3
 // (the summary of format 2 plus a table per column: coverage, and the records that start and that end there on either strand,
 // src/map_align.c:761-849, src/map_alignment.c:635-653) stays outside; its four strand columns are part of -f 42.
+// -u removes duplicate molecules in front of all of it (the reference has the rule in mia -u, not in ma): the
+// halves of reads split at the origin are paired here (host/maln_dedup.h), the clusters are formed on the GPU (mia_hip_ma_dedup), the
+// records that are not kept leave with their inserts and GAPS is reset as cull_maln_from_fsdb does (src/mia.c:484-504).
 // No CPU fallback.
 #include <ctype.h>
 #include <float.h>
@@ -29,11 +32,13 @@
 
 #include "../../include/mia_hip.h"
 #include "maln_text.h"
+#include "maln_dedup.h"
 #include "../csrc/ma_ace_body.h"
 #include "../csrc/ma_sam_body.h"
 #include "../csrc/ma_profile_body.h"
 #include "../csrc/ma_ends_body.h"
 #include "../csrc/ma_cols_body.h"
+#include "../csrc/ma_dedup_body.h"
 
 namespace {
 
@@ -45,6 +50,7 @@ void help() {
   printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92 or 93>\n   -R <REGION_START:REGION_END>\n"
          "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
          "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 42, 9, 91, 92 and 93)\n"
+         "   -u remove duplicate molecules first\n   -t <tolerance of -u in columns, 0 .. 100, default 0>\n"
          "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
          "(-f 1 clustalw, the default; -f 2 one line each plus coverage), the per-column table (-f 41 all positions, -f 4\n"
          "positions that differ from the reference), the assembled sequence (-f 5), and the reference, the consensus and every\n"
@@ -63,7 +69,11 @@ void help() {
          "-f 42 prints the strand table: a line per reference column (-R: of that region only) with the A, C, G, T, gap and other\n"
          "columns of the forward (+) and of the reverse (-) records there, and the records that start and that end on it per strand\n"
          "(damage shows as C>T on + and G>A on -; a variant shows on both; many starts on one column of one strand are duplicates).\n"
-         "Dropped records do not count unless -A is given; the counts come from the MI355X.  Format 3 (format 2's summary plus\n"
+         "Dropped records do not count unless -A is given; the counts come from the MI355X.\n"
+         "-u removes duplicates before anything else is computed, by the rule of mia -u: molecules (a read split at the origin is one)\n"
+         "with the same strand, start and end are one cluster -- with -t N, also those within N columns of the cluster's first in\n"
+         "start and in end -- and only the best-scoring molecule of the cluster's first coordinates stays; GAPS shrinks to the inserts\n"
+         "of what is left, and every format and -m see the smaller file.  Clusters are formed on the MI355X.  Format 3 (format 2's summary plus\n"
          "a table of coverage and of the records that start and end at every column) is outside the accelerated path.\n");
 }
 
@@ -331,11 +341,12 @@ int main(int argc, char* argv[]) {
   std::string ma_in_fn, assign_id, ma_out_fn;
   bool id_assigned = false, in_ma = false, any_arg = false, out_ma = false;
   int cons_scheme = 1, out_format = 1, gpu = 0, reg_start = 90, reg_end = 109;
-  bool in_color = false, use_dropped = false, region_given = false;
+  bool in_color = false, use_dropped = false, region_given = false, dedup = false, tol_given = false;
+  long tolerance = 0;
   double score_int = -1.0, score_slo = -1.0, alpha = 1.0;
   int ich;
-  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount> and -A
-  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:A")) != -1) {
+  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount>, -A, -u and -t <tolerance>
+  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:Aut:")) != -1) {
     switch (ich) {
       case 'I': assign_id = optarg; id_assigned = true; break;
       case 'c': cons_scheme = atoi(optarg); any_arg = true; break;
@@ -351,6 +362,8 @@ int main(int argc, char* argv[]) {
       case 'g': gpu = atoi(optarg); break;
       case 'P': { char* end = nullptr; alpha = strtod(optarg, &end); if (end == optarg || *end) alpha = NAN; } break;
       case 'A': use_dropped = true; break;
+      case 'u': dedup = true; any_arg = true; break;
+      case 't': { char* end = nullptr; tolerance = strtol(optarg, &end, 10); if (end == optarg || *end) tolerance = -1; tol_given = true; } break;
       default: help(); exit(0);
     }
   }
@@ -363,9 +376,32 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "ma_hip: -P must be a number from %g to %g\n", mia::MA_PROF_MIN_ALPHA, mia::MA_PROF_MAX_ALPHA);
     exit(1);
   }
+  if (tol_given && !dedup) { fprintf(stderr, "ma_hip: -t is the tolerance of -u, which is not given\n"); exit(1); }
+  if (tolerance < 0 || tolerance > mia::MA_DEDUP_MAX_TOL) { fprintf(stderr, "ma_hip: -t must be a whole number from 0 to %d\n", mia::MA_DEDUP_MAX_TOL); exit(1); }
   Maln m;
   read_ma(ma_in_fn.c_str(), &m);
   if (id_assigned) m.ref_id = assign_id.substr(0, 256);
+  mia_hip_ctx* g = nullptr;
+  auto open_gpu = [&]() {
+    if (!g && mia_hip_create(&g, gpu) != MIA_HIP_OK) { fprintf(stderr, "ma_hip: no usable MI355X (gfx950) device %d; there is no CPU fallback\n", gpu); exit(1); }
+  };
+  if (dedup) {
+    // the duplicate filter, in front of everything: clusters over all records (dropped or not) on the device, then -u takes out what
+    // is not kept and every check and report below sees the smaller file
+    DedupInput in;
+    std::string why;
+    if (!dedup_input(m, &in, &why)) { fprintf(stderr, "ma_hip: %s has no duplicate filter: %s\n", ma_in_fn.c_str(), why.c_str()); exit(1); }
+    open_gpu();
+    const int64_t n_all = (int64_t)m.rec.size();
+    int64_t n_molecules = 0, n_clusters = 0;
+    std::vector<uint8_t> keep_file((size_t)n_all + 1, 1), keep((size_t)n_all);
+    if (mia_hip_ma_dedup(g, m.L, n_all, in.start.data(), in.end.data(), in.revcom.data(), in.score.data(), in.mate.data(), (int32_t)tolerance, &n_molecules,
+                         &n_clusters) != MIA_HIP_OK)
+      die(g, "ma_dedup");
+    if (mia_hip_get_ma_dedup(g, keep_file.data(), nullptr, nullptr, nullptr) != MIA_HIP_OK) die(g, "get_ma_dedup");
+    for (int64_t f = 0; f < n_all; f++) keep[in.at[(size_t)f]] = keep_file[(size_t)f];
+    remove_records(&m, keep);
+  }
   if (out_format == 8 && !mia::ma_sam_gaps_ok(m.gaps.data(), m.L)) {
     fprintf(stderr, "ma_hip: %s has no SAM export: its GAPS line holds a negative value\n", ma_in_fn.c_str());
     exit(1);
@@ -381,8 +417,7 @@ int main(int argc, char* argv[]) {
     return 0;
   };
 
-  mia_hip_ctx* g = nullptr;
-  if (mia_hip_create(&g, gpu) != MIA_HIP_OK) { fprintf(stderr, "ma_hip: no usable MI355X (gfx950) device %d; there is no CPU fallback\n", gpu); exit(1); }
+  open_gpu();
   if (mia_hip_set_pssm(g, &m.fpsm[0][0][0], &m.rpsm[0][0][0]) != MIA_HIP_OK) die(g, "set_pssm");
   const int64_t n = (int64_t)m.start.size(), n_ins = (int64_t)m.ins_record.size();
   if (mia_hip_ma_tally(g, m.L, m.gaps.data(), n, m.start.data(), m.revcom.data(), m.col_off.data(), m.seq.data(), m.smp.data(), n_ins,

@@ -112,6 +112,7 @@ struct MalnRecord {
   std::string id, desc;                       // desc: the DESC line behind "DESC " (src/map_alignment.c:551-552)
   int start = 0, end = 0, rc = 0, trimmed = 0, num_inputs = 1, score = 0, dropped = 0;
   char segment = 'n';
+  int file_no = 0;                            // the record's place in the file (read_maln_file sorts the records)
   std::string seq, smp;                       // columns start .. end
   std::string seq_raw, smp_raw;               // the SEQ and SMP strings as read: write_ma writes them whole, ace_output counts strlen(SEQ)
   std::vector<int32_t> ins_pos;               // INS_POS pairs, in file order
@@ -208,6 +209,7 @@ inline void read_maln_file(const char* fn, MalnFile* m) {
   m->rec.reserve((size_t)(nas > 0 ? nas : 0));
   for (int r = 0; r < nas; r++) {
     MalnRecord a;
+    a.file_no = r;
     std::string seq, smp;
     c.line(&line); field(line, "ID", &a.id);
     c.line(&line);                                  // DESC: what follows "DESC ", without the newline
