@@ -431,6 +431,30 @@ int mia_hip_ma_dedup(mia_hip_ctx *ctx, int32_t ref_len, int64_t n_records, const
  * mia_hip_ma_dedup before. */
 int mia_hip_get_ma_dedup(mia_hip_ctx *ctx, uint8_t *keep, int64_t *rep, int64_t *size_hist, int64_t *orphans);
 
+/* The deaminated-fragment filter over the records of the last mia_hip_ma_tally (ma_hip -D, -e, -S, -f 95; the reference has no such
+ * filter, the rule is this library's own: DESIGN.md, "Deaminated fragments").  ref_seq: the ref_len characters of the reference;
+ * use[n]: 0 = the record yields no hits and does not make its molecule count (NULL: every record counts); mate[n] as for
+ * mia_hip_ma_dedup, in the record numbers of the tally: -1 = a molecule of its own, -2 = an orphan half (a molecule of its own),
+ * otherwise the record number of its other half (NULL: no halves).  Every column of a record is the event (d', i', j') of
+ * mia_hip_ma_profile, in the read's orientation.  A 5' hit at position k = 1 .. 15 is an event with d' = k - 1, i' = C, j' = T; a 3'
+ * hit at k is one with d' = 31 - k and (i', j') = (G, A), or (C, T) when single_stranded != 0.  MIDDLE, '-' columns, columns behind
+ * the reference and columns with a bad depth code are never hits; INS_POS pairs are not looked at.
+ *   pos5[r], pos3[r]   the smallest k of record r's 5' / 3' hits, 0 for none (they do not depend on n_pos or ends_mode)
+ *   a molecule's m5, m3 = the smallest non-zero pos5 / pos3 over its records; its strand = revcom of its lower-numbered record; it
+ *   counts if one of its records has use != 0
+ *   keep[r]            1 if r's molecule has 0 < m5 <= n_pos (ends_mode 1), 0 < m3 <= n_pos (2), either (0) or both (3)
+ *   hist[2][16][16]    [strand][m5][m3] over the molecules that count; exact, independent of the records' order
+ *   n_molecules = the molecules that count; n_kept = the records with keep == 1.  Either may be NULL.
+ * n_pos = 1 .. 15.  No records: nothing is launched, every result is zero.  MIA_HIP_ERR_STATE without a mia_hip_ma_tally before;
+ * MIA_HIP_ERR_ARG for ref_seq == NULL, n_pos outside 1 .. 15, an ends_mode outside 0 .. 3, a mate that is out of range, r itself or
+ * not mutual, and for records that were tallied with col_off[0] != 0.  A refused call leaves no result; the context stays usable. */
+int mia_hip_ma_damage(mia_hip_ctx *ctx, const char *ref_seq, const uint8_t *use, const int64_t *mate, int32_t n_pos, int32_t single_stranded,
+                      int32_t ends_mode, int64_t *n_molecules, int64_t *n_kept);
+/* pos5[n], pos3[n], keep[n], hist[2 * 16 * 16] and *orphans (the molecules that count whose mate is -2) of the last
+ * mia_hip_ma_damage.  Any pointer may be NULL.  MIA_HIP_ERR_STATE without a successful mia_hip_ma_damage since the last
+ * mia_hip_ma_tally. */
+int mia_hip_get_ma_damage(mia_hip_ctx *ctx, uint8_t *pos5, uint8_t *pos3, uint8_t *keep, int64_t *hist, int64_t *orphans);
+
 /* ---- Myers edit distance -------------------------------------------------- */
 
 /* unsigned myers_diff(const char *seq_a, enum myers_align_mode mode, const char* seq_b, int maxd,
@@ -509,7 +533,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_profile, k_ma_dedup_keys, k_ma_dedup_sort, k_ma_dedup_runs, k_ma_dedup_next, k_ma_dedup_anchors, k_ma_dedup_clusters, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_damage_hits, k_ma_damage_molecules, k_ma_profile, k_ma_dedup_keys, k_ma_dedup_sort, k_ma_dedup_runs, k_ma_dedup_next, k_ma_dedup_anchors, k_ma_dedup_clusters, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

@@ -114,6 +114,9 @@ def _load(path=None):
     if hasattr(lib, "mia_hip_ma_dedup"):
         lib.mia_hip_ma_dedup.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, C.c_int32, P(C.c_int64), P(C.c_int64)]
         lib.mia_hip_get_ma_dedup.argtypes = [vp, vp, vp, vp, P(C.c_int64)]
+    if hasattr(lib, "mia_hip_ma_damage"):
+        lib.mia_hip_ma_damage.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, P(C.c_int64), P(C.c_int64)]
+        lib.mia_hip_get_ma_damage.argtypes = [vp, vp, vp, vp, vp, P(C.c_int64)]
     lib.mia_hip_kernel_time.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_int64)]
     lib.mia_hip_stage_stats.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp, P(C.c_int32)]
     lib.mia_hip_set_stage_mask.argtypes = [vp, C.c_uint32]
@@ -158,7 +161,7 @@ def exported_symbols():
             "mia_hip_upload_reads", "mia_hip_pass1", "mia_hip_realign", "mia_hip_align_windows", "mia_hip_get_alignments", "mia_hip_get_scripts", "mia_hip_cull",
             "mia_hip_get_dropped", "mia_hip_set_slot_dropped", "mia_hip_score_cut", "mia_hip_num_records",
             "mia_hip_tally", "mia_hip_tally_buffers", "mia_hip_ins_events", "mia_hip_set_ins_events",
-            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
+            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
             "mia_hip_get_record_params", "mia_hip_set_read_base", "mia_hip_links", "mia_hip_set_links", "mia_hip_link_lengths",
             "mia_hip_finish_links", "mia_hip_plain_stats", "mia_hip_score_sums",
             "mia_hip_score_cut_from_sums", "mia_hip_stage_stats", "mia_hip_measure_peaks", "mia_hip_measure_issue", "mia_hip_set_tally", "mia_hip_iterate", "mia_hip_set_stage_mask", "mia_hip_comm_unique_id", "mia_hip_comm_init", "mia_hip_comm_destroy",
@@ -567,7 +570,7 @@ class MiaHip:
         self._chk(self._l.mia_hip_stage_stats(self._h, 1 if reset else 0, cap, names, ms, k, C.byref(n)))
         return {names[i].decode(): (ms[i], k[i]) for i in range(min(n.value, cap))}
 
-    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs", "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
+    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs", "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
 
     def comm_init(self, unique_id, n_ranks, rank):
         """attach an RCCL communicator (ncclCommInitRank on this context's GPU); unique_id: the 128 bytes of comm_unique_id()
@@ -618,10 +621,12 @@ class MiaHip:
         io = np.ascontiguousarray(ins_off, dtype=np.int64)
         ib = np.frombuffer(bytes(ins_bases), dtype=np.uint8) if not isinstance(ins_bases, np.ndarray) else ins_bases
         self.L = int(ref_len)
+        self._ma_n = 0
         self._chk(self._l.mia_hip_ma_tally(self._h, int(ref_len), _ptr(gaps), len(start), _ptr(start), _ptr(revcom), _ptr(col_off),
                                            _ptr(seq) if len(seq) else None, _ptr(smp) if len(smp) else None, len(ir),
                                            _ptr(ir) if len(ir) else None, _ptr(ip) if len(ip) else None, _ptr(io),
                                            _ptr(ib) if len(ib) else None))
+        self._ma_n = len(start)
 
     def ma_region(self, first, last):
         """print_region's record lines (reference src/map_align.c:660-750) over the records of the last ma_tally, for the
@@ -748,6 +753,39 @@ class MiaHip:
                                            _ptr(mate) if mate is not None and n else None, int(tolerance), C.byref(n_mol), C.byref(n_clu)))
         self._chk(self._l.mia_hip_get_ma_dedup(self._h, opt(keep), opt(rep), _ptr(hist), C.byref(orphans)))
         return keep, rep, hist, n_mol.value, n_clu.value, orphans.value
+
+    DAMAGE_MODES = {"any": 0, "5": 1, "3": 2, "both": 3}
+
+    def ma_damage(self, ref_seq, n_pos, use=None, mate=None, single_stranded=False, mode="any"):
+        """the deaminated-fragment filter (ma_hip -D, -e, -S, -f 95) over the records of the last ma_tally; ref_seq: the reference's
+        characters; n_pos 1 .. 15; use: per record 0 = no hits from it (None: every record counts); mate: per record -1, -2 (an orphan
+        half) or the record number of its other half (None: no halves); mode "any", "5", "3" or "both".  (pos5[n], pos3[n], keep[n]
+        uint8, hist[2, 16, 16] int64, n_molecules, n_kept, orphans): the smallest position 1 .. 15 of the record's C>T at its 5' end
+        and of its G>A (single_stranded: C>T) at its 3' end, 0 for none; keep = its molecule has such a hit within n_pos at the ends
+        `mode` asks for; hist[strand, m5, m3] = molecules by strand and smallest positions; n_kept = records with keep set."""
+        if not hasattr(self._l, "mia_hip_ma_damage"):
+            raise RuntimeError("this libmia_hip has no mia_hip_ma_damage")
+        ref = ref_seq.encode("latin1") if isinstance(ref_seq, str) else bytes(ref_seq)
+        if len(ref) != self.L:
+            raise ValueError("ma_damage: the reference has %d characters, the tallied job %d columns" % (len(ref), self.L))
+        if mode not in self.DAMAGE_MODES:
+            raise ValueError("ma_damage: mode must be one of any, 5, 3, both")
+        if use is not None:
+            use = np.ascontiguousarray(use, dtype=np.uint8)
+        if mate is not None:
+            mate = np.ascontiguousarray(mate, dtype=np.int64)
+        n = getattr(self, "_ma_n", 0)                      # the records of the last ma_tally
+        if (use is not None and len(use) != n) or (mate is not None and len(mate) != n):
+            raise ValueError("ma_damage: use and mate hold one entry per tallied record (%d)" % n)
+        n_mol, n_kept, orphans = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._l.mia_hip_ma_damage(self._h, C.c_char_p(ref), _ptr(use) if use is not None and use.size else None,
+                                            _ptr(mate) if mate is not None and mate.size else None, int(n_pos), 1 if single_stranded else 0,
+                                            self.DAMAGE_MODES[mode], C.byref(n_mol), C.byref(n_kept)))
+        pos5, pos3, keep = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        hist = np.zeros((2, 16, 16), dtype=np.int64)
+        opt = lambda a: _ptr(a) if n else None
+        self._chk(self._l.mia_hip_get_ma_damage(self._h, opt(pos5), opt(pos3), opt(keep), _ptr(hist), C.byref(orphans)))
+        return pos5, pos3, keep, hist, n_mol.value, n_kept.value, orphans.value
 
     def ins_tally(self):
         """(ins_off[L+1], ins_tally[slots][9]) of the insert columns, after consensus()."""

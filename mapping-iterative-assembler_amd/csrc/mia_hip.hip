@@ -37,15 +37,16 @@
 #include "mia_ma_ends_kernels.h"
 #include "mia_ma_cols_kernels.h"
 #include "mia_ma_dedup_kernels.h"
+#include "mia_ma_damage_kernels.h"
 
 using namespace mia;
 
 // timed stages (HIP events on the context's stream around the kernel launches of that kind)
-enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_PROFILE, STG_MA_DEDUP_KEYS, STG_MA_DEDUP_SORT, STG_MA_DEDUP_RUNS, STG_MA_DEDUP_NEXT, STG_MA_DEDUP_ANCHORS, STG_MA_DEDUP_CLUSTERS, STG_MA_TALLY, STG_MA_COLS, STG_MA_ENDS, STG_COUNT };
+enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_DAMAGE_HITS, STG_MA_DAMAGE_MOLECULES, STG_MA_PROFILE, STG_MA_DEDUP_KEYS, STG_MA_DEDUP_SORT, STG_MA_DEDUP_RUNS, STG_MA_DEDUP_NEXT, STG_MA_DEDUP_ANCHORS, STG_MA_DEDUP_CLUSTERS, STG_MA_TALLY, STG_MA_COLS, STG_MA_ENDS, STG_COUNT };
 static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan",
                                                    "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select",
                                                    "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout",
-                                                   "k_ma_sam_render", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs",
+                                                   "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs",
                                                    "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"};
 
 // One device block for every small counter of an iteration (planner bins and header, filter / band-pipeline counters, link
@@ -268,7 +269,7 @@ struct mia_hip_ctx {
   DevBuf<unsigned long long> d_ma_ctl;
   // what the exports' calls found, per export (the big results are further down): mia_hip_ma_tally forgets all of it at once
   struct MaOut {
-    bool region_done = false, ace_done = false, sam_done = false, prof_done = false, ends_done = false, cols_done = false;
+    bool region_done = false, ace_done = false, sam_done = false, prof_done = false, ends_done = false, cols_done = false, damage_done = false;
     int32_t first = 0, last = -1; int64_t rows = 0, width = 0, ace_bytes = 0, sam_bytes = 0;
   } ma_out;
   // ... and for mia_hip_ma_ace: whether the job has an ACE export at all (GAPS, the records' columns), the running sum of ref->gaps,
@@ -302,6 +303,14 @@ struct mia_hip_ctx {
     DevBuf<uint32_t> d_val[2], d_jump[2], d_counts, d_runid, d_first, d_mark, d_cluster, d_anchor;
     int64_t hist[MA_DEDUP_HIST] = {0};
   } dedup;
+
+  // ... and mia_hip_ma_damage, which reads the tallied records and shares the reference's and the selection's buffers with the profile:
+  // the pairing, per record 16 - k of its best hit at either end (hit5 | hit3, zeroed before the launch), pos5 | pos3 and keep, which
+  // stay on the device until mia_hip_get_ma_damage; the 514 bins (ma_damage_body.h) on the device and, after the call, here
+  struct MaDamage {
+    DevBuf<int64_t> d_mate; DevBuf<uint32_t> d_hit; DevBuf<uint8_t> d_pos, d_keep; DevBuf<unsigned long long> d_bins;
+    int64_t bins[MA_DMG_BINS] = {0};
+  } damage;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------

@@ -621,6 +621,79 @@ extern "C" int mia_hip_get_ma_dedup(mia_hip_ctx* ctx, uint8_t* keep, int64_t* re
   return MIA_HIP_OK;
 }
 
+// The deaminated-fragment filter (ma_hip -D, -e, -S, -f 95) of the records of the last mia_hip_ma_tally: see mia_ma_damage_kernels.h.
+// Columns, depth codes and strands are on the device already; the reference, the selection and the pairing go up.
+extern "C" int mia_hip_ma_damage(mia_hip_ctx* ctx, const char* ref_seq, const uint8_t* use, const int64_t* mate, int32_t n_pos, int32_t single_stranded,
+                                 int32_t ends_mode, int64_t* n_molecules, int64_t* n_kept) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  ctx->ma_out.damage_done = false;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_damage"; return MIA_HIP_ERR_STATE; }
+  if (!ref_seq) { ctx->err = "ma_damage: no reference sequence"; return MIA_HIP_ERR_ARG; }
+  if (!ma_dmg_pos_ok(n_pos)) { ctx->err = "ma_damage: the number of positions must lie in 1 .. 15"; return MIA_HIP_ERR_ARG; }
+  if (!ma_dmg_mode_ok(ends_mode)) { ctx->err = "ma_damage: the ends mode must be 0 (any), 1 (5'), 2 (3') or 3 (both)"; return MIA_HIP_ERR_ARG; }
+  if (ctx->ma_n > 0 && ctx->ma_cols < 0) { ctx->err = "ma_damage: col_off[0] of the tallied records is not 0"; return MIA_HIP_ERR_ARG; }
+  const int64_t n = ctx->ma_n, T = ctx->ma_cols;
+  const int32_t L = ctx->ma_L;
+  if (!ma_dmg_mate_ok(mate, n)) { ctx->err = "ma_damage: mate is out of range, the record itself or not mutual"; return MIA_HIP_ERR_ARG; }
+  auto& dg = ctx->damage;
+  memset(dg.bins, 0, sizeof dg.bins);
+  if (n > 0) {                                               // without records there is no launch and every result is zero
+    HIPCHK(hipSetDevice(ctx->device));
+    MaSelection sel;
+    if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, dg.d_hit, 2 * n) || dev_ensure(ctx, dg.d_pos, 2 * n) || dev_ensure(ctx, dg.d_keep, n) ||
+        dev_ensure(ctx, dg.d_bins, MA_DMG_BINS) || (mate && dev_ensure(ctx, dg.d_mate, n)))
+      return MIA_HIP_ERR_NOMEM;
+    if (const int rc = ma_selection(ctx, nullptr, use, &sel)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+    if (mate) HIPCHK(hipMemcpyAsync(dg.d_mate, mate, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(dg.d_hit, 0, (size_t)n * 2 * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(dg.d_keep, 0, (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(dg.d_bins, 0, (size_t)MA_DMG_BINS * 8, ctx->stream));
+    const MaRecords mr = ma_records(ctx);
+    const int64_t wide = (int64_t)ctx->cus * MAG_WGS_PER_CU;
+    // persistent grids: the workgroups that are resident at once, or one per chunk (per 256 records) when there are fewer
+    int64_t grid = ma_dmg_chunks(T) < wide ? ma_dmg_chunks(T) : wide;
+    if (grid < 1) grid = 1;                                  // (records that all lack columns: one workgroup that finds no chunk)
+    MaProfView v{mr, T, ctx->d_prof_ref, sel.use};
+    if (stage_launch(ctx, STG_MA_DAMAGE_HITS, k_ma_damage_hits, dim3((unsigned)grid), dim3(MAG_THREADS), 0, ctx->stream, v, single_stranded ? 1 : 0,
+                     (uint32_t*)dg.d_hit, (uint32_t*)dg.d_hit + n))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    MaDmgMolView mv{n, mr.revcom, sel.use, mate ? (const int64_t*)dg.d_mate : nullptr, (const uint32_t*)dg.d_hit, (const uint32_t*)dg.d_hit + n, n_pos, ends_mode,
+                    (uint8_t*)dg.d_pos, (uint8_t*)dg.d_pos + n, (uint8_t*)dg.d_keep};
+    grid = ma_dmg_record_wgs(n) < wide ? ma_dmg_record_wgs(n) : wide;
+    if (stage_launch(ctx, STG_MA_DAMAGE_MOLECULES, k_ma_damage_molecules, dim3((unsigned)grid), dim3(MAG_THREADS), 0, ctx->stream, mv,
+                     (unsigned long long*)dg.d_bins))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dg.bins, dg.d_bins, (size_t)MA_DMG_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  int64_t molecules = 0;
+  for (int b = 0; b < MA_DMG_HIST; b++) molecules += dg.bins[b];
+  ctx->ma_out.damage_done = true;
+  if (n_molecules) *n_molecules = molecules;
+  if (n_kept) *n_kept = dg.bins[MA_DMG_KEPT];
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_damage(mia_hip_ctx* ctx, uint8_t* pos5, uint8_t* pos3, uint8_t* keep, int64_t* hist, int64_t* orphans) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident || !ctx->ma_out.damage_done) { ctx->err = "ma_damage first"; return MIA_HIP_ERR_STATE; }
+  const int64_t n = ctx->ma_n;
+  auto& dg = ctx->damage;
+  if (n > 0 && (pos5 || pos3 || keep)) {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (pos5) HIPCHK(hipMemcpyAsync(pos5, dg.d_pos, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (pos3) HIPCHK(hipMemcpyAsync(pos3, dg.d_pos + n, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (keep) HIPCHK(hipMemcpyAsync(keep, dg.d_keep, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  if (hist) memcpy(hist, dg.bins, sizeof(int64_t) * MA_DMG_HIST);
+  if (orphans) *orphans = dg.bins[MA_DMG_ORPHANS];
+  return MIA_HIP_OK;
+}
+
 extern "C" int mia_hip_get_ins_tally(mia_hip_ctx* ctx, int32_t* ins_off, int32_t* ins_tally, int64_t cap_slots, int64_t* n_slots) {
   if (!ctx) return MIA_HIP_ERR_ARG;
   if (!ctx->tallied || !ctx->consensus_done) { ctx->err = "consensus first"; return MIA_HIP_ERR_STATE; }

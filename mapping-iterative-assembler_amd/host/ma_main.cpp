@@ -3,7 +3,7 @@
 // -R), -f 7 (ACE export, every record in full), -f 8 (SAM, which the reference does not have: the reads as aligned to the reference), -f 9 and -f 91 (the substitution profile of the
 // assembly, which the reference does not have either: substitution counts by distance from the read's ends, and a -s matrix made
 // from them; -P pseudocount, -A dropped records too), -f 92 and -f 93 (which the reference does not have either: the reference bases around the places where reads
-// begin and end, and the reads' lengths per strand), -f 42 (likewise this tool's own: -f 41's base counts per
+// begin and end, and the reads' lengths per strand), -f 95 (the damage classes of the molecules), -f 42 (likewise this tool's own: -f 41's base counts per
 // strand, and the records that start and end on every column per strand, which are format 3's columns 5-8) and -m (the .maln written again, sorted, with -c and -I applied).  The .maln text is parsed exactly as read_ma does (host/maln_text.h); the add_base loops of show_consensus /
 // find_ins_cons run on the GPU (mia_hip_ma_tally, every record counts, dropped or not), and so do the selection and the
 // rows of the region view (mia_hip_ma_region), the padded reads of the ACE export (mia_hip_ma_ace) and CIGAR, SEQ and NM of the SAM
@@ -15,6 +15,10 @@
 // -u removes duplicate molecules in front of all of it (the reference has the rule in mia -u, not in ma): the
 // halves of reads split at the origin are paired here (host/maln_dedup.h), the clusters are formed on the GPU (mia_hip_ma_dedup), the
 // records that are not kept leave with their inserts and GAPS is reset as cull_maln_from_fsdb does (src/mia.c:484-504).
+// -D N keeps only the molecules that carry a deamination signature themselves ("Deaminated fragments": a C read as T within N
+// positions of the 5' end, a G read as A -- -S: a C read as T -- within N of the 3' end; -e says which ends must show it): it runs behind
+// -u and in front of everything else, the per-record decision is made on the GPU (mia_hip_ma_damage) over the records of a tally of the
+// file as it stands, and the records that are not kept leave as for -u.  -f 95 prints the molecules' damage classes.
 // No CPU fallback.
 #include <ctype.h>
 #include <float.h>
@@ -39,6 +43,7 @@
 #include "../csrc/ma_ends_body.h"
 #include "../csrc/ma_cols_body.h"
 #include "../csrc/ma_dedup_body.h"
+#include "../csrc/ma_damage_body.h"
 
 namespace {
 
@@ -47,10 +52,12 @@ using namespace maln_text;
 typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92 or 93>\n   -R <REGION_START:REGION_END>\n"
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92, 93 or 95>\n   -R <REGION_START:REGION_END>\n"
          "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
-         "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 42, 9, 91, 92 and 93)\n"
+         "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 42, 9, 91, 92, 93 and 95)\n"
          "   -u remove duplicate molecules first\n   -t <tolerance of -u in columns, 0 .. 100, default 0>\n"
+         "   -D <N: keep only deaminated fragments, a hit within N = 1 .. 15 positions of a read end>\n"
+         "   -e <ends of -D that must show a hit: 5, 3, any (default) or both>\n   -S single-stranded library (-D, format 95)\n"
          "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
          "(-f 1 clustalw, the default; -f 2 one line each plus coverage), the per-column table (-f 41 all positions, -f 4\n"
          "positions that differ from the reference), the assembled sequence (-f 5), and the reference, the consensus and every\n"
@@ -73,7 +80,15 @@ void help() {
          "-u removes duplicates before anything else is computed, by the rule of mia -u: molecules (a read split at the origin is one)\n"
          "with the same strand, start and end are one cluster -- with -t N, also those within N columns of the cluster's first in\n"
          "start and in end -- and only the best-scoring molecule of the cluster's first coordinates stays; GAPS shrinks to the inserts\n"
-         "of what is left, and every format and -m see the smaller file.  Clusters are formed on the MI355X.  Format 3 (format 2's summary plus\n"
+         "of what is left, and every format and -m see the smaller file.  Clusters are formed on the MI355X.\n"
+         "-D N keeps only the molecules that are deaminated themselves, behind -u and in front of everything else: a reference C read as T at\n"
+         "one of the first N positions of the read (a 5' hit), or a reference G read as A at one of its last N positions (a 3' hit; -S, a\n"
+         "single-stranded library: a C read as T there too), positions as mia scored them (1 .. 15 from either end), in the read's\n"
+         "orientation; a read split at the origin is one molecule.  -e 5 asks for a 5' hit, -e 3 for a 3' hit, -e both for both, -e any\n"
+         "(the default) for either.  What is not kept leaves as for -u, and the consensus is called from the deaminated fragments alone\n"
+         "(-D 1 -e 3 -f 9 prints the 5' profile of the fragments deaminated at their 3' end).  The decision is made on the MI355X.\n"
+         "-f 95 prints the damage classes of the file as it stands behind -u and -D: for N = 1 .. 15 the molecules with a 5' hit within N,\n"
+         "with a 3' hit within N, with both and with either, on the forward strand, the reverse strand and both.  Format 3 (format 2's summary plus\n"
          "a table of coverage and of the records that start and end at every column) is outside the accelerated path.\n");
 }
 
@@ -330,6 +345,26 @@ void cols_table(const Maln& m, int64_t n_used, int64_t n_events, int64_t beyond,
   o.flush();
 }
 
+// -f 95: the damage classes, from hist[strand][m5][m3] alone
+void damage_table(int64_t n_molecules, int64_t orphans, int64_t n_used, bool single_stranded, const int64_t* hist) {
+  Out o;
+  o.fmt("# ma_hip damage classes: %lld molecules, %lld orphan halves, %lld records, library %s\n", (long long)n_molecules, (long long)orphans,
+        (long long)n_used, single_stranded ? "ss" : "ds");
+  o.buf += "# N";
+  for (const char* strand : {"+", "-", ""}) for (const char* what : {"5p", "3p", "both", "either"}) o.fmt("\t%s%s", what, strand);
+  o.buf += '\n';
+  for (int n_pos = 1; n_pos <= mia::MA_DMG_MAX_POS; n_pos++) {
+    o.fmt("%d", n_pos);
+    for (int strand = 0; strand < 3; strand++) {
+      int64_t row[4];
+      mia::ma_dmg_row(hist, strand, n_pos, row);
+      for (int k = 0; k < 4; k++) o.fmt("\t%lld", (long long)row[k]);
+    }
+    o.buf += '\n';
+  }
+  o.flush();
+}
+
 void die(mia_hip_ctx* g, const char* what) {
   fprintf(stderr, "%s: %s\n", what, g ? mia_hip_last_error(g) : "no context");
   exit(1);
@@ -342,11 +377,13 @@ int main(int argc, char* argv[]) {
   bool id_assigned = false, in_ma = false, any_arg = false, out_ma = false;
   int cons_scheme = 1, out_format = 1, gpu = 0, reg_start = 90, reg_end = 109;
   bool in_color = false, use_dropped = false, region_given = false, dedup = false, tol_given = false;
-  long tolerance = 0;
+  long tolerance = 0, damage_n = 0;
+  bool damage = false, ends_given = false, single_stranded = false;
+  int ends_mode = mia::MA_DMG_ANY;
   double score_int = -1.0, score_slo = -1.0, alpha = 1.0;
   int ich;
-  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount>, -A, -u and -t <tolerance>
-  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:Aut:")) != -1) {
+  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount>, -A, -u, -t <tolerance>, -D <N>, -e <ends> and -S
+  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:Aut:D:e:S")) != -1) {
     switch (ich) {
       case 'I': assign_id = optarg; id_assigned = true; break;
       case 'c': cons_scheme = atoi(optarg); any_arg = true; break;
@@ -364,12 +401,18 @@ int main(int argc, char* argv[]) {
       case 'A': use_dropped = true; break;
       case 'u': dedup = true; any_arg = true; break;
       case 't': { char* end = nullptr; tolerance = strtol(optarg, &end, 10); if (end == optarg || *end) tolerance = -1; tol_given = true; } break;
+      case 'D': { char* end = nullptr; damage_n = strtol(optarg, &end, 10); if (end == optarg || *end) damage_n = -1; damage = true; any_arg = true; } break;
+      case 'e':
+        ends_given = true;
+        ends_mode = !strcmp(optarg, "any") ? mia::MA_DMG_ANY : !strcmp(optarg, "5") ? mia::MA_DMG_5 : !strcmp(optarg, "3") ? mia::MA_DMG_3 : !strcmp(optarg, "both") ? mia::MA_DMG_BOTH : -1;
+        break;
+      case 'S': single_stranded = true; break;
       default: help(); exit(0);
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 42 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93) {
-    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 42, 8, 9, 91, 92 and 93, which the reference does not have); use the reference's ma\n", out_format);
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 42 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93 && out_format != 95) {
+    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 42, 8, 9, 91, 92, 93 and 95, which the reference does not have); use the reference's ma\n", out_format);
     exit(1);
   }
   if (out_format == 91 && !mia::ma_prof_alpha_ok(alpha)) {
@@ -378,6 +421,13 @@ int main(int argc, char* argv[]) {
   }
   if (tol_given && !dedup) { fprintf(stderr, "ma_hip: -t is the tolerance of -u, which is not given\n"); exit(1); }
   if (tolerance < 0 || tolerance > mia::MA_DEDUP_MAX_TOL) { fprintf(stderr, "ma_hip: -t must be a whole number from 0 to %d\n", mia::MA_DEDUP_MAX_TOL); exit(1); }
+  if (ends_given && !damage) { fprintf(stderr, "ma_hip: -e names the ends of -D, which is not given\n"); exit(1); }
+  if (single_stranded && !damage && out_format != 95) { fprintf(stderr, "ma_hip: -S is the library type of -D and of -f 95, neither of which is given\n"); exit(1); }
+  if (damage && !mia::ma_dmg_pos_ok((int)(damage_n < 0 || damage_n > 1000 ? -1 : damage_n))) {
+    fprintf(stderr, "ma_hip: -D must be a whole number from 1 to %d\n", mia::MA_DMG_MAX_POS);
+    exit(1);
+  }
+  if (ends_given && ends_mode < 0) { fprintf(stderr, "ma_hip: -e (the ends of -D) must be 5, 3, any or both\n"); exit(1); }
   Maln m;
   read_ma(ma_in_fn.c_str(), &m);
   if (id_assigned) m.ref_id = assign_id.substr(0, 256);
@@ -402,6 +452,27 @@ int main(int argc, char* argv[]) {
     for (int64_t f = 0; f < n_all; f++) keep[in.at[(size_t)f]] = keep_file[(size_t)f];
     remove_records(&m, keep);
   }
+  // the file as it stands goes to the device: the PSSMs and the records (mia_hip_ma_tally, which also validates them)
+  auto tally_file = [&]() {
+    open_gpu();
+    if (mia_hip_set_pssm(g, &m.fpsm[0][0][0], &m.rpsm[0][0][0]) != MIA_HIP_OK) die(g, "set_pssm");
+    if (mia_hip_ma_tally(g, m.L, m.gaps.data(), (int64_t)m.start.size(), m.start.data(), m.revcom.data(), m.col_off.data(), m.seq.data(), m.smp.data(),
+                         (int64_t)m.ins_record.size(), m.ins_record.data(), m.ins_pos.data(), m.ins_off.data(), m.ins_bases.data()) != MIA_HIP_OK)
+      die(g, "ma_tally");
+  };
+  if (damage) {
+    // the deaminated-fragment filter, behind -u and in front of everything else: the decision per molecule over all records (dropped
+    // or not) on the device, then what is not kept leaves as for -u
+    tally_file();
+    std::vector<int64_t> mate;
+    pair_halves(m, &mate);
+    std::vector<uint8_t> keep(m.rec.size() + 1, 0);
+    if (mia_hip_ma_damage(g, m.ref_seq.data(), nullptr, mate.data(), (int32_t)damage_n, single_stranded ? 1 : 0, ends_mode, nullptr, nullptr) != MIA_HIP_OK)
+      die(g, "ma_damage");
+    if (mia_hip_get_ma_damage(g, nullptr, nullptr, keep.data(), nullptr, nullptr) != MIA_HIP_OK) die(g, "get_ma_damage");
+    keep.resize(m.rec.size());
+    remove_records(&m, keep);
+  }
   if (out_format == 8 && !mia::ma_sam_gaps_ok(m.gaps.data(), m.L)) {
     fprintf(stderr, "ma_hip: %s has no SAM export: its GAPS line holds a negative value\n", ma_in_fn.c_str());
     exit(1);
@@ -417,12 +488,8 @@ int main(int argc, char* argv[]) {
     return 0;
   };
 
-  open_gpu();
-  if (mia_hip_set_pssm(g, &m.fpsm[0][0][0], &m.rpsm[0][0][0]) != MIA_HIP_OK) die(g, "set_pssm");
-  const int64_t n = (int64_t)m.start.size(), n_ins = (int64_t)m.ins_record.size();
-  if (mia_hip_ma_tally(g, m.L, m.gaps.data(), n, m.start.data(), m.revcom.data(), m.col_off.data(), m.seq.data(), m.smp.data(), n_ins,
-                       m.ins_record.data(), m.ins_pos.data(), m.ins_off.data(), m.ins_bases.data()) != MIA_HIP_OK)
-    die(g, "ma_tally");
+  tally_file();
+  const int64_t n = (int64_t)m.start.size();
   const int L = m.L;
   if (out_format == 8) {
     int64_t n_rec = 0, body_bytes = 0;
@@ -458,6 +525,19 @@ int main(int argc, char* argv[]) {
     if (mia_hip_get_ma_ends(g, ctx_count.data(), len_count.data(), &halves) != MIA_HIP_OK) die(g, "get_ma_ends");
     if (out_format == 92) ends_table(n_used, n5, n3, ctx_count.data());
     else lengths_table(len_count.data(), halves);
+    return finish(g);
+  }
+  if (out_format == 95) {
+    std::vector<uint8_t> use((size_t)n + 1, 1);
+    int64_t n_used = 0;
+    for (int64_t r = 0; r < n; r++) n_used += use[(size_t)r] = use_dropped || !m.rec[(size_t)r].dropped ? 1 : 0;
+    std::vector<int64_t> mate, hist((size_t)mia::MA_DMG_HIST);
+    pair_halves(m, &mate);
+    int64_t n_molecules = 0, orphans = 0;
+    if (mia_hip_ma_damage(g, m.ref_seq.data(), use.data(), mate.data(), mia::MA_DMG_MAX_POS, single_stranded ? 1 : 0, mia::MA_DMG_ANY, &n_molecules, nullptr) != MIA_HIP_OK)
+      die(g, "ma_damage");
+    if (mia_hip_get_ma_damage(g, nullptr, nullptr, nullptr, hist.data(), &orphans) != MIA_HIP_OK) die(g, "get_ma_damage");
+    damage_table(n_molecules, orphans, n_used, single_stranded, hist.data());
     return finish(g);
   }
   if (out_format == 42) {
