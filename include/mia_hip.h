@@ -455,6 +455,35 @@ int mia_hip_ma_damage(mia_hip_ctx *ctx, const char *ref_seq, const uint8_t *use,
  * mia_hip_ma_tally. */
 int mia_hip_get_ma_damage(mia_hip_ctx *ctx, uint8_t *pos5, uint8_t *pos3, uint8_t *keep, int64_t *hist, int64_t *orphans);
 
+/* The end mask over the records of the last mia_hip_ma_tally (ma_hip -E, -x, -f 96; the reference has no such step, the rule is this
+ * library's own: DESIGN.md, "End mask").  Column c of a record has the depth code d = smp[c] - 'A' and, in the read's orientation,
+ * d' = d (forward) or 30 - d (revcom).  It is in the 5' zone at position k = d' + 1 when d lies in 0 .. 30 and d' < n5, in the 3' zone
+ * at k = 31 - d' when d' > 30 - n3; MIDDLE and a bad code are in no zone.  INS_POS pairs have no zone of their own.
+ *   mode 0 (trim)  a = the record's leading zone columns, b = its columns minus its trailing zone columns (not below a); then a moves
+ *                  forward and b backward over columns whose SEQ character is '-'.  a >= b: the record is emptied.  Otherwise it keeps
+ *                  columns a .. b-1, START += a, and of its pairs those with a < pos < b, with pos -= a.
+ *   mode 1 (N)     nothing leaves.  A 5' zone column whose base, upper-cased and in the read's orientation, is T (a stored A of a
+ *                  revcom record) gets the SEQ character N; so does a 3' zone column whose base is A -- T when single_stranded != 0.
+ * n5, n3 = 0 .. 15, not both 0; single_stranded only with mode 1.  *n_kept = the records that are not emptied, *cols_kept = their
+ * columns; either may be NULL.  No records: nothing is launched, every result is zero.  MIA_HIP_ERR_STATE without a mia_hip_ma_tally
+ * before; MIA_HIP_ERR_ARG for n5 or n3 outside 0 .. 15 or both 0, a mode outside 0 .. 1, single_stranded with mode 0, and for records
+ * that were tallied with col_off[0] != 0.  A refused call leaves no result; the context stays usable. */
+int mia_hip_ma_mask(mia_hip_ctx *ctx, int32_t n5, int32_t n3, int32_t mode, int32_t single_stranded, int64_t *n_kept, int64_t *cols_kept);
+/* The record view the last mia_hip_ma_mask left on the device, in the record and pair numbers of the tally:
+ *   first[n], count[n]   a and b - a (mode 1: 0 and the record's columns); count 0 in mode 0 = emptied (then first is 0)
+ *   start[n]             START of the masked record (an emptied record's stays)
+ *   col_off[n+1]         the exclusive sum of count
+ *   seq, smp             the cols_kept characters of the masked records' SEQ and SMP; cap_bytes = what either buffer holds
+ *   pair_keep[n_ins]     1 if the pair stays, ins_pos[n_ins] its position in the masked record (0 where it leaves)
+ *   hist[2 * 2 * 16]     [strand][end][k], end 0 = 5': mode 0 the zone columns that left, an emptied record's included; mode 1 the
+ *                        columns that became N
+ *   scalars[6]           emptied forward, emptied revcom, stripped ('-' columns in no zone that left), pairs of surviving records
+ *                        that left, n_kept, cols_kept
+ * All counts are exact and independent of the records' order.  Any pointer may be NULL.  MIA_HIP_ERR_STATE without a successful
+ * mia_hip_ma_mask since the last mia_hip_ma_tally; MIA_HIP_ERR_ARG if seq or smp is given and cap_bytes < cols_kept. */
+int mia_hip_get_ma_mask(mia_hip_ctx *ctx, int32_t *first, int32_t *count, int32_t *start, int64_t *col_off, char *seq, char *smp, int64_t cap_bytes,
+                        uint8_t *pair_keep, int32_t *ins_pos, int64_t *hist, int64_t *scalars);
+
 /* ---- Myers edit distance -------------------------------------------------- */
 
 /* unsigned myers_diff(const char *seq_a, enum myers_align_mode mode, const char* seq_b, int maxd,
@@ -533,7 +562,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_sam_layout, k_ma_sam_render, k_ma_damage_hits, k_ma_damage_molecules, k_ma_profile, k_ma_dedup_keys, k_ma_dedup_sort, k_ma_dedup_runs, k_ma_dedup_next, k_ma_dedup_anchors, k_ma_dedup_clusters, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_mask_bounds, k_ma_mask_layout, k_ma_mask_apply, k_ma_sam_layout, k_ma_sam_render, k_ma_damage_hits, k_ma_damage_molecules, k_ma_profile, k_ma_dedup_keys, k_ma_dedup_sort, k_ma_dedup_runs, k_ma_dedup_next, k_ma_dedup_anchors, k_ma_dedup_clusters, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

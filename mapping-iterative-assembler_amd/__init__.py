@@ -117,6 +117,9 @@ def _load(path=None):
     if hasattr(lib, "mia_hip_ma_damage"):
         lib.mia_hip_ma_damage.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, P(C.c_int64), P(C.c_int64)]
         lib.mia_hip_get_ma_damage.argtypes = [vp, vp, vp, vp, vp, P(C.c_int64)]
+    if hasattr(lib, "mia_hip_ma_mask"):
+        lib.mia_hip_ma_mask.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int64), P(C.c_int64)]
+        lib.mia_hip_get_ma_mask.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
     lib.mia_hip_kernel_time.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_int64)]
     lib.mia_hip_stage_stats.argtypes = [vp, C.c_int, C.c_int32, vp, vp, vp, P(C.c_int32)]
     lib.mia_hip_set_stage_mask.argtypes = [vp, C.c_uint32]
@@ -161,7 +164,7 @@ def exported_symbols():
             "mia_hip_upload_reads", "mia_hip_pass1", "mia_hip_realign", "mia_hip_align_windows", "mia_hip_get_alignments", "mia_hip_get_scripts", "mia_hip_cull",
             "mia_hip_get_dropped", "mia_hip_set_slot_dropped", "mia_hip_score_cut", "mia_hip_num_records",
             "mia_hip_tally", "mia_hip_tally_buffers", "mia_hip_ins_events", "mia_hip_set_ins_events",
-            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
+            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_ma_mask", "mia_hip_get_ma_mask", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
             "mia_hip_get_record_params", "mia_hip_set_read_base", "mia_hip_links", "mia_hip_set_links", "mia_hip_link_lengths",
             "mia_hip_finish_links", "mia_hip_plain_stats", "mia_hip_score_sums",
             "mia_hip_score_cut_from_sums", "mia_hip_stage_stats", "mia_hip_measure_peaks", "mia_hip_measure_issue", "mia_hip_set_tally", "mia_hip_iterate", "mia_hip_set_stage_mask", "mia_hip_comm_unique_id", "mia_hip_comm_init", "mia_hip_comm_destroy",
@@ -570,7 +573,7 @@ class MiaHip:
         self._chk(self._l.mia_hip_stage_stats(self._h, 1 if reset else 0, cap, names, ms, k, C.byref(n)))
         return {names[i].decode(): (ms[i], k[i]) for i in range(min(n.value, cap))}
 
-    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs", "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
+    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_mask_bounds", "k_ma_mask_layout", "k_ma_mask_apply", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs", "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
 
     def comm_init(self, unique_id, n_ranks, rank):
         """attach an RCCL communicator (ncclCommInitRank on this context's GPU); unique_id: the 128 bytes of comm_unique_id()
@@ -621,12 +624,12 @@ class MiaHip:
         io = np.ascontiguousarray(ins_off, dtype=np.int64)
         ib = np.frombuffer(bytes(ins_bases), dtype=np.uint8) if not isinstance(ins_bases, np.ndarray) else ins_bases
         self.L = int(ref_len)
-        self._ma_n = 0
+        self._ma_n = self._ma_n_ins = 0
         self._chk(self._l.mia_hip_ma_tally(self._h, int(ref_len), _ptr(gaps), len(start), _ptr(start), _ptr(revcom), _ptr(col_off),
                                            _ptr(seq) if len(seq) else None, _ptr(smp) if len(smp) else None, len(ir),
                                            _ptr(ir) if len(ir) else None, _ptr(ip) if len(ip) else None, _ptr(io),
                                            _ptr(ib) if len(ib) else None))
-        self._ma_n = len(start)
+        self._ma_n, self._ma_n_ins = len(start), len(ir)
 
     def ma_region(self, first, last):
         """print_region's record lines (reference src/map_align.c:660-750) over the records of the last ma_tally, for the
@@ -786,6 +789,31 @@ class MiaHip:
         opt = lambda a: _ptr(a) if n else None
         self._chk(self._l.mia_hip_get_ma_damage(self._h, opt(pos5), opt(pos3), opt(keep), _ptr(hist), C.byref(orphans)))
         return pos5, pos3, keep, hist, n_mol.value, n_kept.value, orphans.value
+
+    def ma_mask(self, n5, n3, substitute=False, single_stranded=False):
+        """the end mask (ma_hip -E, -x, -f 96) over the records of the last ma_tally; n5, n3 in 0 .. 15, not both 0: the positions
+        masked at the reads' 5' and 3' ends, by the depth codes.  substitute=False trims (a record keeps columns first .. first + count
+        - 1, count 0 = emptied); substitute=True writes N over a T at the 5' end and an A (single_stranded: a T) at the 3' end, in the
+        read's orientation.  A dict: first[n], count[n], start[n] int32, col_off[n + 1] int64, seq, smp (uint8, cols_kept long),
+        pair_keep[n_ins] uint8, ins_pos[n_ins] int32, hist[2, 2, 16] int64 ([strand, end, k]: the zone columns that left, or became
+        N), emptied [forward, revcom], stripped, pairs_dropped, n_kept, cols_kept."""
+        if not hasattr(self._l, "mia_hip_ma_mask"):
+            raise RuntimeError("this libmia_hip has no mia_hip_ma_mask")
+        n_kept, cols_kept = C.c_int64(), C.c_int64()
+        self._chk(self._l.mia_hip_ma_mask(self._h, int(n5), int(n3), 1 if substitute else 0, 1 if single_stranded else 0, C.byref(n_kept), C.byref(cols_kept)))
+        n = getattr(self, "_ma_n", 0)                      # the records and pairs of the last ma_tally
+        n_ins = getattr(self, "_ma_n_ins", 0)
+        first, count, start = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        col_off = np.zeros(n + 1, dtype=np.int64)
+        seq, smp = np.zeros(cols_kept.value, dtype=np.uint8), np.zeros(cols_kept.value, dtype=np.uint8)
+        pair_keep, ins_pos = np.zeros(n_ins, dtype=np.uint8), np.zeros(n_ins, dtype=np.int32)
+        hist, scalars = np.zeros((2, 2, 16), dtype=np.int64), np.zeros(6, dtype=np.int64)
+        opt = lambda a: _ptr(a) if a.size else None
+        self._chk(self._l.mia_hip_get_ma_mask(self._h, opt(first), opt(count), opt(start), _ptr(col_off), opt(seq), opt(smp), cols_kept.value, opt(pair_keep),
+                                              opt(ins_pos), _ptr(hist), _ptr(scalars)))
+        return {"first": first, "count": count, "start": start, "col_off": col_off, "seq": seq, "smp": smp, "pair_keep": pair_keep, "ins_pos": ins_pos, "hist": hist,
+                "emptied": [int(scalars[0]), int(scalars[1])], "stripped": int(scalars[2]), "pairs_dropped": int(scalars[3]), "n_kept": int(scalars[4]),
+                "cols_kept": int(scalars[5])}
 
     def ins_tally(self):
         """(ins_off[L+1], ins_tally[slots][9]) of the insert columns, after consensus()."""

@@ -38,14 +38,15 @@
 #include "mia_ma_cols_kernels.h"
 #include "mia_ma_dedup_kernels.h"
 #include "mia_ma_damage_kernels.h"
+#include "mia_ma_mask_kernels.h"
 
 using namespace mia;
 
 // timed stages (HIP events on the context's stream around the kernel launches of that kind)
-enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_DAMAGE_HITS, STG_MA_DAMAGE_MOLECULES, STG_MA_PROFILE, STG_MA_DEDUP_KEYS, STG_MA_DEDUP_SORT, STG_MA_DEDUP_RUNS, STG_MA_DEDUP_NEXT, STG_MA_DEDUP_ANCHORS, STG_MA_DEDUP_CLUSTERS, STG_MA_TALLY, STG_MA_COLS, STG_MA_ENDS, STG_COUNT };
+enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_MASK_BOUNDS, STG_MA_MASK_LAYOUT, STG_MA_MASK_APPLY, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_DAMAGE_HITS, STG_MA_DAMAGE_MOLECULES, STG_MA_PROFILE, STG_MA_DEDUP_KEYS, STG_MA_DEDUP_SORT, STG_MA_DEDUP_RUNS, STG_MA_DEDUP_NEXT, STG_MA_DEDUP_ANCHORS, STG_MA_DEDUP_CLUSTERS, STG_MA_TALLY, STG_MA_COLS, STG_MA_ENDS, STG_COUNT };
 static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan",
                                                    "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select",
-                                                   "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_sam_layout",
+                                                   "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_mask_bounds", "k_ma_mask_layout", "k_ma_mask_apply", "k_ma_sam_layout",
                                                    "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs",
                                                    "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"};
 
@@ -269,7 +270,7 @@ struct mia_hip_ctx {
   DevBuf<unsigned long long> d_ma_ctl;
   // what the exports' calls found, per export (the big results are further down): mia_hip_ma_tally forgets all of it at once
   struct MaOut {
-    bool region_done = false, ace_done = false, sam_done = false, prof_done = false, ends_done = false, cols_done = false, damage_done = false;
+    bool region_done = false, ace_done = false, sam_done = false, prof_done = false, ends_done = false, cols_done = false, damage_done = false, mask_done = false;
     int32_t first = 0, last = -1; int64_t rows = 0, width = 0, ace_bytes = 0, sam_bytes = 0;
   } ma_out;
   // ... and for mia_hip_ma_ace: whether the job has an ACE export at all (GAPS, the records' columns), the running sum of ref->gaps,
@@ -311,6 +312,16 @@ struct mia_hip_ctx {
     DevBuf<int64_t> d_mate; DevBuf<uint32_t> d_hit; DevBuf<uint8_t> d_pos, d_keep; DevBuf<unsigned long long> d_bins;
     int64_t bins[MA_DMG_BINS] = {0};
   } damage;
+
+  // ... and mia_hip_ma_mask, which reads the tallied records alone: per record a1 | b1 of the bounds stage (lo preset to all ones, hi
+  // to 0), first | count | start' and col_off' of the layout, the new strings (padded to a multiple of 16), the pairs' fate, the scan's
+  // control words, and the 133 bins (ma_mask_body.h) on the device and, after the call, here.  All of it stays on the device until
+  // mia_hip_get_ma_mask; the next mia_hip_ma_tally invalidates it.
+  struct MaMask {
+    DevBuf<uint32_t> d_lohi; DevBuf<int32_t> d_rec, d_ipos; DevBuf<int64_t> d_off; DevBuf<char> d_seq, d_smp; DevBuf<uint8_t> d_pair_keep;
+    DevBuf<unsigned long long> d_ctl, d_bins;
+    int64_t bins[MA_MASK_BINS] = {0}, cols_kept = 0; int32_t mode = 0;
+  } mask;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------

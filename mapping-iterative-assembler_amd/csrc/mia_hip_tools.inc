@@ -694,6 +694,108 @@ extern "C" int mia_hip_get_ma_damage(mia_hip_ctx* ctx, uint8_t* pos5, uint8_t* p
   return MIA_HIP_OK;
 }
 
+// The end mask (ma_hip -E, -x, -f 96) of the records of the last mia_hip_ma_tally: see mia_ma_mask_kernels.h.  Everything it reads is on
+// the device already; the new record view stays there until mia_hip_get_ma_mask.
+extern "C" int mia_hip_ma_mask(mia_hip_ctx* ctx, int32_t n5, int32_t n3, int32_t mode, int32_t single_stranded, int64_t* n_kept, int64_t* cols_kept) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  ctx->ma_out.mask_done = false;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_mask"; return MIA_HIP_ERR_STATE; }
+  if (!ma_mask_args_ok(n5, n3, mode, single_stranded)) {
+    ctx->err = "ma_mask: n5 and n3 must lie in 0 .. 15 and not both be 0, the mode be 0 (trim) or 1 (N), and single_stranded go with mode 1";
+    return MIA_HIP_ERR_ARG;
+  }
+  if (ctx->ma_n > 0 && ctx->ma_cols < 0) { ctx->err = "ma_mask: col_off[0] of the tallied records is not 0"; return MIA_HIP_ERR_ARG; }
+  const int64_t n = ctx->ma_n, T = ctx->ma_cols, n_ins = ctx->ma_n_ins;
+  auto& mk = ctx->mask;
+  memset(mk.bins, 0, sizeof mk.bins);
+  mk.cols_kept = 0;
+  mk.mode = mode;
+  if (n > 0) {                                               // without records there is no launch and every result is zero
+    HIPCHK(hipSetDevice(ctx->device));
+    const int32_t n_wgs = (int32_t)ma_mask_layout_wgs(n);
+    // (the new strings are no longer than the old ones: sized before the layout is known, padded as the old ones are)
+    if (dev_ensure(ctx, mk.d_lohi, 2 * n) || dev_ensure(ctx, mk.d_rec, 3 * n) || dev_ensure(ctx, mk.d_off, n + 1) || dev_ensure(ctx, mk.d_seq, T + MA_REC_LANE) ||
+        dev_ensure(ctx, mk.d_smp, T + MA_REC_LANE) || dev_ensure(ctx, mk.d_pair_keep, n_ins + 1) || dev_ensure(ctx, mk.d_ipos, n_ins + 1) ||
+        dev_ensure(ctx, mk.d_ctl, (int64_t)MAR_STATE + n_wgs + 1) || dev_ensure(ctx, mk.d_bins, MA_MASK_BINS))
+      return MIA_HIP_ERR_NOMEM;
+    uint32_t *lo = (uint32_t*)mk.d_lohi, *hi = (uint32_t*)mk.d_lohi + n;
+    int32_t *first = (int32_t*)mk.d_rec, *count = (int32_t*)mk.d_rec + n, *start = (int32_t*)mk.d_rec + 2 * n;
+    HIPCHK(hipMemsetAsync(lo, 0xff, (size_t)n * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(hi, 0, (size_t)n * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(mk.d_bins, 0, (size_t)MA_MASK_BINS * 8, ctx->stream));
+    HIPCHK(hipMemsetAsync(mk.d_ctl, 0, ((size_t)MAR_STATE + (size_t)n_wgs) * 8, ctx->stream));
+    const MaProfView v{ma_records(ctx), T, nullptr, nullptr};
+    const int64_t wide = (int64_t)ctx->cus * MAM_WGS_PER_CU;
+    // persistent grids: the workgroups that are resident at once, or one per chunk when there are fewer
+    int64_t grid = ma_mask_chunks(T) < wide ? ma_mask_chunks(T) : wide;
+    if (grid < 1) grid = 1;                                  // (records that all lack columns: one workgroup that finds no chunk)
+    if (stage_launch(ctx, STG_MA_MASK_BOUNDS, k_ma_mask_bounds, dim3((unsigned)grid), dim3(MAM_THREADS), 0, ctx->stream, v, n5, n3, mode, single_stranded ? 1 : 0,
+                     lo, hi, (unsigned long long*)mk.d_bins))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    const MaMaskRecView rv{v, n5, n3, mode, lo, hi, first, count, start};
+    if (stage_launch(ctx, STG_MA_MASK_LAYOUT, k_ma_mask_layout, dim3((unsigned)n_wgs), dim3(MAM_THREADS), 0, ctx->stream, rv, n_wgs,
+                     (unsigned long long*)mk.d_ctl, (int64_t*)mk.d_off, (unsigned long long*)mk.d_bins))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    unsigned long long hdr[MAR_STATE] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(hdr, mk.d_ctl, sizeof hdr, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const int64_t new_T = (int64_t)hdr[MAR_ROWS];
+    if (new_T < 0 || new_T > T) { ctx->err = "ma_mask: the layout came back inconsistent"; return MIA_HIP_ERR_DEVICE; }
+    const MaMaskApplyView av{v, n5, n3, mode, single_stranded ? 1 : 0, first, (const int64_t*)mk.d_off, new_T};
+    const int64_t pieces = ma_mask_chunks(ma_mask_padded(new_T)), pair_wgs = (n_ins + MAM_THREADS - 1) / MAM_THREADS;
+    grid = pieces > pair_wgs ? pieces : pair_wgs;
+    if (grid > wide) grid = wide;
+    if (grid < 1) grid = 1;
+    if (stage_launch(ctx, STG_MA_MASK_APPLY, k_ma_mask_apply, dim3((unsigned)grid), dim3(MAM_THREADS), 0, ctx->stream, av, (const int32_t*)count, n_ins,
+                     (char*)mk.d_seq, (char*)mk.d_smp, (uint8_t*)mk.d_pair_keep, (int32_t*)mk.d_ipos, (unsigned long long*)mk.d_bins))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(mk.bins, mk.d_bins, (size_t)MA_MASK_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int b = 0; b < MA_MASK_HIST; b++) {                 // trim mode: the zone columns that left = all of them - those that stayed
+      mk.bins[b] -= mk.bins[MA_MASK_STAY + b];
+      if (mk.bins[b] < 0) { ctx->err = "ma_mask: the counts came back inconsistent"; return MIA_HIP_ERR_DEVICE; }
+    }
+    mk.cols_kept = new_T;
+  }
+  ctx->ma_out.mask_done = true;
+  if (n_kept) *n_kept = mk.bins[MA_MASK_KEPT];
+  if (cols_kept) *cols_kept = mk.cols_kept;
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_mask(mia_hip_ctx* ctx, int32_t* first, int32_t* count, int32_t* start, int64_t* col_off, char* seq, char* smp, int64_t cap_bytes,
+                                   uint8_t* pair_keep, int32_t* ins_pos, int64_t* hist, int64_t* scalars) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident || !ctx->ma_out.mask_done) { ctx->err = "ma_mask first"; return MIA_HIP_ERR_STATE; }
+  auto& mk = ctx->mask;
+  if ((seq || smp) && cap_bytes < mk.cols_kept) { ctx->err = "get_ma_mask: buffer too small"; return MIA_HIP_ERR_ARG; }
+  const int64_t n = ctx->ma_n, n_ins = ctx->ma_n_ins;
+  if (n > 0) {
+    HIPCHK(hipSetDevice(ctx->device));
+    auto down = [&](void* h, const void* d, size_t b) { return h && b ? hipMemcpyAsync(h, d, b, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
+    HIPCHK(down(first, mk.d_rec, (size_t)n * 4));
+    HIPCHK(down(count, (int32_t*)mk.d_rec + n, (size_t)n * 4));
+    HIPCHK(down(start, (int32_t*)mk.d_rec + 2 * n, (size_t)n * 4));
+    HIPCHK(down(col_off, mk.d_off, (size_t)(n + 1) * 8));
+    HIPCHK(down(seq, mk.d_seq, (size_t)mk.cols_kept));
+    HIPCHK(down(smp, mk.d_smp, (size_t)mk.cols_kept));
+    HIPCHK(down(pair_keep, mk.d_pair_keep, (size_t)n_ins));
+    HIPCHK(down(ins_pos, mk.d_ipos, (size_t)n_ins * 4));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  } else if (col_off) {
+    col_off[0] = 0;
+  }
+  if (hist) memcpy(hist, mk.bins, sizeof(int64_t) * MA_MASK_HIST);
+  if (scalars) {
+    scalars[0] = mk.bins[MA_MASK_EMPTIED]; scalars[1] = mk.bins[MA_MASK_EMPTIED + 1]; scalars[2] = mk.bins[MA_MASK_STRIPPED];
+    scalars[3] = mk.bins[MA_MASK_PAIRS]; scalars[4] = mk.bins[MA_MASK_KEPT]; scalars[5] = mk.cols_kept;
+  }
+  return MIA_HIP_OK;
+}
+
 extern "C" int mia_hip_get_ins_tally(mia_hip_ctx* ctx, int32_t* ins_off, int32_t* ins_tally, int64_t cap_slots, int64_t* n_slots) {
   if (!ctx) return MIA_HIP_ERR_ARG;
   if (!ctx->tallied || !ctx->consensus_done) { ctx->err = "consensus first"; return MIA_HIP_ERR_STATE; }

@@ -19,6 +19,10 @@
 // positions of the 5' end, a G read as A -- -S: a C read as T -- within N of the 3' end; -e says which ends must show it): it runs behind
 // -u and in front of everything else, the per-record decision is made on the GPU (mia_hip_ma_damage) over the records of a tally of the
 // file as it stands, and the records that are not kept leave as for -u.  -f 95 prints the molecules' damage classes.
+// -E n5[,n3] masks the reads' ends behind -u and -D and in front of everything else ("End mask"): the columns whose depth code
+// lies within n5 positions of the read's 5' end or n3 of its 3' end leave the record (with -x: a T there at the 5' end, an A -- -S: a T --
+// at the 3' end becomes N), so that the consensus is not called from deaminated bases.  The new record view is made on the GPU
+// (mia_hip_ma_mask) and put back into the file here (host/maln_mask.h); -f 96 prints what left.
 // No CPU fallback.
 #include <ctype.h>
 #include <float.h>
@@ -37,6 +41,7 @@
 #include "../../include/mia_hip.h"
 #include "maln_text.h"
 #include "maln_dedup.h"
+#include "maln_mask.h"
 #include "../csrc/ma_ace_body.h"
 #include "../csrc/ma_sam_body.h"
 #include "../csrc/ma_profile_body.h"
@@ -44,6 +49,7 @@
 #include "../csrc/ma_cols_body.h"
 #include "../csrc/ma_dedup_body.h"
 #include "../csrc/ma_damage_body.h"
+#include "../csrc/ma_mask_body.h"
 
 namespace {
 
@@ -52,12 +58,14 @@ using namespace maln_text;
 typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92, 93 or 95>\n   -R <REGION_START:REGION_END>\n"
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92, 93, 95 or 96>\n   -R <REGION_START:REGION_END>\n"
          "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
          "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 42, 9, 91, 92, 93 and 95)\n"
          "   -u remove duplicate molecules first\n   -t <tolerance of -u in columns, 0 .. 100, default 0>\n"
          "   -D <N: keep only deaminated fragments, a hit within N = 1 .. 15 positions of a read end>\n"
-         "   -e <ends of -D that must show a hit: 5, 3, any (default) or both>\n   -S single-stranded library (-D, format 95)\n"
+         "   -e <ends of -D that must show a hit: 5, 3, any (default) or both>\n   -S single-stranded library (-D, format 95, -x)\n"
+         "   -E <n5[,n3]: mask n5 positions at the reads' 5' end and n3 (default n5) at their 3' end, 0 .. 15, not both 0>\n"
+         "   -x with -E: do not trim, write N over the bases deamination makes\n"
          "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
          "(-f 1 clustalw, the default; -f 2 one line each plus coverage), the per-column table (-f 41 all positions, -f 4\n"
          "positions that differ from the reference), the assembled sequence (-f 5), and the reference, the consensus and every\n"
@@ -88,7 +96,15 @@ void help() {
          "(the default) for either.  What is not kept leaves as for -u, and the consensus is called from the deaminated fragments alone\n"
          "(-D 1 -e 3 -f 9 prints the 5' profile of the fragments deaminated at their 3' end).  The decision is made on the MI355X.\n"
          "-f 95 prints the damage classes of the file as it stands behind -u and -D: for N = 1 .. 15 the molecules with a 5' hit within N,\n"
-         "with a 3' hit within N, with both and with either, on the forward strand, the reverse strand and both.  Format 3 (format 2's summary plus\n"
+         "with a 3' hit within N, with both and with either, on the forward strand, the reverse strand and both.\n"
+         "-E n5[,n3] masks the reads' ends behind -u and -D and in front of everything else: a column belongs to a read's 5' end when the\n"
+         "position mia scored it at (1 .. 15 from either end, in the read's orientation) is at most n5, to its 3' end when it is at most n3.\n"
+         "Those columns at either end of a record leave it, with the '-' columns next to them; START, END and the inserts' positions move,\n"
+         "an insert in front of the new first column leaves, a record that keeps no base leaves the file, GAPS shrinks as for -u.  With -x\n"
+         "nothing leaves: a T at the 5' end and an A (-S: a T) at the 3' end, in the read's orientation, become N.  Every format and -m see\n"
+         "the masked file; formats 92, 93 and 95 describe real fragment ends and refuse -E.  The mask is made on the MI355X.  -f 96 prints\n"
+         "what the mask took: per position 1 .. 15 the columns removed (-x: set to N) at the 5' and 3' ends of forward and reverse records.\n"
+         "Format 3 (format 2's summary plus\n"
          "a table of coverage and of the records that start and end at every column) is outside the accelerated path.\n");
 }
 
@@ -380,10 +396,12 @@ int main(int argc, char* argv[]) {
   long tolerance = 0, damage_n = 0;
   bool damage = false, ends_given = false, single_stranded = false;
   int ends_mode = mia::MA_DMG_ANY;
+  bool mask = false, mask_ok = false, substitute = false;
+  long mask_n5 = 0, mask_n3 = 0;
   double score_int = -1.0, score_slo = -1.0, alpha = 1.0;
   int ich;
-  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount>, -A, -u, -t <tolerance>, -D <N>, -e <ends> and -S
-  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:Aut:D:e:S")) != -1) {
+  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount>, -A, -u, -t <tolerance>, -D <N>, -e <ends>, -S, -E <n5[,n3]> and -x
+  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:Aut:D:e:SE:x")) != -1) {
     switch (ich) {
       case 'I': assign_id = optarg; id_assigned = true; break;
       case 'c': cons_scheme = atoi(optarg); any_arg = true; break;
@@ -407,12 +425,14 @@ int main(int argc, char* argv[]) {
         ends_mode = !strcmp(optarg, "any") ? mia::MA_DMG_ANY : !strcmp(optarg, "5") ? mia::MA_DMG_5 : !strcmp(optarg, "3") ? mia::MA_DMG_3 : !strcmp(optarg, "both") ? mia::MA_DMG_BOTH : -1;
         break;
       case 'S': single_stranded = true; break;
+      case 'E': mask = true; mask_ok = parse_mask_ends(optarg, &mask_n5, &mask_n3); any_arg = true; break;
+      case 'x': substitute = true; break;
       default: help(); exit(0);
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 42 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93 && out_format != 95) {
-    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 42, 8, 9, 91, 92, 93 and 95, which the reference does not have); use the reference's ma\n", out_format);
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 42 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93 && out_format != 95 && out_format != 96) {
+    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 42, 8, 9, 91, 92, 93, 95 and 96, which the reference does not have); use the reference's ma\n", out_format);
     exit(1);
   }
   if (out_format == 91 && !mia::ma_prof_alpha_ok(alpha)) {
@@ -422,7 +442,17 @@ int main(int argc, char* argv[]) {
   if (tol_given && !dedup) { fprintf(stderr, "ma_hip: -t is the tolerance of -u, which is not given\n"); exit(1); }
   if (tolerance < 0 || tolerance > mia::MA_DEDUP_MAX_TOL) { fprintf(stderr, "ma_hip: -t must be a whole number from 0 to %d\n", mia::MA_DEDUP_MAX_TOL); exit(1); }
   if (ends_given && !damage) { fprintf(stderr, "ma_hip: -e names the ends of -D, which is not given\n"); exit(1); }
-  if (single_stranded && !damage && out_format != 95) { fprintf(stderr, "ma_hip: -S is the library type of -D and of -f 95, neither of which is given\n"); exit(1); }
+  if (substitute && !mask) { fprintf(stderr, "ma_hip: -x is the substitution mode of -E, which is not given\n"); exit(1); }
+  if (out_format == 96 && !mask) { fprintf(stderr, "ma_hip: -f 96 is the report of -E, which is not given\n"); exit(1); }
+  if (mask && (!mask_ok || !mia::ma_mask_args_ok((int)mask_n5, (int)mask_n3, mia::MA_MASK_TRIM, 0))) {
+    fprintf(stderr, "ma_hip: -E must be n5 or n5,n3: whole numbers from 0 to %d, not both 0\n", mia::MA_MASK_MAX_POS);
+    exit(1);
+  }
+  if (mask && (out_format == 92 || out_format == 93 || out_format == 95)) {
+    fprintf(stderr, "ma_hip: -f %d describes real fragment ends and cannot follow -E, which masks them\n", out_format);
+    exit(1);
+  }
+  if (single_stranded && !damage && out_format != 95 && !substitute) { fprintf(stderr, "ma_hip: -S is the library type of -D and of -f 95, neither of which is given\n"); exit(1); }
   if (damage && !mia::ma_dmg_pos_ok((int)(damage_n < 0 || damage_n > 1000 ? -1 : damage_n))) {
     fprintf(stderr, "ma_hip: -D must be a whole number from 1 to %d\n", mia::MA_DMG_MAX_POS);
     exit(1);
@@ -472,6 +502,25 @@ int main(int argc, char* argv[]) {
     if (mia_hip_get_ma_damage(g, nullptr, nullptr, keep.data(), nullptr, nullptr) != MIA_HIP_OK) die(g, "get_ma_damage");
     keep.resize(m.rec.size());
     remove_records(&m, keep);
+  }
+  MaskResult masked;
+  const int64_t mask_n_in = (int64_t)m.rec.size();
+  if (mask) {
+    // the end mask, behind -u and -D and in front of everything else: the new record view is made on the device from a tally of the
+    // file as it stands, put back into the file here, and what is emptied leaves as for -u
+    tally_file();
+    const int64_t n_rec = (int64_t)m.start.size(), n_pairs = (int64_t)m.ins_record.size();
+    int64_t cols_kept = 0;
+    if (mia_hip_ma_mask(g, (int32_t)mask_n5, (int32_t)mask_n3, substitute ? mia::MA_MASK_N : mia::MA_MASK_TRIM, substitute && single_stranded ? 1 : 0, nullptr,
+                        &cols_kept) != MIA_HIP_OK)
+      die(g, "ma_mask");
+    masked.first.resize((size_t)n_rec + 1); masked.count.resize((size_t)n_rec + 1); masked.start.resize((size_t)n_rec + 1);
+    masked.col_off.resize((size_t)n_rec + 1); masked.pair_keep.resize((size_t)n_pairs + 1); masked.ins_pos.resize((size_t)n_pairs + 1);
+    masked.seq.assign((size_t)cols_kept + 1, '\0'); masked.smp.assign((size_t)cols_kept + 1, '\0');
+    if (mia_hip_get_ma_mask(g, masked.first.data(), masked.count.data(), masked.start.data(), masked.col_off.data(), &masked.seq[0], &masked.smp[0], cols_kept,
+                            masked.pair_keep.data(), masked.ins_pos.data(), masked.hist, masked.scalars) != MIA_HIP_OK)
+      die(g, "get_ma_mask");
+    apply_mask(&m, masked, substitute);
   }
   if (out_format == 8 && !mia::ma_sam_gaps_ok(m.gaps.data(), m.L)) {
     fprintf(stderr, "ma_hip: %s has no SAM export: its GAPS line holds a negative value\n", ma_in_fn.c_str());
@@ -525,6 +574,11 @@ int main(int argc, char* argv[]) {
     if (mia_hip_get_ma_ends(g, ctx_count.data(), len_count.data(), &halves) != MIA_HIP_OK) die(g, "get_ma_ends");
     if (out_format == 92) ends_table(n_used, n5, n3, ctx_count.data());
     else lengths_table(len_count.data(), halves);
+    return finish(g);
+  }
+  if (out_format == 96) {
+    mask_report(stdout, mask_n_in, masked, substitute, substitute && single_stranded);
+    fflush(stdout);
     return finish(g);
   }
   if (out_format == 95) {

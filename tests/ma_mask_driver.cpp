@@ -1,0 +1,193 @@
+// Host caller of the shared code of the end mask (csrc/ma_mask_body.h: what the kernels of mia_ma_mask_kernels.h run per lane):
+// ma_mask_stretch over every stretch of 16 flat positions, into lo / hi by minimum and maximum as the device's atomics do, then
+// ma_mask_record over every record and an exclusive sum, then ma_mask_gather over every stretch of the new layout and ma_mask_pair
+// over every listed pair.  Every array ends where the device's may end -- SEQ and SMP, old and new, on the next multiple of 16 behind
+// their last character, everything else on its last element -- and is heap memory of its own, so that AddressSanitizer sees every
+// index.  Beside it a loop record by record and column by column that shares ma_mask_zone and ma_mask_substituted alone; the two must
+// agree.  The results are printed for the test to compare with its own restatement (tests/ma_mask_ref.py), which shares nothing.
+//
+//   ma_mask_driver <file> <n5> <n3> <mode> <single_stranded>
+//   file: "n T n_ins", ">" + SEQ, ">" + SMP (flat), then n lines "start rc col_off_end" and n_ins lines "record pos"
+//   output: first, count, start, col_off, ">" + SEQ', ">" + SMP', pair_keep, ins_pos, hist, scalars -- a line each
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../mapping-iterative-assembler_amd/csrc/ma_mask_body.h"
+
+using namespace mia;
+
+template <class T>
+struct Exact {                              // exactly `count` elements on the heap (none: a null pointer)
+  T* p = nullptr;
+  explicit Exact(size_t count, size_t align = alignof(T)) {
+    if (!count) return;
+    const size_t bytes = count * sizeof(T);                  // (an aligned block's size is a multiple of its alignment: the caller's)
+    p = (T*)(align > alignof(T) ? aligned_alloc(align, bytes) : malloc(bytes));
+    if (!p) { fprintf(stderr, "out of memory\n"); exit(2); }
+    memset(p, 0, bytes);
+  }
+  ~Exact() { free(p); }
+  Exact(const Exact&) = delete;
+  Exact& operator=(const Exact&) = delete;
+};
+
+static std::string line_of(FILE* f) {
+  std::string s;
+  int ch;
+  while ((ch = fgetc(f)) != EOF && ch != '\n') s += (char)ch;
+  return s;
+}
+
+static size_t padded(long long T) { return (size_t)(T + MA_MASK_LANE - 1) / MA_MASK_LANE * MA_MASK_LANE; }
+
+template <class T>
+static void print_row(const char* name, const T* p, long long count) {
+  printf("%s", name);
+  for (long long k = 0; k < count; k++) printf(" %lld", (long long)p[k]);
+  printf("\n");
+}
+
+int main(int argc, char** argv) {
+  if (argc < 6) { fprintf(stderr, "usage: ma_mask_driver <file> <n5> <n3> <mode> <single_stranded>\n"); return 2; }
+  const int n5 = atoi(argv[2]), n3 = atoi(argv[3]), mode = atoi(argv[4]), ss = atoi(argv[5]);
+  if (!ma_mask_args_ok(n5, n3, mode, ss)) { fprintf(stderr, "bad arguments\n"); return 2; }
+  FILE* f = fopen(argv[1], "r");
+  if (!f) { perror(argv[1]); return 2; }
+  long long n = 0, T = 0, n_ins = 0;
+  if (fscanf(f, "%lld %lld %lld\n", &n, &T, &n_ins) != 3) { fprintf(stderr, "bad header\n"); return 2; }
+  const std::string seq_s = line_of(f).substr(1), smp_s = line_of(f).substr(1);
+  if ((long long)seq_s.size() != T || (long long)smp_s.size() != T) { fprintf(stderr, "bad strings\n"); return 2; }
+  Exact<char> seq(padded(T), 16), smp(padded(T), 16);
+  Exact<int32_t> start((size_t)n), first((size_t)n), count((size_t)n), new_start((size_t)n), ins_record((size_t)n_ins), ins_pos((size_t)n_ins), new_pos((size_t)n_ins);
+  Exact<uint8_t> revcom((size_t)n), pair_keep((size_t)n_ins);
+  Exact<int64_t> col_off((size_t)n + 1), new_off((size_t)n + 1);
+  Exact<uint32_t> lo((size_t)n), hi((size_t)n);
+  if (T) { memcpy(seq.p, seq_s.data(), (size_t)T); memcpy(smp.p, smp_s.data(), (size_t)T); }
+  for (long long r = 0; r < n; r++) {
+    long long s, rc, e;
+    if (fscanf(f, "%lld %lld %lld", &s, &rc, &e) != 3) { fprintf(stderr, "bad record %lld\n", r); return 2; }
+    start.p[r] = (int32_t)s; revcom.p[r] = (uint8_t)rc; col_off.p[r + 1] = e;
+  }
+  for (long long e = 0; e < n_ins; e++) {
+    long long r, p;
+    if (fscanf(f, "%lld %lld", &r, &p) != 2 || r < 0 || r >= n) { fprintf(stderr, "bad pair %lld\n", e); return 2; }
+    ins_record.p[e] = (int32_t)r; ins_pos.p[e] = (int32_t)p;
+  }
+  fclose(f);
+  if (n == 0) {                             // the library launches nothing
+    printf("first\ncount\nstart\ncol_off 0\n>\n>\npair_keep\nins_pos\n");
+    std::vector<int64_t> zero(MA_MASK_HIST, 0);
+    print_row("hist", zero.data(), MA_MASK_HIST);
+    print_row("scalars", zero.data(), 6);
+    return 0;
+  }
+  std::vector<int32_t> rec_ins_v, ins_list_v;
+  ma_list_pairs(n, n_ins, ins_record.p, ins_pos.p, &rec_ins_v, &ins_list_v);
+  Exact<int32_t> rec_ins((size_t)n + 1), ins_list((size_t)n_ins);
+  memcpy(rec_ins.p, rec_ins_v.data(), ((size_t)n + 1) * 4);
+  if (n_ins) memcpy(ins_list.p, ins_list_v.data(), (size_t)n_ins * 4);
+  const MaProfView v(n, T, 1, start.p, revcom.p, col_off.p, seq.p, smp.p, nullptr, nullptr);
+  std::vector<int64_t> bins(MA_MASK_BINS, 0);
+  auto add = [&](int first_bin, int size) {
+    return [&bins, first_bin, size](int bin) {
+      if (bin < first_bin || bin >= first_bin + size) { fprintf(stderr, "a bin out of range\n"); exit(1); }
+      bins[(size_t)bin]++;
+    };
+  };
+  // the bounds stage: stretch by stretch, last stretch first (minimum and maximum do not care)
+  for (long long r = 0; r < n; r++) { lo.p[r] = MA_MASK_NO_COLUMN; hi.p[r] = 0; }
+  std::vector<int> direct((size_t)n, 0), shared((size_t)n, 0);
+  for (long long base = (long long)padded(T) - MA_MASK_LANE; base >= 0; base -= MA_MASK_LANE)
+    ma_mask_stretch(
+        v, n5, n3, mode, ss != 0, base,
+        [&](int64_t r, uint32_t a1, uint32_t b1, bool whole) {
+          if (r < 0 || r >= n || mode != MA_MASK_TRIM) { fprintf(stderr, "a call out of range\n"); exit(1); }
+          if (whole) { direct[(size_t)r]++; lo.p[r] = a1; hi.p[r] = b1; return; }
+          shared[(size_t)r]++;
+          if (a1 < lo.p[r]) lo.p[r] = a1;
+          if (b1 > hi.p[r]) hi.p[r] = b1;
+        },
+        add(0, MA_MASK_HIST));
+  for (long long r = 0; r < n; r++)
+    if (direct[(size_t)r] > 1 || (direct[(size_t)r] && shared[(size_t)r])) { fprintf(stderr, "record %lld: a plain store beside another lane's\n", r); return 1; }
+  // the layout stage
+  const MaMaskRecView rv{v, n5, n3, mode, lo.p, hi.p, first.p, count.p, new_start.p};
+  std::vector<int64_t> len((size_t)n, 0);
+  for (long long r = n - 1; r >= 0; r--) len[(size_t)r] = ma_mask_record(rv, r, add(MA_MASK_EMPTIED, MA_MASK_BINS - MA_MASK_EMPTIED));
+  for (long long r = 0; r < n; r++) new_off.p[r + 1] = new_off.p[r] + len[(size_t)r];
+  const long long new_T = new_off.p[n];
+  // the apply stage
+  Exact<char> new_seq(padded(new_T), 16), new_smp(padded(new_T), 16);
+  const MaMaskApplyView av{v, n5, n3, mode, ss, first.p, new_off.p, new_T};
+  std::vector<int64_t> stay(MA_MASK_HIST, 0);                // the zone columns that stay: taken off the bounds stage's count
+  for (long long base = (long long)padded(new_T) - MA_MASK_LANE; base >= 0; base -= MA_MASK_LANE) {
+    MaRecWord so, mo;
+    ma_mask_gather(av, base, &so, &mo, [&](int bin) {
+      if (bin < 0 || bin >= MA_MASK_HIST || mode != MA_MASK_TRIM) { fprintf(stderr, "a bin out of range\n"); exit(1); }
+      stay[(size_t)bin]++;
+    });
+    memcpy(new_seq.p + base, &so, sizeof so);
+    memcpy(new_smp.p + base, &mo, sizeof mo);
+  }
+  for (int b = 0; b < MA_MASK_HIST; b++) { bins[(size_t)b] -= stay[(size_t)b]; if (bins[(size_t)b] < 0) { fprintf(stderr, "more columns stay than there are\n"); return 1; } }
+  for (long long k = 0; k < n_ins; k++) {
+    long long r = 0;
+    while (rec_ins.p[r + 1] <= k) r++;
+    const int32_t e = ins_list.p[k];
+    const bool stays = ma_mask_pair(mode, first.p[r], count.p[r], ins_pos.p[e], &new_pos.p[e]);
+    pair_keep.p[e] = stays ? 1 : 0;
+    if (!stays && count.p[r] > 0) bins[MA_MASK_PAIRS]++;
+  }
+  for (size_t x = (size_t)new_T; x < padded(new_T); x++)
+    if (new_seq.p[x] || new_smp.p[x]) { fprintf(stderr, "the padding is not zero\n"); return 1; }
+  // record by record, column by column
+  std::vector<int64_t> hist2(MA_MASK_HIST, 0);
+  long long stripped = 0, emptied[2] = {0, 0};
+  for (long long r = 0; r < n; r++) {
+    const int64_t o0 = col_off.p[r], cols = col_off.p[r + 1] - o0;
+    const bool rc = revcom.p[r] != 0;
+    if (mode == MA_MASK_N) {
+      if (first.p[r] != 0 || count.p[r] != cols || new_off.p[r] != o0) { fprintf(stderr, "record %lld: the layout moved\n", r); return 1; }
+      for (int64_t c = 0; c < cols; c++) {
+        const int zone = ma_mask_zone(smp.p[o0 + c], rc, n5, n3);
+        const bool sub = zone && ma_mask_substituted(seq.p[o0 + c], zone, rc, ss != 0);
+        if (sub) hist2[(size_t)ma_mask_hist_bin(rc, zone)]++;
+        if (new_seq.p[o0 + c] != (sub ? 'N' : seq.p[o0 + c]) || new_smp.p[o0 + c] != smp.p[o0 + c]) { fprintf(stderr, "record %lld column %lld: wrong character\n", r, (long long)c); return 1; }
+      }
+      continue;
+    }
+    int64_t a = 0, b = cols;
+    while (a < cols && ma_mask_zone(smp.p[o0 + a], rc, n5, n3)) a++;
+    while (b > a && ma_mask_zone(smp.p[o0 + b - 1], rc, n5, n3)) b--;
+    while (a < b && seq.p[o0 + a] == '-') a++;
+    while (b > a && seq.p[o0 + b - 1] == '-') b--;
+    for (int64_t c = 0; c < cols; c++) {
+      if (a < b && c >= a && c < b) continue;
+      const int zone = ma_mask_zone(smp.p[o0 + c], rc, n5, n3);
+      if (zone) hist2[(size_t)ma_mask_hist_bin(rc, zone)]++; else stripped++;
+    }
+    if (a >= b) { emptied[rc ? 1 : 0]++; a = b = 0; }
+    if (first.p[r] != a || count.p[r] != b - a) { fprintf(stderr, "record %lld: stretches %d %d, columns %lld %lld\n", r, first.p[r], count.p[r], (long long)a, (long long)(b - a)); return 1; }
+    for (int64_t c = a; c < b; c++)
+      if (new_seq.p[new_off.p[r] + c - a] != seq.p[o0 + c] || new_smp.p[new_off.p[r] + c - a] != smp.p[o0 + c]) { fprintf(stderr, "record %lld column %lld: wrong character\n", r, (long long)c); return 1; }
+  }
+  for (int b = 0; b < MA_MASK_HIST; b++)
+    if (bins[(size_t)b] != hist2[(size_t)b]) { fprintf(stderr, "hist bin %d: stretches %lld, columns %lld\n", b, (long long)bins[(size_t)b], (long long)hist2[(size_t)b]); return 1; }
+  if (bins[MA_MASK_STRIPPED] != stripped || bins[MA_MASK_EMPTIED] != emptied[0] || bins[MA_MASK_EMPTIED + 1] != emptied[1]) { fprintf(stderr, "scalars differ\n"); return 1; }
+  print_row("first", first.p, n);
+  print_row("count", count.p, n);
+  print_row("start", new_start.p, n);
+  print_row("col_off", new_off.p, n + 1);
+  printf(">%.*s\n>%.*s\n", (int)new_T, new_T ? new_seq.p : "", (int)new_T, new_T ? new_smp.p : "");
+  print_row("pair_keep", pair_keep.p, n_ins);
+  print_row("ins_pos", new_pos.p, n_ins);
+  print_row("hist", bins.data(), MA_MASK_HIST);
+  const int64_t scalars[6] = {bins[MA_MASK_EMPTIED], bins[MA_MASK_EMPTIED + 1], bins[MA_MASK_STRIPPED], bins[MA_MASK_PAIRS], bins[MA_MASK_KEPT], new_T};
+  print_row("scalars", scalars, 6);
+  return 0;
+}
