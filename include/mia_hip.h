@@ -279,8 +279,13 @@ int mia_hip_trim(mia_hip_ctx *ctx, const char *adapter, int64_t n_reads, const c
                  uint8_t *trimmed, int32_t *trim_point);
 
 /* reads of the most recent mia_hip_trim call whose best path held a gap of 63 or more and that were therefore
- * re-run by the exact scalar kernel (diagnostic; results are identical either way) */
+ * re-run by the exact scalar kernel (diagnostic; results are identical either way); 0 after a call with n_reads = 0.
+ * The re-run takes 4 096 reads at a time on one scratch of at most 0.55 GB, however many reads need it. */
 int mia_hip_trim_stats(mia_hip_ctx *ctx, int64_t *exact_reruns);
+
+/* how the most recent mia_hip_trim call re-ran those reads: launches of the exact kernel and bytes of the one scratch they
+ * shared (both 0 without re-runs): at most 4 096 reads' worth, (adapter bases * 256 + 1 280) * 4 bytes each, however many reads */
+int mia_hip_trim_rerun_stats(mia_hip_ctx *ctx, int64_t *launches, int64_t *scratch_bytes);
 
 /* ---- ma: reports from a .maln ------------------------------------------ */
 

@@ -92,6 +92,8 @@ def _load(path=None):
     lib.mia_hip_score_cut_from_sums.argtypes = [vp, P(C.c_double), P(C.c_double)]
     lib.mia_hip_score_cut_from_sums.restype = C.c_int
     lib.mia_hip_trim_stats.argtypes = [vp, P(C.c_int64)]
+    if hasattr(lib, "mia_hip_trim_rerun_stats"):  # (MIA_HIP_LIB may name an older build, for A/B timing)
+        lib.mia_hip_trim_rerun_stats.argtypes = [vp, P(C.c_int64), P(C.c_int64)]
     lib.mia_hip_get_ins_tally.argtypes = [vp, vp, vp, C.c_int64, P(C.c_int64)]
     if hasattr(lib, "mia_hip_ma_region"):         # (MIA_HIP_LIB may name an older build, for A/B timing)
         lib.mia_hip_ma_region.argtypes = [vp, C.c_int32, C.c_int32, P(C.c_int64), P(C.c_int64)]
@@ -164,7 +166,7 @@ def exported_symbols():
             "mia_hip_upload_reads", "mia_hip_pass1", "mia_hip_realign", "mia_hip_align_windows", "mia_hip_get_alignments", "mia_hip_get_scripts", "mia_hip_cull",
             "mia_hip_get_dropped", "mia_hip_set_slot_dropped", "mia_hip_score_cut", "mia_hip_num_records",
             "mia_hip_tally", "mia_hip_tally_buffers", "mia_hip_ins_events", "mia_hip_set_ins_events",
-            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_ma_mask", "mia_hip_get_ma_mask", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
+            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_ma_mask", "mia_hip_get_ma_mask", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_trim_rerun_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
             "mia_hip_get_record_params", "mia_hip_set_read_base", "mia_hip_links", "mia_hip_set_links", "mia_hip_link_lengths",
             "mia_hip_finish_links", "mia_hip_plain_stats", "mia_hip_score_sums",
             "mia_hip_score_cut_from_sums", "mia_hip_stage_stats", "mia_hip_measure_peaks", "mia_hip_measure_issue", "mia_hip_set_tally", "mia_hip_iterate", "mia_hip_set_stage_mask", "mia_hip_comm_unique_id", "mia_hip_comm_init", "mia_hip_comm_destroy",
@@ -884,6 +886,12 @@ class MiaHip:
         n = C.c_int64()
         self._chk(self._l.mia_hip_trim_stats(self._h, C.byref(n)))
         return n.value
+
+    def trim_rerun_stats(self):
+        """(launches of the exact kernel, bytes of their scratch) of the last trim call"""
+        a, b = C.c_int64(), C.c_int64()
+        self._chk(self._l.mia_hip_trim_rerun_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def pass1_time(self):
         ms = C.c_double()

@@ -261,6 +261,8 @@ struct mia_hip_ctx {
   double pass1_ms = 0; int64_t pass1_filtered = 0, pass1_anchored = 0;   // reads of the last pass-1 call that the diagonal filter decided
   double myers_kernel_ms = 0; bool myers_no_lanes = false, myers_no_ond = false;   // the kernels of the last mia_hip_myers call (HIP events)
   int64_t trim_escapes = 0;   // reads of the last mia_hip_trim call that took the exact scalar path
+  int64_t trim_launches = 0, trim_scratch_bytes = 0;   // ... in how many k_trim_wide launches, on how large a scratch
+  bool trim_exact = false;    // (alt build) every read of a mia_hip_trim call is re-run by the exact scalar kernel
   // the records of the last mia_hip_ma_tally stay on the device for mia_hip_ma_region: start, col_off, seq, the INS_POS pairs (and
   // which pairs each record owns), ref->gaps; the region's column map, selected records and text
   bool ma_resident = false; int64_t ma_n = 0, ma_n_ins = 0; int32_t ma_L = 0;
@@ -374,6 +376,8 @@ static void read_alt_switches(mia_hip_ctx* ctx) {
   // Myers
   if (on("MIA_HIP_MYERS_NO_LANES")) ctx->myers_no_lanes = true;                    // every pair through k_myers
   if (on("MIA_HIP_MYERS_NO_OND")) ctx->myers_no_ond = true;    // no O(ND) kernel
+  // trimming
+  if (on("MIA_HIP_TRIM_EXACT")) ctx->trim_exact = true;        // every read through k_trim_wide, after k_trim has run
   // profiling: results are wrong on purpose
   if (const char* v = alt_env("MIA_HIP_DEBUG_SKIP")) ctx->dbg = (uint32_t)atoi(v);                  // bits: see the kernels' dbg tests
   if (const char* v = alt_env("MIA_HIP_BX_DEBUG")) ctx->bx_dbg = (uint32_t)atoi(v);                 // 1 no traceback, 2 one DP row, 4 no values launch, 8 no trace launch, ...

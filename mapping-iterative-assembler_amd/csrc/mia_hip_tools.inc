@@ -8,7 +8,7 @@ extern "C" int mia_hip_trim(mia_hip_ctx* ctx, const char* adapter, int64_t n, co
   const int len2 = (int)strlen(adapter);
   if (len2 < 1 || len2 > MAX_ADAPTER) { ctx->err = "adapter length outside 1..127"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
-  if (n == 0) return MIA_HIP_OK;
+  if (n == 0) { ctx->trim_escapes = ctx->trim_launches = ctx->trim_scratch_bytes = 0; return MIA_HIP_OK; }
   for (int64_t i = 0; i < n; i++) {
     const int64_t l = offsets[i + 1] - offsets[i];
     if (l < 1 || l > MIA_HIP_MAX_READ) { ctx->err = "read length outside 1..256"; return MIA_HIP_ERR_ARG; }
@@ -58,18 +58,24 @@ extern "C" int mia_hip_trim(mia_hip_ctx* ctx, const char* adapter, int64_t n, co
   }
   if (e == hipSuccess) e = hipMemcpyAsync(status.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  // gaps of 63 or more on the optimal path: exact scalar re-run of those reads
+  // gaps of 63 or more on the optimal path: exact scalar re-run of those reads (MIA_HIP_TRIM_EXACT of the alt build: of every read),
+  // TRIM_EXACT_PIECE reads per launch on one scratch, so that a batch full of such reads needs 0.55 GB at 127 adapter bases and no more
   std::vector<int32_t> esc;
+  int64_t launches = 0, scratch_bytes = 0;
   if (e == hipSuccess)
-    for (int64_t i = 0; i < n; i++) if (status[(size_t)i] != ST_OK) esc.push_back((int32_t)i);
+    for (int64_t i = 0; i < n; i++) if (status[(size_t)i] != ST_OK || ctx->trim_exact) esc.push_back((int32_t)i);
   if (e == hipSuccess && !esc.empty()) {
-    const int64_t words = (int64_t)len2 * MAX_READ + 5 * (int64_t)MAX_READ;
-    if (dev_alloc(ctx, d_list, (int64_t)esc.size()) || dev_alloc(ctx, d_scratch, words * (int64_t)esc.size())) return MIA_HIP_ERR_NOMEM;
+    const int64_t words = (int64_t)len2 * MAX_READ + 5 * (int64_t)MAX_READ, total = (int64_t)esc.size();
+    const int64_t piece = total < TRIM_EXACT_PIECE ? total : TRIM_EXACT_PIECE;
+    if (dev_alloc(ctx, d_list, total) || dev_alloc(ctx, d_scratch, words * piece)) return MIA_HIP_ERR_NOMEM;
+    scratch_bytes = words * piece * (int64_t)sizeof(int32_t);
     up(d_list, esc.data(), esc.size() * 4);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_trim_wide, dim3((unsigned)((esc.size() + 63) / 64)), dim3(64), 0, ctx->stream, tr, d_ac, len2, d_flat, d_list,
-                         (int32_t)esc.size(), d_scratch, words);
+    for (int64_t lo = 0; lo < total && e == hipSuccess; lo += piece) {     // (one stream: a piece starts when the one before it is done)
+      const int64_t cnt = total - lo < piece ? total - lo : piece;
+      hipLaunchKernelGGL(k_trim_wide, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, ctx->stream, tr, d_ac, len2, d_flat, d_list + lo,
+                         (int32_t)cnt, d_scratch, words);
       e = hipGetLastError();
+      launches++;
     }
   }
   if (e == hipSuccess) e = hipMemcpyAsync(trimmed, d_trimmed, (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
@@ -77,12 +83,21 @@ extern "C" int mia_hip_trim(mia_hip_ctx* ctx, const char* adapter, int64_t n, co
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) { ctx->err = std::string("trim: ") + hipGetErrorString(e); return MIA_HIP_ERR_DEVICE; }
   ctx->trim_escapes = (int64_t)esc.size();
+  ctx->trim_launches = launches;
+  ctx->trim_scratch_bytes = scratch_bytes;
   return MIA_HIP_OK;
 }
 
 extern "C" int mia_hip_trim_stats(mia_hip_ctx* ctx, int64_t* exact_reruns) {
   if (!ctx || !exact_reruns) return MIA_HIP_ERR_ARG;
   *exact_reruns = ctx->trim_escapes;
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_trim_rerun_stats(mia_hip_ctx* ctx, int64_t* launches, int64_t* scratch_bytes) {
+  if (!ctx || !launches || !scratch_bytes) return MIA_HIP_ERR_ARG;
+  *launches = ctx->trim_launches;
+  *scratch_bytes = ctx->trim_scratch_bytes;
   return MIA_HIP_OK;
 }
 

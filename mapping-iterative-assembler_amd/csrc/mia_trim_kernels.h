@@ -16,6 +16,7 @@ namespace mia {
 
 constexpr int TRIM_SCORE_CUT = 1000;   // src/params.h:32
 constexpr int MAX_ADAPTER = 127;       // src/mia_main.c:559
+constexpr int TRIM_EXACT_PIECE = 4096; // reads per k_trim_wide launch: (127 * 256 + 5 * 256) * 4 bytes of scratch each, 0.55 GB in all
 
 struct TrimReads {
   int64_t n;

@@ -304,3 +304,36 @@ def test_trim_lastcol_mode(emul, oracle):
         assert [trimmed, abc - 1 if trimmed else -999] == exp[:2]
         n_ok += 1
     assert n_ok > 450
+
+
+def test_trim_lastcol_mode_edges(emul):
+    """the emulated LASTCOL aligner on the reference's edge vectors (tests/golden/trim_vectors_edges.txt): all six numbers of
+    trim_frag wherever it does not report ST_ESCAPE.  No ST_ESCAPE where at most 62 unrelated bases split the adapter, nor on
+    the row-gap kind: a row gap of 63 or more aligns 64 of the 127 adapter rows at most, 64 * 200 - (1000 + 63 * 200) = -800,
+    below the -600 that row 0 reaches in the last column at worst, so it is never on the best path and the trace's row-gap
+    saturation cannot be reached.  ST_ESCAPE on at least half of the pairs built around 63 and more unrelated bases."""
+    import mia_amd
+    from test_oracle_vs_golden import trim_edge_gap, trim_edge_vectors
+    flat = mia_amd.flat_pssm().reshape(-1).astype(np.int32)
+    out = (C.c_int32 * 6)()
+    n_ok = n_short = n_long = n_long_esc = 0
+    for kind, ad, read, exp in trim_edge_vectors():
+        cr, ca = codes(read), codes(ad)
+        assert emul.emu_trim(cr.ctypes.data_as(C.c_void_p), len(read), ca.ctypes.data_as(C.c_void_p), len(ad),
+                             flat.ctypes.data_as(C.c_void_p), 600, out) == 0
+        score, aec, aer, abc, abr, st = list(out)
+        assert (aec, aer) == tuple(exp[2:4]), (kind, ad, read)
+        g = trim_edge_gap(kind)
+        if g is not None and g >= 63:
+            n_long += 1
+            n_long_esc += st & 1
+        if st & 1:            # ST_ESCAPE
+            assert g is not None and g >= 63, (kind, ad, read)
+            continue
+        n_short += kind == "rowgap" or (g is not None and g <= 62)
+        trimmed = int(score >= 1000 or score >= (aer - abr + 1) * 200)
+        assert st == 0 and [trimmed, abc - 1 if trimmed else -999, aec, aer, abc, abr] == exp, (kind, ad, read, list(out), exp)
+        n_ok += 1
+    print(f"trim edge vectors: {n_ok} equal, ST_ESCAPE on {n_long_esc} of the {n_long} pairs built around 63+ unrelated bases")
+    assert n_ok >= 600 and n_short >= 80 and n_long >= 60
+    assert 2 * n_long_esc >= n_long, (n_long_esc, n_long)

@@ -154,6 +154,52 @@ def test_trim_vectors(oracle):
         assert got == exp, (ad, read, got, exp)
 
 
+def trim_edge_vectors():
+    """tests/golden/trim_vectors_edges.txt (tools/make_goldens.py trim_edge_inputs): [(kind, adapter, read, the reference's six numbers)]"""
+    out, kind = [], None
+    lines = open(os.path.join(GOLDEN, "trim_vectors_edges.txt")).read().splitlines()
+    k = 0
+    while k < len(lines):
+        if lines[k].startswith("#"):
+            if lines[k].startswith("# kind "):
+                kind = lines[k].split()[2]
+            k += 1
+            continue
+        ad, read = lines[k].split()
+        f = lines[k + 1].split()
+        assert f[0] == "T" and kind
+        out.append((kind, ad, read, [int(x) for x in f[1:]]))
+        k += 2
+    return out
+
+
+def trim_edge_gap(kind):
+    """the number of unrelated bases a `gap<g>_<flavour>` kind is built around, None for the other kinds"""
+    return int(kind[3:].split("_")[0]) if kind.startswith("gap") else None
+
+
+def test_trim_edge_vectors(oracle):
+    """ora_trim against trim_frag of the real reference at the edges: adapters of 1 .. 127 bases, reads of 1 .. 256, adapter-only
+    reads, alignments that begin below row 0, ties in the last column, long gaps, gaps from column 0 / row 0, N and other letters"""
+    vecs = trim_edge_vectors()
+    count = {}
+    for kind, ad, read, exp in vecs:
+        count[kind] = count.get(kind, 0) + 1
+        tr, tp, a = C.c_int(), C.c_int(), oc.Aln()
+        oracle.ora_trim(read.encode(), len(read), ad.encode(), C.byref(tr), C.byref(tp), C.byref(a))
+        got = [tr.value, tp.value if tr.value else -999, a.aec, a.aer, a.abc, a.abr]
+        assert got == exp, (kind, ad, read, got, exp)
+    # the file holds what it was made to hold (the generator refuses to write less)
+    assert {len(ad) for _, ad, _, _ in vecs} >= {1, 2, 3, 63, 64, 65, 126, 127}
+    assert {len(r) for _, _, r, _ in vecs} >= {1, 2, 3, 4, 5, 63, 64, 65, 255, 256}
+    assert count["lengths"] >= 160 and count["adapter_only"] >= 30 and count["ties"] >= 50 and count["rowgap"] >= 30 and count["quirk"] >= 10
+    assert sum(1 for k, _, _, e in vecs if k == "fresh" and e[5] > 0) >= 60 and count["fresh_n"] >= 30
+    assert sum(1 for k, _, _, e in vecs if k == "adapter_only" and e[:2] == [1, -1]) >= 10
+    assert all(count[k] >= 30 for k in ("alpha_n_adapter", "alpha_n_read", "alpha_n_both", "alpha_iupac"))
+    assert {trim_edge_gap(k) for k in count} - {None} == {60, 61, 62, 63, 64, 65, 100}
+    assert os.path.getsize(os.path.join(GOLDEN, "trim_vectors_edges.txt")) <= 200_000
+
+
 # ---- the per-iteration loop on a read store filled with post-pass-1 fields (ora_push_frag), alignments on host threads ----
 def _iter_push_sets():
     import json

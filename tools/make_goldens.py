@@ -10,6 +10,7 @@ the GPU box, which has no /root/reference, can replay them.
   tests/golden/dp_vectors.txt        DP unit vectors  (ref_dp_driver)
   tests/golden/cons_vectors.txt      find_consensus vectors (ref_dp_driver)
   tests/golden/myers_vectors.txt     Myers vectors    (ref_myers_driver)
+  tests/golden/trim_vectors*.txt     trim_frag vectors, random and at the edges (ref_dp_driver)
   tests/golden/maln/<case>.<iter>    whole-run .maln files, line 1 (timestamp) removed
   tests/golden/maln/cases.json       the command line of each case
   tests/golden/ccheck/*              ccheck inputs (.maln.gz) and the reference's reports on them
@@ -520,6 +521,233 @@ def trim_vectors():
     print("trim vectors:", len(pairs), "trimmed:", sum(1 for o in out if o.split()[1] == "1"))
 
 
+TRIM_EDGE_KINDS_MIN = {"lengths": 160, "adapter_only": 30, "fresh": 60, "fresh_n": 30, "ties": 50, "rowgap": 30, "quirk": 10,
+                       "alpha_n_adapter": 30, "alpha_n_read": 30, "alpha_n_both": 30, "alpha_iupac": 30}
+TRIM_EDGE_GAPS = (60, 61, 62, 63, 64, 65, 100)
+TRIM_EDGE_MAX_BYTES = 200_000
+
+
+def _oracle_fill(lib, adapter, read):
+    """the oracle's score and trace matrices [len(adapter)][len(read)] of trim_frag's alignment (ora_align with sg5 = 1 is the
+    same fill); used to SELECT inputs only -- every recorded answer comes from the reference's own trim_frag"""
+    import ctypes as C
+    import numpy as np
+    import oracle_ctypes as oc
+    n1, n2 = len(read), len(adapter)
+    S, T = (C.c_int * (n1 * n2))(), (C.c_int * (n1 * n2))()
+    flat, res = oc.Pssm(), oc.Aln()
+    lib.ora_pssm_flat(C.byref(flat))
+    lib.ora_align(read.encode(), n1, adapter.encode(), n2, None, C.byref(flat), 1, C.byref(res), C.create_string_buffer(1100),
+                  C.create_string_buffer(1100), S, T)
+    return np.ctypeslib.as_array(S).reshape(n2, n1).copy(), np.ctypeslib.as_array(T).reshape(n2, n1).copy()
+
+
+def _trim_walk(adapter, read, S, T):
+    """find_align_begin (src/mia.c:612-637) from the first maximum of the last column, as trim_frag walks it.  Returns
+    (longest gap on the walk, whether the walk took a T == 0 that was a gap from column 0 or row 0 for a diagonal step)."""
+    def code(ch):
+        return "ACGT".find(ch) if ch in "ACGT" else 4
+    c = len(read) - 1
+    r = int(S[:, c].argmax())
+    longest, quirk = 0, False
+    while True:
+        t = int(T[r, c])
+        if t == c or t == -r:
+            break
+        if t == 0:
+            i, j = code(read[c]), code(adapter[r])
+            sub = -10 if i == 4 else (-100 if j == 4 else (200 if i == j else -600))          # init_flatsubmat
+            quirk |= int(S[r, c]) - sub != int(S[r - 1, c - 1])
+            r, c = r - 1, c - 1
+        elif t < 0:
+            longest = max(longest, r - 1 + t)
+            r, c = -t, c - 1
+        else:
+            longest = max(longest, c - 1 - t)
+            r, c = r - 1, t
+    return longest, quirk
+
+
+def trim_edge_inputs(oracle_lib, seed=20261020):
+    """[(kind, adapter, read)] at the edges trim_inputs leaves out: adapters of 1 .. 127 bases against reads of 1 .. 256,
+    reads that are adapter only, alignments that begin below adapter row 0, ties for the maximum of the last column, column
+    gaps of 60 .. 65 and 100 read bases (the GPU byte trace saturates at 63), row gaps of 63 and more (never on the best
+    path, see below), gaps whose source is column 0 or row 0 (find_align_begin reads their T == 0 as a diagonal step), and N,
+    lower-case and IUPAC letters in either string.  Every letter other than upper-case ACGT is code 4 in the reference
+    (pop_s1c_in_a, pop_s2c_in_a: the switch's default), so none has to be left out.
+    Kinds `gap<g>_<flavour>`: adapter prefix, g unrelated read bases, rest of the adapter.  Bridging g bases beats a fresh
+    start behind them only if 2 k >= g for a prefix of k bases, and beats row 0 alone in the last column (-600 at worst) only
+    if 200 * len(adapter) - (1000 + 200 g) does: never for the 44-base adapters (two pairs of each kind all the same: a long
+    gap in the matrix, off the path).  With a prefix of 50 bases g = 100 is a tie with the fresh start at best, and what the
+    unrelated bases match by chance decides it against the bridge: four pairs of each g = 100 kind hold such gaps off the
+    path, four more have 127 adapter bases and a prefix of 54 .. 62, and a gap of 100 on the path.
+    Kind `rowgap`: adapter[:k] + adapter[k+g:] with g >= 63.  With 127 adapter bases at most such a path aligns 64 rows at
+    most and scores 64 * 200 - (1000 + 63 * 200) = -800 at best, below the -600 that row 0 reaches in the last column at
+    worst: a row gap of 63 or more is never on the best path."""
+    rnd = random.Random(seed)
+
+    def rseq(k, alphabet="ACGT"):
+        return "".join(rnd.choice(alphabet) for _ in range(k))
+
+    def other(ch):
+        return rnd.choice([b for b in "ACGT" if b != ch])
+
+    out = []
+    # adapter lengths x read lengths: the adapter (or what fits of it) at the read's end, and no adapter at all
+    for la in (1, 2, 3, 63, 64, 65, 126, 127):
+        for lr in (1, 2, 3, 4, 5, 63, 64, 65, 255, 256):
+            ad = rseq(la)
+            k = rnd.randint(1, min(la, lr))
+            out.append(("lengths", ad, rseq(lr - k) + ad[:k]))
+            out.append(("lengths", ad, rseq(lr)))
+    # the read is adapter and nothing else (trim_point = -1), or the adapter's last k bases only
+    for i in range(40):
+        ad = [NEAND_ADAPT, STAND_ADAPT, rseq(rnd.randint(2, 127)), rseq(rnd.randint(1, 20))][i % 4]
+        k = rnd.randint(1, len(ad))
+        out.append(("adapter_only", ad, [ad, ad[:k], ad[len(ad) - k:], ad[len(ad) - k:]][i // 4 % 4]))
+    # fresh starts (abr > 0): adapter over ACG, read body all T (or T and N), read ends in adapter[a0 : a0 + m].  The m matches
+    # have to outweigh the a0 unaligned rows (200 each and 1000 once), or row 0 alone is the best of the last column: m around a0
+    cand = []
+    for i in range(170):
+        a0 = rnd.randint(1, 30)
+        m = rnd.randint(max(6, a0 - 1), a0 + 15)
+        ad = rseq(a0 + m + rnd.randint(0, 20), "ACG")
+        cand.append(("fresh", ad, "T" * rnd.randint(1, 40) + ad[a0:a0 + m]))
+    for i in range(60):
+        a0 = rnd.randint(1, 30)
+        m = rnd.randint(max(6, a0 - 1), a0 + 15)
+        ad = rseq(a0 + m + rnd.randint(0, 20), "ACG")
+        cand.append(("fresh_n", ad, rseq(rnd.randint(2, 40), "TTTN") + ad[a0:a0 + m]))
+    out += cand
+    # ties for the maximum of the last column: short pairs over two letters, selected with the oracle's score matrix
+    n_ties = 0
+    while n_ties < 60:
+        ab = rnd.choice(["AC", "AG", "CT", "GT", "AT", "CG"])
+        ad, read = rseq(rnd.randint(2, 14), ab), rseq(rnd.randint(1, 16), ab)
+        S, _ = _oracle_fill(oracle_lib, ad, read)
+        if (S[:, -1] == S[:, -1].max()).sum() >= 2:
+            out.append(("ties", ad, read))
+            n_ties += 1
+    # column gaps either side of the byte trace's saturation
+    for g in TRIM_EDGE_GAPS:
+        for flavour in ("plain", "del", "sub"):
+            for i in range(10 if 63 <= g <= 65 else 6 if g < 63 else 8):
+                for ad in ([NEAND_ADAPT, STAND_ADAPT][g % 2] if i == 0 else rseq(127 if i >= 4 else rnd.randint(121 if g == 100 else 100, 127)),):
+                    k = rnd.randint(32, 40) if len(ad) == 44 else (rnd.randint(54, 62) if i >= 4 else 50 if g == 100 else rnd.randint(32, 50))
+                    left, right = ad[:k], ad[k:]
+                    if flavour == "del":        # one adapter base missing from the read: a row gap of 1 beside the column gap
+                        if i % 2:
+                            p = rnd.randint(4, len(left) - 4); left = left[:p] + left[p + 1:]
+                        elif len(right) > 8:
+                            p = rnd.randint(3, len(right) - 4); right = right[:p] + right[p + 1:]
+                        else:
+                            p = rnd.randint(4, len(left) - 4); left = left[:p] + left[p + 1:]
+                    if flavour == "sub":
+                        p = rnd.randint(2, len(left) - 3); left = left[:p] + other(left[p]) + left[p + 1:]
+                        if len(right) > 6:
+                            p = rnd.randint(2, len(right) - 3); right = right[:p] + other(right[p]) + right[p + 1:]
+                        else:
+                            p = rnd.randint(2, len(left) - 3); left = left[:p] + other(left[p]) + left[p + 1:]
+                    out.append((f"gap{g}_{flavour}", ad, (rseq(rnd.randint(0, 10)) + left + rseq(g) + right)[:256]))
+    # row gaps of 63 and more: never on the best path (see above)
+    for i in range(36):
+        ad = rseq(rnd.randint(100, 127))
+        g = rnd.randint(63, len(ad) - 30)
+        k = rnd.randint(10, len(ad) - g - 10)
+        out.append(("rowgap", ad, rseq(rnd.randint(0, 60)) + ad[:k] + ad[k + g:]))
+    # gaps whose source is column 0 or row 0: T == 0 there, and find_align_begin takes it for a diagonal step.  Kept where the
+    # walk trim_frag makes does take such a step (told from the scores: the cell is not its diagonal neighbour plus the match).
+    # (The column-0 form, adapter[0] + 1 .. 5 unrelated bases + adapter[1:], is never kept: beginning in row 0 at the last
+    # unrelated base costs 600 at most, the gap back to column 0 1200 at least.)
+    n_quirk = [0, 0]
+    for i in range(400):
+        ad = [NEAND_ADAPT, STAND_ADAPT, rseq(rnd.randint(20, 60)), rseq(rnd.randint(8, 20))][i % 4]
+        g = 1 + i // 4 % 5
+        if i % 8 < 4:
+            read = ad[0] + rseq(g) + ad[1:]
+        else:
+            if 1 + g >= len(ad):
+                continue
+            read = rseq(rnd.randint(0, 40)) + ad[0] + ad[1 + g:]
+        S, T = _oracle_fill(oracle_lib, ad, read)
+        if _trim_walk(ad, read, S, T)[1] and n_quirk[i % 8 >= 4] < 20:
+            out.append(("quirk", ad, read))
+            n_quirk[i % 8 >= 4] += 1
+    print("trim edges: quirk pairs kept: column-0 form", n_quirk[0], "row-0 form", n_quirk[1])
+    # N, lower case and IUPAC letters
+    def spoil(s, letters, k):
+        s = list(s)
+        for _ in range(k):
+            s[rnd.randrange(len(s))] = rnd.choice(letters)
+        return "".join(s)
+
+    for i in range(132):
+        kind = ("alpha_n_adapter", "alpha_n_read", "alpha_n_both", "alpha_iupac")[i // 33]
+        ad = [NEAND_ADAPT, STAND_ADAPT, rseq(rnd.randint(5, 127))][i % 3]
+        tail = ad[: rnd.randint(min(4, len(ad)), len(ad))]
+        read = (rseq(rnd.randint(0, 120)) + tail)[:256]
+        if kind in ("alpha_n_adapter", "alpha_n_both"):
+            ad = spoil(ad, "N", rnd.randint(1, 3))
+        if kind in ("alpha_n_read", "alpha_n_both"):
+            read = spoil(read, "N", rnd.randint(1, 4))
+        if kind == "alpha_iupac":
+            ad = spoil(ad, "acgtnRYSWKMBDHV", rnd.randint(1, 4))
+            read = spoil(read, "acgtnRYSWKMBDHV", rnd.randint(1, 6))
+        out.append((kind, ad, read))
+    return out
+
+
+def trim_edge_vectors():
+    """tests/golden/trim_vectors_edges.txt: trim_vectors.txt's two lines per pair, under `# kind <name>` lines"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_ctypes
+    sh(["make", "-s", "-f", "oracle/Makefile"], cwd=ROOT)
+    lib = oracle_ctypes.load(os.path.join(ROOT, "oracle", "_build", "libmia_oracle.so"))
+    items = trim_edge_inputs(lib)
+    assert all(1 <= len(a) <= 127 and 1 <= len(r) <= 256 for _, a, r in items)
+    ans = subprocess.run([os.path.join(RB, "ref_dp_driver")], input="".join(f"T {a} {r}\n" for _, a, r in items).encode(), check=True,
+                         stdout=subprocess.PIPE).stdout.decode().splitlines()
+    assert len(ans) == len(items)
+    kept = []
+    for (kind, a, r), o in zip(items, ans):
+        if kind == "fresh" and int(o.split()[6]) == 0:       # fresh starts: only what the reference did begin below row 0
+            continue
+        kept.append((kind, a, r, o))
+    count = {}
+    for kind, *_ in kept:
+        count[kind] = count.get(kind, 0) + 1
+    need = dict(TRIM_EDGE_KINDS_MIN)
+    for g in TRIM_EDGE_GAPS:
+        need.update({f"gap{g}_{f}": 6 if g < 63 else 10 if g <= 65 else 8 for f in ("plain", "del", "sub")})       # 18 / 30 / 24 per g
+    missed = {k: (count.get(k, 0), v) for k, v in need.items() if count.get(k, 0) < v}
+    if missed:
+        sys.exit(f"trim edges: not written, counts missed (have, need): {missed}")
+    long_gap = [0, 0]
+    for kind, a, r, _ in kept:
+        if kind.startswith("gap") and int(kind[3:].split("_")[0]) >= 63:
+            long_gap[0] += _trim_walk(a, r, *_oracle_fill(lib, a, r))[0] >= 63
+            long_gap[1] += 1
+    if 2 * long_gap[0] < long_gap[1]:
+        sys.exit(f"trim edges: not written, only {long_gap[0]} of {long_gap[1]} pairs built around 63+ unrelated bases bridge them")
+    text = ["# trim_frag of the reference at its edges (tools/make_goldens.py trim_edge_inputs): as trim_vectors.txt, `adapter read`, then",
+            "# `T trimmed trim_point aec aer abc abr`; a `# kind` line names the pairs below it"]
+    last = None
+    for kind, a, r, o in kept:
+        if kind != last:
+            text.append(f"# kind {kind}")
+            last = kind
+        text += [f"{a} {r}", o]
+    text = "\n".join(text) + "\n"
+    if len(text) > TRIM_EDGE_MAX_BYTES:
+        sys.exit(f"trim edges: not written, {len(text)} bytes")
+    with open(os.path.join(G, "trim_vectors_edges.txt"), "w") as f:
+        f.write(text)
+    print("trim edge vectors:", len(kept), "pairs,", len(text), "bytes; trimmed:", sum(1 for *_, o in kept if o.split()[1] == "1"),
+          "; abr > 0:", sum(1 for *_, o in kept if int(o.split()[6]) > 0), "; a gap of 63+ on the path of", long_gap[0], "of the",
+          long_gap[1], "pairs built around 63+ unrelated bases")
+    print("  " + " ".join(f"{k}={v}" for k, v in sorted(count.items())))
+
+
 MA_HEADER = "/* map_alignment [V1.0] */ golden\n"   # line 1 of a .maln carries a timestamp and is not stored
 MA_RUNS = [(5, 1), (5, 2), (41, 1), (41, 2), (4, 1)]
 
@@ -677,6 +905,7 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "trim":        # only the trim_frag vectors
         sh(["make", "-s", "-f", "oracle/Makefile.ref"], cwd=ROOT)
         trim_vectors()
+        trim_edge_vectors()
         return
     if len(sys.argv) > 1 and sys.argv[1] == "ccheck":      # only the ccheck inputs and reports
         sh(["make", "-s", "-f", "oracle/Makefile.ref"], cwd=ROOT)
@@ -712,6 +941,7 @@ def main():
     g2_cases()
     ma_cases()
     trim_vectors()
+    trim_edge_vectors()
     ccheck_cases(os.path.join(G, "mt311.fa"))
 
 
