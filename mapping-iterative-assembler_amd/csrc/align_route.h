@@ -17,6 +17,7 @@ struct AlignRouteIn {
   int64_t kh_entries = 0;              // > 0: the reference has N columns and its 10-mer table lists them
   bool flat = false, ref_mostly_bases = true, ref_few_n = true, bx_ok = false, explicit_win = false, deferred = false, pend_encode = false;
   bool own_umax = false;               // the context's own reads, their U at hand (a borrowed read set has none)
+  bool ref_ready = false;              // codes, planes, nibbles, table and bitmaps of this reference stand, and the control block is clear (ref_ahead.h: a hit)
   int64_t rejects = 0;                 // reads the plan of the alignment before gave up on: sum of bx_last[BXC_FAIL0 + k], k = 1 .. BXF_KINDS - 1
   // the alt switches (read_alt_switches); the release build only ever holds the defaults
   int use_filter = 1, use_banddp = 1, use_bx = 1, use_lanes = 1, use_fine = 1, use_quick = 1;
@@ -28,6 +29,7 @@ struct AlignRoute {
   int64_t plane_words = 0;             // (the caller's)
   int nwords = 0;                      // 64-row words of the longest read
   bool bx = false, run_filter = false, fused_prep = false, filtered = false, kocc = false, banded = false;
+  bool prep_none = false;              // the reference preparation launches nothing: it only hands the stages the views of what stands
   bool want_bits = false, new_flow = false, split = false, fork_by_launch = false, fine = false;
   bool many_rejects = false;           // THE many-rejects predicate: one answer for fine, planner_head_first / direct_open and use_plain
   bool planner_head_first = false, direct_open = false;
@@ -62,6 +64,9 @@ inline AlignRoute align_route(const AlignRouteIn& in) {
   r.run_filter = filter_ok && !r.bx;
   // mia_hip_iterate with the band pipeline alone: codes, control block, planes, nibbles and 10-mer table in one launch (k_ref_prep)
   r.fused_prep = in.pend_encode && r.bx && !in.no_prep_fuse;
+  // ... or none at all: the last call of mia_hip_iterate made all of it behind its consensus, for the string it returned, and this call
+  // brings that string (only the band pipeline's set is prepared ahead)
+  r.prep_none = in.ref_ready && r.bx;
   r.filtered = r.run_filter || r.bx;            // bin_of carries marks for the planner
   // the 10-mer table of this reference (rule (c) looks long clean stretches up instead of sliding over every diagonal;
   // the band plans are made of its anchors); not for the very long concatenated strings mia_hip_align_windows may be given

@@ -14,10 +14,12 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/mia_hip.h"
 #include "dev_buf.h"
+#include "ref_ahead.h"
 #include "dev_pool.h"
 #include "mia_comm.h"
 #include "mia_consensus_kernels.h"
@@ -88,12 +90,18 @@ struct mia_hip_ctx {
   DevPool pool;                            // device temporaries of the one-off calls (dev_pool.h; pool_take)
   // pinned staging: small copies to and from pageable memory wait for the stream, pinned ones do not
   unsigned char* h_pin = nullptr; static constexpr size_t PIN_BYTES = 1 << 20, PIN_MISC = 64 << 10;
-  DevBuf<int32_t> d_ctrl;                  // the control block (CTRL_*)
+  // the control block (CTRL_*), twice: the views below look at one half (ctrl_bind); k_ref_prep's shadow launch clears the other, and
+  // the call that adopts the shadow's work turns to it -- what the getters read from the device after a step stays as the step left it
+  DevBuf<int32_t> d_ctrl; int ctrl_half = 0;
+  int32_t* ctrl = nullptr;                 // the current half (view)
+  int32_t* d_genn = nullptr;               // CTRL_GENN (view)
+  const int32_t* d_ctr0 = nullptr;         // CTRL_C0: the CTRL_CN words the host looks at behind an alignment (view)
   uint32_t dbg = 0;                        // timing experiments only, results are wrong when set (read_alt_switches)
 
   // ---- streams and events ------------------------------------------------------------------------------------------------
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // the trace DP of the plan's own lists runs beside the values DP
+  hipEvent_t ev_cons = nullptr;            // k_cons_scatter's own end, where a shadow launch follows it (ref_ahead_speculate)
   hipStream_t stream3 = nullptr; hipEvent_t ev_join3 = nullptr;                      // ... and both beside the planner and the full-window kernels of the reads the plan gave up on
   // the launches other streams wait for signal their events themselves (launch_k) instead of a marker behind them: a bit per launch, all or none
   uint32_t ext_events = 31u; bool align_end_signalled = false;      // (the alignment's last launch on the context's stream has signalled ev_fork: bx_join_and_retry)
@@ -168,6 +176,19 @@ struct mia_hip_ctx {
   DevBuf<KbPair> d_kbits;               // the quick plan's bitmaps over all 4^10 10-mers (bandx_body.h: KmerBits), remade with the table
   int use_quick = 1; int64_t quick_steps = 0;      // the quick plan in front of k_bx_plan's launches
   DevBuf<uint32_t> d_prep_bar; uint32_t prep_bar_count = 0; bool no_prep_fuse = false;   // k_ref_prep's grid barrier
+  // REFERENCE AHEAD (ref_ahead.h): a second set of everything k_ref_prep writes.  mia_hip_iterate launches k_ref_prep
+  // into it behind the consensus it returns (the string is the next call's reference in every real loop); the next call, if it brings
+  // that string, swaps the set into place instead of preparing anything (ref_ahead_adopt).  Barrier counter and `stuck` word are shared
+  // with the ordinary launch: both are on the context's stream, one after the other.
+  struct RefAhead {
+    DevBuf<uint8_t> d_ref; DevBuf<uint64_t> d_planes; DevBuf<uint32_t> d_refnib, d_khash; DevBuf<int32_t> d_khash_ovf; DevBuf<KbPair> d_kbits;
+    bool queued = false;                    // a speculative launch with `key` is queued behind this call's k_cons_scatter (not settled yet)
+    bool valid = false;                     // a shadow launch is queued or done, `key` and `str` describe it
+    RefAheadKey key; std::string str;       // what it was built with; the string as returned
+  } ahead;
+  bool no_ref_ahead = false;               // (alt build, MIA_HIP_NO_REF_AHEAD=1) no shadow launch
+  bool ref_ready = false;                  // this call adopted the shadow's work (AlignRouteIn::ref_ready); never outlives the call
+  bool last_route_bx = false;              // the last alignment took the band pipeline
   DevBuf<uint32_t> d_bx_plan; DevBuf<int32_t> d_bx_expect, d_bx_lists;
   DevBuf<BxCandRec> d_bx_cand; bool plan_split = true;      // k_bx_plan's hand-over list between its two launches
   DevBuf<BxCandRec> d_bx_cand2; int use_fine = 1;      // the third launch's list (reads for the fine blocks)
@@ -355,6 +376,7 @@ static void read_alt_switches(mia_hip_ctx* ctx) {
   if (const char* v = alt_env("MIA_HIP_QUICK_PLAN")) ctx->use_quick = atoi(v);     // 2: the quick plan also where align_all's size rule says no
   if (on("MIA_HIP_NO_DIRECT_OPEN")) ctx->use_direct_open = false;                  // open reads through the planner's count / scan / fill and the quad kernels
   if (on("MIA_HIP_NO_PREP_FUSE")) ctx->no_prep_fuse = true;    // six launches instead of k_ref_prep
+  if (on("MIA_HIP_NO_REF_AHEAD")) ctx->no_ref_ahead = true;    // no k_ref_prep behind the consensus for the next call (ref_ahead.h)
   // mia_hip_iterate: what is queued when
   if (on("MIA_HIP_NO_SPEC")) ctx->no_spec = true;              // wait for the alignment's counters before the cull is queued
   if (on("MIA_HIP_SPEC_TEST")) ctx->spec_force = true;         // every iteration queues cull / tally / consensus twice
@@ -409,6 +431,28 @@ static int dev_ensure(mia_hip_ctx* ctx, DevBuf<T>& b, int64_t need) { return dev
 template <class T>
 static int pool_take(mia_hip_ctx* ctx, PoolLease<T>& lease, size_t n) { return dev_nomem(ctx, lease.take(ctx->pool, n)); }
 
+// THE one place where the views into the control block are set: at context creation, and when a call adopts the tables prepared
+// ahead together with the half of the block that was cleared for them (ref_ahead_adopt).  A view that is derived from one of these
+// (d_n_links_all while it names this context's own link count) follows.
+static_assert(CTRL_WORDS % 64 == 0, "the second half of the control block starts on a cache line, as the first does");
+static void ctrl_bind(mia_hip_ctx* ctx, int half) {
+  const bool own_links = ctx->d_n_links_all && ctx->d_n_links_all == ctx->lk.n;
+  int32_t* b = ctx->d_ctrl + (size_t)half * CTRL_WORDS;
+  ctx->ctrl_half = half;
+  ctx->ctrl = b;
+  ctx->d_bins = b + CTRL_BINS;
+  ctx->d_plan_hdr = b + CTRL_HDR;
+  ctx->d_filter_n = reinterpret_cast<uint32_t*>(b + CTRL_FILTER);
+  ctx->lk.n = b + CTRL_LKN;
+  ctx->d_cull_flags = reinterpret_cast<uint32_t*>(b + CTRL_CULLF);
+  ctx->tb.n_events = b + CTRL_NEV;
+  ctx->tb.flags = reinterpret_cast<uint32_t*>(b + CTRL_TFLAGS);
+  ctx->d_genn = b + CTRL_GENN;
+  ctx->d_bx_ctr = reinterpret_cast<uint32_t*>(b + CTRL_BXC);
+  ctx->d_ctr0 = b + CTRL_C0;
+  if (own_links) ctx->d_n_links_all = ctx->lk.n;
+}
+
 extern "C" const char* mia_hip_last_error(const mia_hip_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 extern "C" int mia_hip_create(mia_hip_ctx** out, int device_index) {
@@ -422,7 +466,7 @@ extern "C" int mia_hip_create(mia_hip_ctx** out, int device_index) {
   const unsigned evf = hipEventDisableTiming;
   if (hipSetDevice(device_index) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_join3, evf) != hipSuccess ||
+      hipEventCreateWithFlags(&ctx->ev_join3, evf) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_cons, evf) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_fork, evf) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_join, evf) != hipSuccess) {
     delete ctx;
     return MIA_HIP_ERR_DEVICE;
@@ -437,7 +481,7 @@ extern "C" int mia_hip_create(mia_hip_ctx** out, int device_index) {
     read_alt_switches(ctx);
     if (const char* sw = getenv("MIA_HIP_SPIN_WAIT")) ctx->spin_wait = atoi(sw) != 0;
   }
-  if (dev_alloc(ctx, ctx->d_pssm, 2 * PSSM_WORDS) || dev_alloc(ctx, ctx->d_ctrl, CTRL_WORDS) ||
+  if (dev_alloc(ctx, ctx->d_pssm, 2 * PSSM_WORDS) || dev_alloc(ctx, ctx->d_ctrl, 2 * CTRL_WORDS) ||
       dev_alloc(ctx, ctx->d_total, 1) || dev_alloc(ctx, ctx->d_ins_total, 1) ||
       dev_alloc(ctx, ctx->d_bx_sub, 2 * BX_SUB_WORDS) || dev_alloc(ctx, ctx->d_bx_mrow, 2 * 31 * 4) || dev_alloc(ctx, ctx->d_bx_loss, BX_LOSS_WORDS) ||
       dev_alloc(ctx, ctx->d_bx_dl, BX_DL_WORDS) ||
@@ -445,15 +489,8 @@ extern "C" int mia_hip_create(mia_hip_ctx** out, int device_index) {
     delete ctx;
     return MIA_HIP_ERR_NOMEM;
   }
-  ctx->d_bins = ctx->d_ctrl + CTRL_BINS;
-  ctx->d_plan_hdr = ctx->d_ctrl + CTRL_HDR;
-  ctx->d_filter_n = reinterpret_cast<uint32_t*>(ctx->d_ctrl + CTRL_FILTER);
-  ctx->lk.n = ctx->d_ctrl + CTRL_LKN;
-  ctx->d_cull_flags = reinterpret_cast<uint32_t*>(ctx->d_ctrl + CTRL_CULLF);
-  ctx->tb.n_events = ctx->d_ctrl + CTRL_NEV;
-  ctx->tb.flags = reinterpret_cast<uint32_t*>(ctx->d_ctrl + CTRL_TFLAGS);
-  ctx->d_bx_ctr = reinterpret_cast<uint32_t*>(ctx->d_ctrl + CTRL_BXC);
-  if (hipMemset(ctx->d_ctrl, 0, CTRL_WORDS * 4) != hipSuccess) { delete ctx; return MIA_HIP_ERR_DEVICE; }
+  ctrl_bind(ctx, 0);
+  if (hipMemset(ctx->d_ctrl, 0, 2 * CTRL_WORDS * 4) != hipSuccess) { delete ctx; return MIA_HIP_ERR_DEVICE; }
   {
     const int32_t one = 1;
     if (dev_alloc(ctx, ctx->d_one, 1) || hipMemcpy(ctx->d_one, &one, 4, hipMemcpyHostToDevice) != hipSuccess) { delete ctx; return MIA_HIP_ERR_DEVICE; }
@@ -480,6 +517,7 @@ extern "C" void mia_hip_destroy(mia_hip_ctx* ctx) {
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
   if (ctx->ev_join3) (void)hipEventDestroy(ctx->ev_join3);
+  if (ctx->ev_cons) (void)hipEventDestroy(ctx->ev_cons);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   delete ctx;                               // its DevBuf members free every device block, the pool's included
@@ -1015,7 +1053,7 @@ static AlignRouteIn align_route_in(const mia_hip_ctx* ctx) {
   in.n = ctx->rs.n; in.max_len = ctx->max_len; in.wrap = ctx->wrap; in.L = ctx->L; in.kh_entries = ctx->kh_entries;
   in.plane_words = plane_words((int64_t)ctx->wrap + 64);
   in.flat = ctx->flat; in.ref_mostly_bases = ctx->ref_mostly_bases; in.ref_few_n = ctx->ref_few_n; in.bx_ok = ctx->bx_ok;
-  in.explicit_win = ctx->explicit_win != 0; in.deferred = ctx->deferred; in.pend_encode = ctx->pend_encode;
+  in.explicit_win = ctx->explicit_win != 0; in.deferred = ctx->deferred; in.pend_encode = ctx->pend_encode; in.ref_ready = ctx->ref_ready;
   in.own_umax = ctx->umax_valid && ctx->rs.roff == ctx->d_roff;
   for (int k = 1; k < BXF_KINDS; k++) in.rejects += ctx->bx_last[BXC_FAIL0 + k];
   in.use_filter = ctx->use_filter; in.use_banddp = ctx->use_banddp; in.use_bx = ctx->use_bx; in.use_lanes = ctx->use_lanes;
@@ -1082,15 +1120,47 @@ static int align_ensure_buffers(mia_hip_ctx* ctx, AlignCall& c) {
   return MIA_HIP_OK;
 }
 
+// k_ref_prep over one set of buffers: the call's own (align_ref_prep), or the set prepared ahead with the idle half of the control
+// block (ref_ahead_queue).  Both go to the context's stream and share the barrier's counter and the `stuck` word.
+struct RefPrepSet { uint8_t* codes; int32_t* ctrl; uint32_t* khash; int32_t* kovf; uint64_t* planes; int64_t pstride; uint32_t* nib; KbPair* kbits; };
+static int launch_ref_prep(mia_hip_ctx* ctx, const RefPrepSet& s, const char* ascii, int32_t L, int32_t wl, int32_t total, uint32_t kslots, int kwild,
+                           int64_t words, int64_t nw) {
+  const int wrap = total - 64;
+  RefPrep rp2;
+  rp2.ascii = ascii; rp2.L = L; rp2.wl = wl; rp2.total = total; rp2.codes = s.codes;
+  rp2.ctrl = s.ctrl; rp2.ctrl_words = CTRL_WORDS;
+  rp2.kslot = s.khash; rp2.kovf = s.kovf; rp2.kslots = kslots; rp2.kmask = kslots - 1; rp2.kshift = kh_shift_for(kslots); rp2.kwild = kwild;
+  rp2.plane_words = words; rp2.plo = s.planes; rp2.phi = s.planes + s.pstride; rp2.pok = s.planes + 2 * s.pstride;
+  rp2.nib_words = nw; rp2.nib = s.nib;
+  const int64_t want = ((int64_t)wrap + (kwild > 0 ? 63 : 255)) / (kwild > 0 ? 64 : 256);       // (N columns spelled out: 64 positions per workgroup, see kmer_hash_insert_block)
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, ctx->cus));      // one workgroup per compute unit at most: all resident
+  // the grid barrier's target: what the counter reaches when this launch's workgroups have all arrived.  The host's count only
+  // moves once the launch is known to be queued (a refused launch adds nothing on the device either), the wait inside the
+  // kernel is bounded, and a barrier given up on is reported through a pinned word the step's one wait looks at.
+  rp2.bar = ctx->d_prep_bar; rp2.bar_target = ctx->prep_bar_count + grid;
+  rp2.stuck = ctx->h_pin ? reinterpret_cast<uint32_t*>(ctx->h_pin + (62 << 10)) : nullptr;
+  rp2.kbits = s.kbits;
+  hipLaunchKernelGGL(k_ref_prep, dim3(grid), dim3(256), 0, ctx->stream, rp2);
+  HIPCHK(hipGetLastError());
+  ctx->prep_bar_count += grid;
+  return MIA_HIP_OK;
+}
+
 // REFERENCE PREPARATION: codes, control block, bit planes, and the table of the route -- round 1's 10-mer occurrences, or nibbles, hash
 // table and bitmaps of the band pipeline; mia_hip_iterate with the band pipeline: all of it in ONE launch (k_ref_prep)
 static int align_ref_prep(mia_hip_ctx* ctx, AlignCall& c) {
   const AlignRoute& r = c.r;
   const int wrap = ctx->wrap;
   const int64_t words = r.plane_words, pstride = ctx->d_planes.cap / 3;      // the block holds three planes
+  if (r.prep_none) {
+    // everything below was made behind the last consensus, and the control block's current half was cleared with it (ref_ahead_adopt)
+    c.rp = RefPlanes{ctx->d_planes, ctx->d_planes + pstride, ctx->d_planes + 2 * pstride};
+    c.kh = KmerHash{ctx->d_khash, ctx->d_khash_ovf, c.kslots - 1, kh_shift_for(c.kslots), ctx->kh_entries > 0 ? BX_WILD : 0};
+    return MIA_HIP_OK;
+  }
   if (!r.fused_prep) {
     encode_now(ctx);
-    HIPCHK(hipMemsetAsync(ctx->d_ctrl, 0, (size_t)CTRL_WORDS * 4, ctx->stream));     // every counter of the iteration at once
+    HIPCHK(hipMemsetAsync(ctx->ctrl, 0, (size_t)CTRL_WORDS * 4, ctx->stream));     // every counter of the iteration at once
   }
   if (!r.filtered) return MIA_HIP_OK;
   c.rp = RefPlanes{ctx->d_planes, ctx->d_planes + pstride, ctx->d_planes + 2 * pstride};
@@ -1119,23 +1189,8 @@ static int align_ref_prep(mia_hip_ctx* ctx, AlignCall& c) {
     }
     return MIA_HIP_OK;
   }
-  RefPrep rp2;
-  rp2.ascii = ctx->ascii_src; rp2.L = ctx->pend_L; rp2.wl = ctx->pend_wl; rp2.total = ctx->pend_total; rp2.codes = ctx->d_ref;
-  rp2.ctrl = ctx->d_ctrl; rp2.ctrl_words = CTRL_WORDS;
-  rp2.kslot = ctx->d_khash; rp2.kovf = ctx->d_khash_ovf; rp2.kslots = kslots; rp2.kmask = kh.mask; rp2.kshift = kh.shift; rp2.kwild = kh.wild;
-  rp2.plane_words = words; rp2.plo = ctx->d_planes; rp2.phi = ctx->d_planes + pstride; rp2.pok = ctx->d_planes + 2 * pstride;
-  rp2.nib_words = nw; rp2.nib = ctx->d_refnib;
-  const int64_t want = ((int64_t)wrap + (kh.wild > 0 ? 63 : 255)) / (kh.wild > 0 ? 64 : 256);       // (N columns spelled out: 64 positions per workgroup, see kmer_hash_insert_block)
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, ctx->cus));      // one workgroup per compute unit at most: all resident
-  // the grid barrier's target: what the counter reaches when this launch's workgroups have all arrived.  The host's count only
-  // moves once the launch is known to be queued (a refused launch adds nothing on the device either), the wait inside the
-  // kernel is bounded, and a barrier given up on is reported through a pinned word the step's one wait looks at.
-  rp2.bar = ctx->d_prep_bar; rp2.bar_target = ctx->prep_bar_count + grid;
-  rp2.stuck = ctx->h_pin ? reinterpret_cast<uint32_t*>(ctx->h_pin + (62 << 10)) : nullptr;
-  rp2.kbits = r.want_bits ? ctx->d_kbits : nullptr;
-  hipLaunchKernelGGL(k_ref_prep, dim3(grid), dim3(256), 0, ctx->stream, rp2);
-  HIPCHK(hipGetLastError());
-  ctx->prep_bar_count += grid;
+  const RefPrepSet own{ctx->d_ref, ctx->ctrl, ctx->d_khash, ctx->d_khash_ovf, ctx->d_planes, pstride, ctx->d_refnib, r.want_bits ? ctx->d_kbits.p : nullptr};
+  if (int rc = launch_ref_prep(ctx, own, ctx->ascii_src, ctx->pend_L, ctx->pend_wl, ctx->pend_total, kslots, kh.wild, words, nw)) return rc;
   ctx->pend_encode = false;
   return MIA_HIP_OK;
 }
@@ -1420,7 +1475,7 @@ static int align_finish_deferred(mia_hip_ctx* ctx, AlignCall& c) {
   align_ck(ctx, c, "retry");
   if (int rcj = bx_join_and_retry(ctx, c)) return rcj;
   align_ck(ctx, c, "band join");
-  constexpr int C0 = CTRL_C0, CN = CTRL_CN;
+  constexpr int CN = CTRL_CN;
   std::vector<int32_t> pageable;
   int32_t* hb;
   if (ctx->h_pin) hb = reinterpret_cast<int32_t*>(ctx->h_pin);
@@ -1430,7 +1485,7 @@ static int align_finish_deferred(mia_hip_ctx* ctx, AlignCall& c) {
   const bool spec = ctx->spec_ok && ctx->h_pin && !pre_cull && !c.dbg_steps;
   // (a copy in the middle of the step holds the stream up for 20 us: with zero_copy the step's last kernel, k_cons_scatter,
   // writes these words into h_pin itself, whether or not the speculation held)
-  if (!(spec && ctx->zero_copy)) HIPCHK(hipMemcpyAsync(hb, ctx->d_ctrl + C0, (size_t)CN * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (!(spec && ctx->zero_copy)) HIPCHK(hipMemcpyAsync(hb, ctx->d_ctr0, (size_t)CN * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (spec) {
     // mia_hip_iterate, one context, a cut line that needs no scores on the host: no wait here.  The caller queues cull,
     // tally and consensus behind this copy; their kernels look at the exact-kernel count themselves (abort_if) and
@@ -1607,6 +1662,7 @@ static int align_all(mia_hip_ctx* ctx) {
   AlignCall c;
   c.r = align_route(align_route_in(ctx));
   const AlignRoute& r = c.r;
+  ctx->last_route_bx = r.bx;
   c.ref = RefInfo{ctx->d_ref, ctx->L, ctx->wrap, ctx->explicit_win};
   c.d_count = ctx->d_bins; c.d_off = ctx->d_bins + N_BINS; c.d_cursor = ctx->d_bins + 2 * N_BINS; c.d_wide_count = ctx->d_bins + 3 * N_BINS;
   c.gb = (int)((n + (int64_t)256 * PLAN_PER - 1) / ((int64_t)256 * PLAN_PER));
@@ -2133,7 +2189,7 @@ static int tally_launch(mia_hip_ctx* ctx) {
       const bool planes_ok = ctx->umax_valid && ctx->rs.roff == ctx->d_roff && ctx->d_rplanes && ctx->d_umax;
       const bool defer = ctx->tally_defer;
       if (defer && dev_ensure(ctx, ctx->d_gen_list, n)) return MIA_HIP_ERR_NOMEM;
-      int32_t* n_gen = ctx->d_ctrl + CTRL_GENN;
+      int32_t* n_gen = ctx->d_genn;
       if (defer && !ctx->in_iterate) HIPCHK(hipMemsetAsync(n_gen, 0, 4, ctx->stream));     // (mia_hip_iterate clears the whole control block)
 #define MIA_TALLY_ARGS(PL, RW, UM, BIAS)                                                                                                              \
   dim3(grid), dim3(256), 0, ctx->stream, ctx->rs, ref, ctx->d_pssm, ctx->d_drop_f, ctx->d_drop_b, ctx->tb, nb, d_off, d_wgoff, split ? ctx->d_order2 : ctx->d_order, ctx->ri.trec, \

@@ -155,6 +155,105 @@ __global__ __launch_bounds__(256) void k_events_compact(const uint64_t* __restri
   if (r == 0 && blockIdx.x == 0 && threadIdx.x == 0) *n_out = (int32_t)total;
 }
 
+// ---- reference ahead (ref_ahead.h, DESIGN.md 3.5) -------------------------------------------------------------------------
+// characters of the string that are no base, and the entries their spellings add to the 10-mer table of the wrapped string
+// (kh_wild_entries, without making the codes)
+static void ref_count_other(const char* ref, int L, int wrap, int64_t* n_other_out, int64_t* kh_entries_out) {
+  // (base_code: only upper-case ACGT are bases.  Four compares per character, no table: the loop is one the compiler turns into
+  // vector instructions -- the shadow launch waits for this count, with the device idle)
+  uint32_t cnt = 0;
+  for (int i = 0; i < L; i++) { const char c = ref[i]; cnt += (uint32_t)((c != 'A') & (c != 'C') & (c != 'G') & (c != 'T')); }
+  int64_t n_other = cnt, e = 0;
+  if (n_other) {
+    int k = 0;
+    auto other = [&](int j) { return base_code(ref[j < L ? j : j - L]) > 3 ? 1 : 0; };
+    for (int pq = 0; pq < wrap; pq++) {
+      k += other(pq);
+      if (pq >= DF_K) k -= other(pq - DF_K);
+      if (pq >= DF_K - 1 && k <= BX_WILD) e += (int64_t)1 << (2 * k);
+    }
+    if (e > ((int64_t)1 << 24)) e = 0;
+  }
+  *n_other_out = n_other; *kh_entries_out = e;
+}
+
+// What k_ref_prep's arguments would be for a call of mia_hip_iterate on a reference of L characters with these counts -- by the
+// functions such a call uses itself (align_route, align_ensure_buffers) -- and whether the call would take the band pipeline,
+// the only route whose tables are prepared ahead.  Asked twice: behind a consensus (the shadow launch's key) and at the top of the
+// next call (the key it wants).
+static bool ref_ahead_want(const mia_hip_ctx* ctx, int L, int circular, int64_t n_other, int64_t kh_entries, RefAheadKey* key) {
+  const int wl = circular ? (L < MAX_READ ? L : MAX_READ) : 0, wrap = L + wl;
+  AlignRouteIn in = align_route_in(ctx);
+  in.L = L; in.wrap = wrap; in.plane_words = plane_words((int64_t)wrap + 64); in.kh_entries = kh_entries;
+  in.ref_mostly_bases = n_other * 50 <= L; in.ref_few_n = n_other * 500 <= L;
+  in.explicit_win = false; in.deferred = true; in.pend_encode = true; in.ref_ready = false;
+  const AlignRoute r = align_route(in);
+  key->L = L; key->circular = circular ? 1 : 0; key->n_other = n_other; key->kh_entries = kh_entries;
+  key->kslots = kh_slots_for_entries(wrap, kh_entries); key->kwild = kh_entries > 0 ? BX_WILD : 0;
+  key->plane_words = r.plane_words; key->nib_words = bx_nib_words((int64_t)wrap + 64); key->bits = r.want_bits;
+  return r.bx && r.fused_prep;
+}
+
+// THE SHADOW LAUNCH: k_ref_prep for the consensus a call returns, into the second set of buffers and the idle half of the control
+// block.  Nothing the call returns depends on it: whatever goes wrong here leaves no shadow behind, and the next call prepares its
+// reference as it always did.
+//   WHEN.  Behind the step's wait the host has the string and could derive every argument from it -- but the device then idles while
+//   the host notices the end, counts and launches (measured: a step as long as without the shadow launch, and a caller that waits
+//   for the context behind the call pays for the launch in full).  So the launch is SPECULATIVE and nothing else: queued right
+//   behind k_cons_scatter, with the key this call's own reference has (ref_ahead_speculate) -- at steady state the consensus is as
+//   long as its reference and holds no N either -- and the host waits for k_cons_scatter's own event, not for the stream.  Behind the
+//   wait the key is made from the string as returned (ref_ahead_settle): equal keys -- the launch that is already running read the
+//   right string with the right arguments, and the next call may adopt it; else it is dropped and the next call is a miss.
+//   A speculative launch reads key.L characters of the result block, which holds at least this call's L: in bounds whatever the
+//   consensus turns out to be.  It is only made with kwild = 0: no 10-mer is spelled out then, the table (four slots per column) cannot
+//   fill up whatever the characters are, and the insert's probe loop ends.
+static bool ref_ahead_allowed(const mia_hip_ctx* ctx) {
+  return !ctx->no_ref_ahead && !ctx->no_prep_fuse && ctx->h_pin && ctx->last_route_bx && ctx->rs.n > 0;
+}
+// src: the string, for the device -- the pinned result block (with zero_copy k_cons_scatter writes no device copy)
+static bool ref_ahead_queue(mia_hip_ctx* ctx, const RefAheadKey& key, const char* src) {
+  mia_hip_ctx::RefAhead& ah = ctx->ahead;
+  const int L = key.L, wl = key.circular ? (L < MAX_READ ? L : MAX_READ) : 0, total = L + wl + 64;
+  // the twins grow as their originals do (iterate_body, align_ensure_buffers)
+  if (dev_ensure(ctx, ah.d_ref, total, (int64_t)total * 2) || dev_ensure(ctx, ah.d_planes, key.plane_words * 3) ||
+      dev_ensure(ctx, ah.d_refnib, key.nib_words, key.nib_words * 2) || dev_ensure(ctx, ah.d_khash, (int64_t)key.kslots * 4) ||
+      dev_ensure(ctx, ah.d_khash_ovf, (int64_t)key.kslots * 2) || (key.bits && !ah.d_kbits && dev_alloc(ctx, ah.d_kbits, KB_WORDS)))
+    return false;
+  const RefPrepSet twin{ah.d_ref, ctx->d_ctrl + (size_t)(1 - ctx->ctrl_half) * CTRL_WORDS, ah.d_khash, ah.d_khash_ovf, ah.d_planes, ah.d_planes.cap / 3,
+                        ah.d_refnib, key.bits ? ah.d_kbits.p : nullptr};
+  if (launch_ref_prep(ctx, twin, src, L, wl, total, key.kslots, key.kwild, key.plane_words, key.nib_words)) return false;
+  ah.key = key;
+  return true;
+}
+static void ref_ahead_speculate(mia_hip_ctx* ctx, const RefAheadKey& key, const char* src) {
+  ctx->ahead.valid = false;
+  ctx->ahead.queued = key.kwild == 0 && ref_ahead_queue(ctx, key, src);
+}
+// h_str: the string in the pinned result block, len characters
+static void ref_ahead_settle(mia_hip_ctx* ctx, const char* h_str, int64_t len, int circular) {
+  mia_hip_ctx::RefAhead& ah = ctx->ahead;
+  const bool queued = ah.queued;
+  ah.valid = false; ah.queued = false;
+  if (!queued || !ref_ahead_allowed(ctx) || len <= 0 || len > (1 << 22)) return;
+  const int L = (int)len, wl = circular ? (L < MAX_READ ? L : MAX_READ) : 0, wrap = L + wl;
+  int64_t n_other = 0, kh_entries = 0;
+  ref_count_other(h_str, L, wrap, &n_other, &kh_entries);            // (counted here instead of at the top of the call that adopts this)
+  RefAheadKey key;
+  if (!ref_ahead_want(ctx, L, circular, n_other, kh_entries, &key) || !ref_ahead_same_key(ah.key, key)) return;
+  ah.str.assign(h_str, (size_t)L);
+  ah.valid = true;
+}
+
+// ADOPTION (a hit, ref_ahead_hit): the second set becomes the context's, the half of the control block that was cleared with it the
+// current one.  Only ever from iterate_body, never while an AlignBorrow lends d_ref.p out (mia_hip_tools.inc).
+static void ref_ahead_adopt(mia_hip_ctx* ctx) {
+  mia_hip_ctx::RefAhead& ah = ctx->ahead;
+  std::swap(ctx->d_ref, ah.d_ref); std::swap(ctx->d_planes, ah.d_planes); std::swap(ctx->d_refnib, ah.d_refnib);
+  std::swap(ctx->d_khash, ah.d_khash); std::swap(ctx->d_khash_ovf, ah.d_khash_ovf);
+  if (ah.key.bits) std::swap(ctx->d_kbits, ah.d_kbits);
+  ctrl_bind(ctx, 1 - ctx->ctrl_half);
+}
+
 // ---- one whole iteration -------------------------------------------------------------------------
 // reiterate_assembly + pop_smp_from_FSDB + cull_maln_from_fsdb + consensus_assembly_string (src/mia_main.c:931-963) as
 // one call: the same kernels as mia_hip_realign / _cull / _tally / _consensus, but what those entry points hand back to
@@ -171,7 +270,7 @@ extern "C" int mia_hip_iterate(mia_hip_ctx* ctx, const char* new_ref, int32_t re
   if (!new_ref || ref_len <= 0 || !out || out_cap < 1) { ctx->err = "iterate: bad argument"; rc = MIA_HIP_ERR_ARG; }
   else if (!ctx->have_pssm || !ctx->d_packed) { ctx->err = "set_pssm and upload_reads must precede iterate"; rc = MIA_HIP_ERR_STATE; }
   else rc = iterate_body(ctx, new_ref, ref_len, circular, hard_cut, slope_intercept, cons_code, out, out_cap, out_len);
-  ctx->in_iterate = false; ctx->deferred = false;
+  ctx->in_iterate = false; ctx->deferred = false; ctx->ref_ready = false;
   // a rank that fails here will not come to the collectives the others are about to enter: tell the transport, so that
   // they return an error as well instead of waiting for ever
   if (rc != MIA_HIP_OK && ctx->comm && ctx->coll.abort) ctx->coll.abort(ctx->coll.user);
@@ -183,39 +282,61 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
   HIPCHK(hipSetDevice(ctx->device));
   // -- the new reference: ASCII up, codes and wrap made on the device (make_ref_upper / add_ref_wrap, src/mia.c:642-689)
   const int L = ref_len, wl = circular ? (L < MAX_READ ? L : MAX_READ) : 0, wrap = L + wl, total = wrap + 64;
-  int64_t n_other = 0;
-  {
-    static const struct Other { uint8_t t[256]; Other() { for (int c = 0; c < 256; c++) t[c] = base_code((char)c) > 3; } } other_of;   // (a load and an add per character)
-    for (int i = 0; i < L; i++) n_other += other_of.t[(uint8_t)new_ref[i]];
-  }
+  // REFERENCE AHEAD: the last call prepared the string it returned (ref_ahead_speculate, ref_ahead_settle).  If this is that string, what was counted on it
+  // holds, and if the call wants what was prepared (ref_ahead_hit) it adopts it.
+  mia_hip_ctx::RefAhead& ah = ctx->ahead;
+  const bool had_shadow = ah.valid;
+  ah.queued = false;
+  const bool same_string = had_shadow && ref_ahead_same_string(ah.key, ah.str.data(), new_ref, L, circular);
+  int64_t n_other = 0, kh_entries = 0;
+  if (same_string) { n_other = ah.key.n_other; kh_entries = ah.key.kh_entries; }
+  else ref_count_other(new_ref, L, wrap, &n_other, &kh_entries);
   ctx->ref_mostly_bases = n_other * 50 <= L;
   ctx->ref_few_n = n_other * 500 <= L;
-  ctx->kh_entries = 0;
-  if (n_other) {            // (kh_wild_entries over the wrapped string, without making the codes here)
-    int64_t e = 0;
-    int k = 0;
-    auto other = [&](int j) { return base_code(new_ref[j < L ? j : j - L]) > 3 ? 1 : 0; };
-    for (int pq = 0; pq < wrap; pq++) {
-      k += other(pq);
-      if (pq >= DF_K) k -= other(pq - DF_K);
-      if (pq >= DF_K - 1 && k <= BX_WILD) e += (int64_t)1 << (2 * k);
-    }
-    ctx->kh_entries = e > ((int64_t)1 << 24) ? 0 : e;
+  ctx->kh_entries = kh_entries;
+  const bool staged = ctx->h_pin && (size_t)L <= mia_hip_ctx::PIN_BYTES - mia_hip_ctx::PIN_MISC;
+  bool hit = false;
+  if (had_shadow) {
+    ah.valid = false;                        // (adopted or dropped: either way it is not there for the call after this one)
+    RefAheadKey want;
+    hit = ref_ahead_want(ctx, L, circular, n_other, kh_entries, &want) && ref_ahead_hit(ah.key, want, ah.str.data(), new_ref);
   }
-  if (dev_ensure(ctx, ctx->d_ref, total, (int64_t)total * 2) || dev_ensure(ctx, ctx->d_ascii, L, (int64_t)L * 2)) return MIA_HIP_ERR_NOMEM;
-  if (ctx->h_pin && (size_t)L <= mia_hip_ctx::PIN_BYTES - mia_hip_ctx::PIN_MISC) {
-    HIPCHK(hipStreamSynchronize(ctx->stream));             // the staging area may still feed an earlier copy
-    memcpy(ctx->h_pin + mia_hip_ctx::PIN_MISC, new_ref, (size_t)L);
-    // (zero_copy: the step's first kernel reads the sixteen thousand characters from the pinned area itself -- a copy in
-    // front of it is a second engine and a wait between the two before anything runs)
-    if (ctx->zero_copy) ctx->ascii_src = reinterpret_cast<const char*>(ctx->h_pin + mia_hip_ctx::PIN_MISC);
-    else { HIPCHK(hipMemcpyAsync(ctx->d_ascii, ctx->h_pin + mia_hip_ctx::PIN_MISC, (size_t)L, hipMemcpyHostToDevice, ctx->stream)); ctx->ascii_src = ctx->d_ascii; }
+  // A MISS waits for the stream as the call always did (the staging area may still feed an earlier copy), and with that for the
+  // shadow launch; if that gave its barrier up, the word is cleared here: a call that uses nothing of it must not fail for it.
+  // A HIT does not wait.  Everything that reads the adopted tables is queued behind the shadow launch on this stream, or behind an
+  // event of this stream; the caller is usually back before the launch has ended (it is queued some 30 us before the call returns and
+  // runs for 20), and a wait here put the plan's launch latency behind it -- measured: with the wait the step was as long as without
+  // the shadow launch.  The stream is ASKED once: if the launch has ended and gave up, the call is a miss; if it has not ended,
+  // the check behind the step's own wait finds the word, as it does for the call's own k_ref_prep (the iteration is void then).
+  uint32_t* stuck = ctx->h_pin ? reinterpret_cast<uint32_t*>(ctx->h_pin + (62 << 10)) : nullptr;
+  bool shadow_ended = !hit;
+  if (hit) {
+    const hipError_t eq = hipStreamQuery(ctx->stream);
+    if (eq != hipErrorNotReady) { HIPCHK(eq); shadow_ended = true; }
+  } else if (staged || had_shadow) HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (had_shadow && shadow_ended && stuck && *stuck) {
+    *stuck = 0;
+    ctx->no_prep_fuse = true;                // (from now on: six plain launches, and no shadow launch)
+    hit = false;
+  }
+  if (hit) {
+    ref_ahead_adopt(ctx);
   } else {
-    HIPCHK(hipMemcpyAsync(ctx->d_ascii, new_ref, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
-    ctx->ascii_src = ctx->d_ascii;
+    if (dev_ensure(ctx, ctx->d_ref, total, (int64_t)total * 2) || dev_ensure(ctx, ctx->d_ascii, L, (int64_t)L * 2)) return MIA_HIP_ERR_NOMEM;
+    if (staged) {
+      memcpy(ctx->h_pin + mia_hip_ctx::PIN_MISC, new_ref, (size_t)L);
+      // (zero_copy: the step's first kernel reads the sixteen thousand characters from the pinned area itself -- a copy in
+      // front of it is a second engine and a wait between the two before anything runs)
+      if (ctx->zero_copy) ctx->ascii_src = reinterpret_cast<const char*>(ctx->h_pin + mia_hip_ctx::PIN_MISC);
+      else { HIPCHK(hipMemcpyAsync(ctx->d_ascii, ctx->h_pin + mia_hip_ctx::PIN_MISC, (size_t)L, hipMemcpyHostToDevice, ctx->stream)); ctx->ascii_src = ctx->d_ascii; }
+    } else {
+      HIPCHK(hipMemcpyAsync(ctx->d_ascii, new_ref, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+      ctx->ascii_src = ctx->d_ascii;
+    }
+    // (the codes are made by align_all's first launch: k_ref_prep with everything else that is derived from the reference, or k_ref_encode)
+    ctx->pend_encode = true; ctx->pend_L = L; ctx->pend_wl = wl; ctx->pend_total = total;
   }
-  // (the codes are made by align_all's first launch: k_ref_prep with everything else that is derived from the reference, or k_ref_encode)
-  ctx->pend_encode = true; ctx->pend_L = L; ctx->pend_wl = wl; ctx->pend_total = total;
+  ctx->ref_ready = hit;
   if (ctx->rs.n == 0) { encode_now(ctx); HIPCHK(hipGetLastError()); }
   const bool dbg_steps = alt_env("MIA_HIP_ITER_DEBUG") != nullptr;      // diagnostic: wait and report after every stage
   // MIA_HIP_TIMING=1 (release builds too): host time at every stage boundary, no waits added -- where the HOST is held up (allocations, copies)
@@ -225,7 +346,7 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
     if (dbg_steps) { hipError_t e = hipStreamSynchronize(ctx->stream); fprintf(stderr, "[mia_hip_iterate] %s: %s\n", what, hipGetErrorString(e)); fflush(stderr); }
     if (host_laps) fprintf(stderr, "[mia_hip_iterate host] %-20s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - lap_t0).count());
   };
-  checkpoint("reference");
+  checkpoint(hit ? "reference (ahead)" : "reference");
   ctx->L = L; ctx->wrap = wrap; ctx->have_ref = true; ctx->explicit_win = 0;
   const int64_t n = ctx->rs.n;
   const int W = ctx->comm_ranks;
@@ -241,7 +362,7 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
   const int rca = align_all(ctx);
   ctx->deferred = false;
   ctx->spec_ok = false;
-  ctx->pend_encode = false;                 // (never outlives the call)
+  ctx->pend_encode = false; ctx->ref_ready = false;      // (never outlive the call)
   if (rca) { ctx->spec_pending = false; ctx->abort_if = nullptr; return rca; }
   checkpoint("realign");
   int64_t slot_base = 0, g_sums[5] = {0, 0, 0, 0, 0};
@@ -399,8 +520,10 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
   }
   const int64_t cons_cap = (int64_t)L + ctx->ins_tally_cap + 64;          // string bytes
   const int64_t res_bytes = (int64_t)CH_WORDS * 4 + cons_cap;
-  if (dev_ensure(ctx, ctx->d_cons, res_bytes, res_bytes * 2) || dev_ensure(ctx, ctx->d_cons_pos, Lp, (int64_t)Lp * 2)) return MIA_HIP_ERR_NOMEM;
   const size_t need = (size_t)res_bytes;
+  // (the result blocks are about to move: a shadow launch that this call adopted without waiting may still be reading the last string)
+  if (res_bytes > ctx->d_cons.cap || need > ctx->pin2_bytes) HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (dev_ensure(ctx, ctx->d_cons, res_bytes, res_bytes * 2) || dev_ensure(ctx, ctx->d_cons_pos, Lp, (int64_t)Lp * 2)) return MIA_HIP_ERR_NOMEM;
   if (need > ctx->pin2_bytes) {
     if (ctx->h_pin2) (void)hipHostFree(ctx->h_pin2);
     ctx->h_pin2 = nullptr; ctx->pin2_bytes = 0;
@@ -409,6 +532,10 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
   }
   int32_t* h_hdr = reinterpret_cast<int32_t*>(ctx->h_pin2);
   char* h_str = reinterpret_cast<char*>(ctx->h_pin2) + CH_WORDS * 4;
+  // REFERENCE AHEAD, speculatively (ref_ahead_speculate): one context, the string written to the host by k_cons_scatter itself, a
+  // reference of plain bases -- the key of a consensus as long as its reference and as free of N
+  RefAheadKey spec_key;
+  bool spec_ahead = !ctx->comm && ctx->zero_copy && n_other == 0 && ref_ahead_allowed(ctx) && ref_ahead_want(ctx, L, circular, 0, 0, &spec_key);
   // consensus calls, the string consensus_assembly_string returns put together on the device (characters per column, their
   // prefix sums, a scatter), header and string back in one copy, the second and last wait
   auto consensus_tail = [&]() -> int {
@@ -437,13 +564,15 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
                        (const int32_t*)ctx->d_ins_off, ctx->d_ins_tally, cons_code, (const char*)ctx->d_calls, ctx->d_ins_calls, (int32_t)cap,
                        (const int32_t*)ctx->d_ins_total, ctx->d_cons_pos, ctx->abort_if);
     if (!fused_scans) hipLaunchKernelGGL(k_excl_scan, dim3(1), dim3(1024), 0, ctx->stream, (const int32_t*)ctx->d_cons_pos, L, 0, L, ctx->d_cons_pos, d_res + CH_LEN, ctx->abort_if);
-    hipLaunchKernelGGL(k_cons_scatter, dim3(gl), dim3(256), 0, ctx->stream, (const char*)ctx->d_calls, (const char*)ctx->d_ins_calls,
+    // (with a shadow launch behind it the kernel signals ev_cons itself: the host waits for that, the stream goes on)
+    launch_k(k_cons_scatter, dim3(gl), dim3(256), 0, ctx->stream, spec_ahead ? ctx->ev_cons : (hipEvent_t) nullptr, (const char*)ctx->d_calls, (const char*)ctx->d_ins_calls,
                        (const int32_t*)ctx->tb.gaps, (const int32_t*)ctx->d_ins_off, L, (int32_t)cap, (const int32_t*)ctx->d_ins_total,
                        (const int32_t*)ctx->d_cons_pos, d_res, (int32_t)cons_cap, (const int32_t*)ctx->tb.n_events, (const uint32_t*)ctx->tb.flags,
                        (const uint32_t*)ctx->d_cull_flags, ctx->abort_if, zc ? reinterpret_cast<int32_t*>(ctx->h_pin2) : (int32_t*)nullptr,
-                       (const int32_t*)(ctx->d_ctrl + CTRL_C0), (int32_t)CTRL_CN, (zc && ctx->spec_pending) ? reinterpret_cast<int32_t*>(ctx->h_pin) : (int32_t*)nullptr,
+                       ctx->d_ctr0, (int32_t)CTRL_CN, (zc && ctx->spec_pending) ? reinterpret_cast<int32_t*>(ctx->h_pin) : (int32_t*)nullptr,
                        fused_scans ? 1 : 0, ctx->comm ? (const int32_t*)(ctx->tb.gaps + Lp + W) : (const int32_t*)nullptr);
     HIPCHK(hipGetLastError());
+    if (spec_ahead) ref_ahead_speculate(ctx, spec_key, h_str);
     checkpoint("assemble");
     if (!zc) HIPCHK(hipMemcpyAsync(ctx->h_pin2, ctx->d_cons, need, hipMemcpyDeviceToHost, ctx->stream));
     if (ctx->comm && !counted) HIPCHK(hipMemcpyAsync(h_evc, ctx->tb.gaps + Lp, (size_t)W * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -451,9 +580,10 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
     // sleeping on an interrupt (MIA_HIP_SPIN_WAIT=0: hipStreamSynchronize)
     if (ctx->spin_wait) {
       hipError_t eq;
-      while ((eq = hipStreamQuery(ctx->stream)) == hipErrorNotReady) {}
+      while ((eq = spec_ahead ? hipEventQuery(ctx->ev_cons) : hipStreamQuery(ctx->stream)) == hipErrorNotReady) {}
       HIPCHK(eq);
-    } else HIPCHK(hipStreamSynchronize(ctx->stream));
+    } else if (spec_ahead) HIPCHK(hipEventSynchronize(ctx->ev_cons));
+    else HIPCHK(hipStreamSynchronize(ctx->stream));
     return MIA_HIP_OK;
   };
   if (int rct = consensus_tail()) return rct;
@@ -482,6 +612,8 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
       if (n_wide > 0) { if (int rcw = run_wide(ctx, rinfo, n_wide)) return rcw; }
       if (int rcq = queue_cull()) return rcq;
       if (int rct = tally_launch(ctx)) return rct;
+      // (the speculative shadow launch read a string the aborted tail never wrote: it is dropped, and none rides on the second round)
+      spec_ahead = false; ctx->ahead.queued = false;
       if (int rct = consensus_tail()) return rct;
     }
   }
@@ -511,6 +643,7 @@ static int iterate_body(mia_hip_ctx* ctx, const char* new_ref, int32_t ref_len, 
   }
   const int64_t len = h_hdr[CH_LEN];
   if (len + 1 > out_cap) { ctx->err = "consensus buffer too small"; return MIA_HIP_ERR_ARG; }
+  ref_ahead_settle(ctx, h_str, len, circular);       // (in front of the copy: the device works while the host copies and returns)
   memcpy(out, h_str, (size_t)len);
   out[len] = 0;
   if (out_len) *out_len = len;

@@ -871,6 +871,9 @@ static void build_kmer_lists(const std::string& seq, int k, int soft_mask, std::
 //   rejects from them (AlignRouteIn::rejects), which moves reads between exact kernels and changes no result; bx_launches, band_done,
 //   direct_open_steps and quick_steps, which are statistics; align_end_signalled, which every alignment sets anew before anything
 //   reads it; and the buffers the borrowed run grows (trace slabs, the open list and the like), which every alignment sizes for itself.
+//   REFERENCE AHEAD: d_ref is lent by its raw pointer, and ref_ahead_adopt swaps d_ref's block for its twin's.  The two never meet: adoption
+//   happens at the top of iterate_body alone, a borrow lives inside one mia_hip_pass1 call, and neither calls the other.  ref_mostly_bases
+//   and kh_entries, restored here, are the context's; what the shadow launch counted lives in ctx->ahead.key and is not lent.
 static auto align_lent_fields(mia_hip_ctx* c) {
   return std::tie(c->rs, c->d_bin_of.p, c->d_list.p, c->d_wide_list.p, c->d_retry_list.p, c->max_len, c->d_ref.p, c->L, c->wrap, c->explicit_win,
                   c->use_filter, c->aligned, c->culled, c->tallied, c->pre_cull_valid, c->ref_mostly_bases, c->diag_scripts_missing, c->kh_entries,

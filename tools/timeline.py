@@ -2,7 +2,10 @@ import csv,sys,glob
 f=glob.glob(sys.argv[1]+'/**/*kernel_trace.csv',recursive=True)[0]
 rows=list(csv.DictReader(open(f)))
 rows.sort(key=lambda r:int(r['Start_Timestamp']))
-idx=[i for i,r in enumerate(rows) if 'k_ref_encode' in r['Kernel_Name'] or 'k_ref_prep' in r['Kernel_Name']]
+# a step begins with the reference's preparation -- or, named as the second argument, with another kernel (with the reference prepared
+# ahead, behind the consensus, a steady step of mia_hip_iterate begins with the quick plan: 'k_bx_plan<2, 5>')
+marks=sys.argv[2:] or ['k_ref_encode','k_ref_prep']
+idx=[i for i,r in enumerate(rows) if any(m in r['Kernel_Name'] for m in marks)]
 a,b=idx[-3],idx[-2]
 t0=int(rows[a]['Start_Timestamp'])
 prev_end=t0
