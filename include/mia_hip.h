@@ -150,6 +150,11 @@ int mia_hip_links(mia_hip_ctx *ctx, int64_t **d_links, int64_t *n_links);
 int mia_hip_set_links(mia_hip_ctx *ctx, const int64_t *d_links_all, int64_t n_all);
 int mia_hip_link_lengths(mia_hip_ctx *ctx, int32_t **d_len, int32_t **d_act, int64_t *n);
 int mia_hip_finish_links(mia_hip_ctx *ctx);
+/* The last cull: links_before = the links it was going to emit, counted before it ran (-1 where the count is not taken);
+ * lean = 1 if it ran inside mia_hip_iterate without a communicator and without a link, and therefore left the per-read slot
+ * numbers and the per-read / per-slot link side arrays unwritten.  After such a cull mia_hip_set_links, mia_hip_link_lengths
+ * and mia_hip_finish_links return MIA_HIP_ERR_STATE until mia_hip_cull has run again. */
+int mia_hip_cull_stats(mia_hip_ctx *ctx, int64_t *links_before, int32_t *lean);
 
 /* find_fsdb_score_cut (src/fsdb.c:269-383) -- HOST helper, no device work: the
  * reference's least-squares line through (seq_len, score) of all unique_best

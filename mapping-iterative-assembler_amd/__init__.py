@@ -87,6 +87,8 @@ def _load(path=None):
     lib.mia_hip_set_links.argtypes = [vp, vp, C.c_int64]
     lib.mia_hip_link_lengths.argtypes = [vp, P(vp), P(vp), P(C.c_int64)]
     lib.mia_hip_finish_links.argtypes = [vp]
+    if hasattr(lib, "mia_hip_cull_stats"):        # (MIA_HIP_LIB may name an older build, for A/B timing)
+        lib.mia_hip_cull_stats.argtypes = [vp, P(C.c_int64), P(C.c_int32)]
     lib.mia_hip_plain_stats.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_int64), P(C.c_int64), P(C.c_int64)]
     lib.mia_hip_score_sums.argtypes = [vp, vp]
     lib.mia_hip_score_cut_from_sums.argtypes = [vp, P(C.c_double), P(C.c_double)]
@@ -168,7 +170,7 @@ def exported_symbols():
             "mia_hip_tally", "mia_hip_tally_buffers", "mia_hip_ins_events", "mia_hip_set_ins_events",
             "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_ma_mask", "mia_hip_get_ma_mask", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_trim_rerun_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
             "mia_hip_get_record_params", "mia_hip_set_read_base", "mia_hip_links", "mia_hip_set_links", "mia_hip_link_lengths",
-            "mia_hip_finish_links", "mia_hip_plain_stats", "mia_hip_score_sums",
+            "mia_hip_finish_links", "mia_hip_cull_stats", "mia_hip_plain_stats", "mia_hip_score_sums",
             "mia_hip_score_cut_from_sums", "mia_hip_stage_stats", "mia_hip_measure_peaks", "mia_hip_measure_issue", "mia_hip_set_tally", "mia_hip_iterate", "mia_hip_set_stage_mask", "mia_hip_comm_unique_id", "mia_hip_comm_init", "mia_hip_comm_destroy",
             "mia_hip_comm_attach", "mia_hip_comm_info", "mia_hip_loopback_create", "mia_hip_loopback_table", "mia_hip_loopback_destroy"]
 
@@ -875,6 +877,12 @@ class MiaHip:
 
     def finish_links(self):
         self._chk(self._l.mia_hip_finish_links(self._h))
+
+    def cull_stats(self):
+        """(links counted before the last cull, -1 if they were not; whether that cull ran in its lean form): mia_hip_cull_stats."""
+        n, lean = C.c_int64(), C.c_int32()
+        self._chk(self._l.mia_hip_cull_stats(self._h, C.byref(n), C.byref(lean)))
+        return n.value, bool(lean.value)
 
     def plain_stats(self, reset=False):
         """(ms, launches, reads in, reads re-run with a trace) of the values-only first pass."""

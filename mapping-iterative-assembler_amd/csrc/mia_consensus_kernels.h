@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cull_body.h"
 #include "ma_records.h"
 #include "mia_kernels.h"
 #include "mia_layout.h"
@@ -25,19 +26,7 @@ struct TallyBuf {
   uint32_t* flags;     // bit 0: event list overflow, bit 1: geometry the reference leaves undefined
 };
 
-// how a read's alignment maps onto AlnSeq records (src/mia_main.c:259-276, src/mia.c:1376-1438)
-struct RecGeom {
-  int start_w, end, split, ncols_f, ncols_b;
-};
-MIA_HD inline RecGeom rec_geom(int as, int ae, int L) {
-  RecGeom g;
-  g.start_w = as;
-  g.end = ae > L ? ae - L : ae;
-  g.split = as > g.end;
-  g.ncols_f = g.split ? (L - as) : (g.end - as + 1);
-  g.ncols_b = g.split ? g.end + 1 : 0;
-  return g;
-}
+// (RecGeom / rec_geom, the record and link counts of a read and the raw-count arithmetic: cull_body.h)
 
 // ---- records per read + exclusive scan -> AlnSeq slot of every read ---------------
 __global__ void k_scan_blocks(ReadSet rs, int32_t L, int64_t* partial) {
@@ -201,15 +190,18 @@ __device__ __forceinline__ void rec_write(const ReadSet& rs, int64_t i, int32_t*
 }
 
 // ... the same record as four 16-byte words in registers (k_cull_records hands a wavefront's records over through LDS: rec_store_wave)
-__device__ __forceinline__ void rec_make(const ReadSet& rs, int64_t i, uint8_t* drop_front, uint8_t* drop_back, uint8_t df, uint8_t db, const int32_t* p,
-                                         uint32_t st, int32_t actf, const int32_t* umax, int4* r4) {
-  drop_front[i] = df;
-  drop_back[i] = db;
-  const int fl = (rs.rc[i] ? TRF_RC : 0) | (df ? TRF_DF : 0) | (db ? TRF_DB : 0) | ((st & ST_DIAG) ? TRF_DIAG : 0) |
-                 ((st & ST_TOO_LONG) ? TRF_TOO_LONG : 0) | (rs.sk[i] ? TRF_SK : 0) | ((st & ST_ONEGAP) ? TRF_ONEGAP : 0) |
-                 ((umax && umax[i] >= 0) ? TRF_NO_N : 0);
-  r4[0] = make_int4(rs.as[i], rs.ae[i], (int32_t)((uint32_t)rs.len[i] | ((uint32_t)(uint16_t)rs.abr[i] << 16)), fl);
-  r4[1] = make_int4(rs.refstart[i], (int32_t)rs.roff[i], actf, (int32_t)(st >> 8));
+// v: the read's own values, loaded by the caller in one go (no_n: umax[i] >= 0)
+struct RecVals {
+  int32_t as, ae, len, abr, refstart;
+  uint32_t roff;
+  bool rc, sk, no_n;
+};
+__device__ __forceinline__ void rec_make(const RecVals& v, uint8_t df, uint8_t db, const int32_t* p, uint32_t st, int32_t actf, int4* r4) {
+  const int fl = (v.rc ? TRF_RC : 0) | (df ? TRF_DF : 0) | (db ? TRF_DB : 0) | ((st & ST_DIAG) ? TRF_DIAG : 0) |
+                 ((st & ST_TOO_LONG) ? TRF_TOO_LONG : 0) | (v.sk ? TRF_SK : 0) | ((st & ST_ONEGAP) ? TRF_ONEGAP : 0) |
+                 (v.no_n ? TRF_NO_N : 0);
+  r4[0] = make_int4(v.as, v.ae, (int32_t)((uint32_t)v.len | ((uint32_t)(uint16_t)v.abr << 16)), fl);
+  r4[1] = make_int4(v.refstart, (int32_t)v.roff, actf, (int32_t)(st >> 8));
   r4[2] = make_int4(p[0], p[1], p[2], p[3]);
   r4[3] = make_int4(p[4], p[5], p[6], p[7]);
 }
@@ -251,16 +243,24 @@ struct Links {                // [cap][4] int64: reader (global read index), slo
 // inserted bases per record and bases in the front: one read per wavefront (the script walk of the tally's pass A)
 // A block takes 256 reads.  Proven-diagonal reads (ST_DIAG, the large majority) need no script: one thread each.  The
 // others are walked by the block's four wavefronts, 64 script rows at a time (ballot counts).
+// n_local: the slots this context owns.  lean (k_cull_records in an iteration without a link): nothing will read the side arrays --
+// only the test that the read's slots are this context's own remains
+__device__ __forceinline__ void rec_store_val(int64_t i, const RecGeom& g, int nf, int nb, int af, int bases, int64_t slot_i, const RecInfo& ri,
+                                              const SlotInfo& si, int64_t read_base, uint32_t* flags, int64_t n_local, bool lean) {
+  const int flen = g.ncols_f + nf, blen = g.split ? g.ncols_b + nb : 0;
+  if (!lean) { ri.flen[i] = flen; ri.blen[i] = blen; ri.actf[i] = af + nf; }
+  const int64_t ls = slot_i - si.base;
+  if (ls >= 0 && ls + (g.split ? 1 : 0) < n_local) {
+    if (!lean) {
+      const unsigned long long me = ((unsigned long long)(read_base + i) << 20) | LINK_NONE;
+      si.reclen[ls] = flen; si.recact[ls] = af + nf; si.mult[ls] = 1; si.writer[ls] = me;
+      if (g.split) { si.reclen[ls + 1] = blen; si.recact[ls + 1] = bases - (af + nf); si.mult[ls + 1] = 1; si.writer[ls + 1] = me; }
+    }
+  } else atomicOr(flags, 4u);
+}
 __device__ __forceinline__ void rec_store_at(int64_t i, const RecGeom& g, int nf, int nb, int af, int bases, int64_t slot_i, RecInfo& ri,
                                              SlotInfo& si, int64_t read_base, uint32_t* flags) {
-  const int flen = g.ncols_f + nf, blen = g.split ? g.ncols_b + nb : 0;
-  ri.flen[i] = flen; ri.blen[i] = blen; ri.actf[i] = af + nf;
-  const int64_t ls = slot_i - si.base;
-  if (ls >= 0 && ls + (g.split ? 1 : 0) < (*si.n_local_p)) {
-    const unsigned long long me = ((unsigned long long)(read_base + i) << 20) | LINK_NONE;
-    si.reclen[ls] = flen; si.recact[ls] = af + nf; si.mult[ls] = 1; si.writer[ls] = me;
-    if (g.split) { si.reclen[ls + 1] = blen; si.recact[ls + 1] = bases - (af + nf); si.mult[ls + 1] = 1; si.writer[ls + 1] = me; }
-  } else atomicOr(flags, 4u);
+  rec_store_val(i, g, nf, nb, af, bases, slot_i, ri, si, read_base, flags, *si.n_local_p, false);
 }
 __device__ __forceinline__ void rec_store(int64_t i, const RecGeom& g, int nf, int nb, int af, int bases, const int64_t* slot, RecInfo& ri,
                                           SlotInfo& si, int64_t read_base, uint32_t* flags) {
@@ -346,47 +346,67 @@ __global__ __launch_bounds__(256) void k_rec_geom(ReadSet rs, int32_t L, const i
   }
 }
 
+// the mark byte of every read from its two pointers (cull_body.h: cull_link_mark), after the host has set them
+__global__ void k_link_marks(int64_t n, const int64_t* back_slot, const int64_t* front_slot0, uint8_t* link_mark) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) link_mark[i] = (uint8_t)cull_link_mark(back_slot[i], front_slot0[i]);
+}
+
 // ---- the cull's first half as two launches (mia_hip_cull; k_scan_blocks / _partials / _apply, k_rec_geom and k_cull_mark
 // above remain for the entry points that need one of them alone) -----------------------------------------------------------
 // k_slot_count: AlnSeq records per stretch of 256 reads (a workgroup takes sixteen stretches one after the other: one
 // arrival per 4 096 reads -- a counter every block of 256 adds to is served one add at a time, 80 us for a million reads);
 // the workgroup that arrives last turns the counts into exclusive offsets (+ base) and leaves the total in *total.
 // nb: stretches.  *blocks_done must be 0 on entry and is 0 again on exit.
-__global__ __launch_bounds__(256) void k_slot_count(ReadSet rs, int32_t L, int64_t* partial, int nb, int64_t base, int64_t* total, uint32_t* blocks_done, const int32_t* abort_if = nullptr) {
+__global__ __launch_bounds__(256) void k_slot_count(ReadSet rs, int32_t L, int64_t* partial, int nb, int64_t base, int64_t* total, uint32_t* blocks_done, const int32_t* abort_if = nullptr,
+                                                      const uint8_t* __restrict__ link_mark = nullptr) {
   if (abort_if && *abort_if != 0) return;     // (mia_hip_iterate queued this launch before the alignment's exact-kernel count was known: see iterate_body)
   __shared__ bool last;
   __shared__ int64_t s_run[256];
-  __shared__ int32_t wsum[16][4];
+  __shared__ int32_t wsum[16][4], lsum[4];
   // stretch k of this workgroup = reads base + 256 k .. + 255, one per thread (neighbouring threads, neighbouring reads)
   const int64_t base_read = (int64_t)blockIdx.x * 4096;
   // (all sixteen stretches' loads first: one after the other, each waited for, they were 25 of this kernel's 40 us)
-  uint8_t sk16[16];
+  // link_mark: the links this iteration will emit are counted on the way (cull_links_marked; one byte per read -- with the two 8-byte
+  // pointers themselves this kernel took 20 us instead of 12) -- k_cull_records learns from their sum whether anything will read the
+  // per-read and per-slot side arrays it would otherwise write
+  uint8_t sk16[16], mk16[16];
   int32_t as16[16], ae16[16];
 #pragma unroll
   for (int k = 0; k < 16; k++) {
     const int64_t i = base_read + k * 256 + threadIdx.x;
     const bool in = i < rs.n;
-    sk16[k] = in ? rs.sk[i] : (uint8_t)0;
+    sk16[k] = in ? rs.sk[i] : (uint8_t)1;
     as16[k] = in ? rs.as[i] : 0;
     ae16[k] = in ? rs.ae[i] : 0;
+    mk16[k] = (in && link_mark) ? link_mark[i] : (uint8_t)0;
   }
+  int my_links = 0;
 #pragma unroll
   for (int k = 0; k < 16; k++) {
-    const int cnt = sk16[k] ? (rec_geom(as16[k], ae16[k], L).split ? 2 : 1) : 0;
+    const int64_t i = base_read + k * 256 + threadIdx.x;
+    const bool in = i < rs.n;
+    const int cnt = in ? cull_records(sk16[k] != 0, as16[k], ae16[k], L) : 0;
     const int w = __popcll(__ballot(cnt >= 1)) + __popcll(__ballot(cnt == 2));
     if ((threadIdx.x & 63) == 0) wsum[k][threadIdx.x >> 6] = w;
+    my_links += cull_links_marked(sk16[k] != 0, cnt == 2, mk16[k]);
   }
+#pragma unroll
+  for (int o = 32; o; o >>= 1) my_links += __shfl_xor(my_links, o);
+  if ((threadIdx.x & 63) == 0) lsum[threadIdx.x >> 6] = my_links;
   __syncthreads();
   if (threadIdx.x < 16 && blockIdx.x * 16 + (int)threadIdx.x < nb)
     partial[blockIdx.x * 16 + threadIdx.x] = (int64_t)wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
   if (!blocks_done) {
     // the counts alone, and behind them (partial[nb + workgroup]) this workgroup's sum: k_cull_records adds up what lies before
-    // each of its blocks itself (raw_nb) -- the arrival below, with its device-scope fence per workgroup, was 25 of this
+    // each of its blocks itself (cull_share) -- the arrival below, with its device-scope fence per workgroup, was 25 of this
     // kernel's 40 us, and a single-workgroup scan between the two kernels (k_scan_partials) another 15
+    // ... and behind those (partial[nb + workgroups + workgroup]) this workgroup's links
     if (threadIdx.x == 0) {
       int64_t g = 0;
       for (int k = 0; k < 16; k++) g += (int64_t)wsum[k][0] + wsum[k][1] + wsum[k][2] + wsum[k][3];
       partial[nb + blockIdx.x] = g;
+      partial[nb + cull_groups(nb) + blockIdx.x] = (int64_t)lsum[0] + lsum[1] + lsum[2] + lsum[3];
     }
     return;
   }
@@ -416,63 +436,91 @@ __global__ __launch_bounds__(256) void k_slot_count(ReadSet rs, int32_t L, int64
 
 // k_cull_records: slot numbers (k_scan_apply), record geometry (k_rec_geom) and the reads' own dropped marks / back slots /
 // links (k_cull_mark) of a block of 256 reads in one go: what the three kernels hand each other per read stays in registers.
-__global__ __launch_bounds__(256) void k_cull_records(ReadSet rs, int32_t L, const int64_t* partial, int64_t* slot, RecInfo ri, SlotInfo si, int64_t read_base,
-                                                        uint32_t* flags, uint8_t* slot_dropped, int64_t n_slots, int32_t hard_cut, double slope, double intercept,
-                                                        int64_t* back_slot, const int64_t* front_slot0, Links lk, const double* dev_cut, const int32_t* abort_if = nullptr,
+// One round trip to memory per read: everything the block needs of its 256 reads is loaded at the top, side by side with
+// the raw counts, and the record is made from those registers (rec_make takes values).  Only slot_dropped[my_slot] waits
+// for the scan.  (Field by field, each load behind the branch that wanted it -- sk; as, ae; status; len, abr; score;
+// back_slot; then every one of them again for the record, since stores through ri / si lay in between -- the kernel was
+// eight dependent round trips long and moved its bytes at half the rate of a copy.)
+// lean_ok (mia_hip_iterate without a communicator): in an iteration whose link count -- taken by k_slot_count, summed here
+// beside the record total -- is 0, nothing reads slot[], ri.flen / blen / actf or si.reclen / recact / mult / writer: their
+// only readers are k_links_apply, k_rec_params behind its skip_if_no_links return, k_cull_mark and k_rec_geom.  They are
+// not written then (36 of 109 written bytes per read).  With a link, everything is written for every read as before.
+// stats (block 0): {links counted beforehand or -1, 1 if the lean form ran}
+__global__ __launch_bounds__(256) void k_cull_records(ReadSet rs, int32_t L, const int64_t* __restrict__ partial, int64_t* __restrict__ slot, RecInfo ri, SlotInfo si,
+                                                        int64_t read_base, uint32_t* flags, uint8_t* __restrict__ slot_dropped, int64_t n_slots, int32_t hard_cut,
+                                                        double slope, double intercept, int64_t* __restrict__ back_slot, const int64_t* __restrict__ front_slot0, Links lk,
+                                                        const double* __restrict__ dev_cut, const int32_t* abort_if = nullptr,
                                                         int32_t raw_nb = 0, int64_t slot_base = 0, int64_t* total_out = nullptr,
-                                                        int32_t with_records = 0, uint8_t* drop_front = nullptr, uint8_t* drop_back = nullptr, const int32_t* umax = nullptr) {
+                                                        int32_t with_records = 0, uint8_t* __restrict__ drop_front = nullptr, uint8_t* __restrict__ drop_back = nullptr,
+                                                        const int32_t* __restrict__ umax = nullptr, int32_t lean_ok = 0, int32_t* __restrict__ stats = nullptr,
+                                                        uint32_t* apply_ticket = nullptr, int32_t* link_len = nullptr, int32_t* link_act = nullptr,
+                                                        uint8_t* __restrict__ link_mark = nullptr) {
   if (abort_if && *abort_if != 0) return;     // (mia_hip_iterate queued this launch before the alignment's exact-kernel count was known: see iterate_body)
   __shared__ int32_t wsum[4];
-  __shared__ int64_t s_red[2][4], s_first, s_total;
+  __shared__ int64_t s_red[3][4];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (raw_nb) {
-    // partial[] holds k_slot_count's counts as they are -- per block of 256 reads, and from [raw_nb] on per sixteen blocks:
-    // the first slot of this block = slot_base + the sixteens before its own + the blocks before it in its sixteen
-    const int ng = (raw_nb + 15) >> 4, myg = (int)(blockIdx.x >> 4);
-    int64_t pre = 0, tot = 0;
-    for (int g = threadIdx.x; g < ng; g += 256) { const int64_t v = partial[raw_nb + g]; tot += v; if (g < myg) pre += v; }
-    if (threadIdx.x < 16) { const int b = myg * 16 + (int)threadIdx.x; if (b < (int)blockIdx.x) pre += partial[b]; }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) { pre += __shfl_xor(pre, o); tot += __shfl_xor(tot, o); }
-    if (lane == 0) { s_red[0][wv] = pre; s_red[1][wv] = tot; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      s_first = slot_base + s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
-      s_total = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
-      if (blockIdx.x == 0 && total_out) *total_out = s_total;
-    }
-    si.n_local_p = &s_total;                  // (rec_store_at reads the total through the pointer: this block's own sum, not a word another block is writing)
-  }
   const int64_t i0 = (int64_t)blockIdx.x * 256 + (threadIdx.x & ~63);     // first read of this wavefront
   const int64_t me = i0 + lane;
   const bool in = me < rs.n;
-  const bool sk = in && rs.sk[me];
-  int as_me = 0, ae_me = 0;
-  if (sk) { as_me = rs.as[me]; ae_me = rs.ae[me]; }
-  const RecGeom g_me = rec_geom(as_me, ae_me, L);
+  // ---- every load of this read, none behind a branch: a lane past the end loads the last read's values (the grid has no
+  // block without a read) and uses none of them
+  const int64_t ix = in ? me : rs.n - 1;
+  RecVals v;
+  v.sk = rs.sk[ix] != 0; v.rc = rs.rc[ix] != 0;
+  v.as = rs.as[ix]; v.ae = rs.ae[ix]; v.len = rs.len[ix]; v.abr = rs.abr[ix]; v.refstart = rs.refstart[ix]; v.roff = rs.roff[ix];
+  const int32_t score_me = rs.score[ix];
+  uint32_t my_st = rs.status[ix];                    // (the walk below may rewrite a read's status: its own lane keeps the new one)
+  const int mark_me = link_mark[ix];               // (cull_link_mark: which of the read's two pointers are set; the pointers themselves are looked at only where a link follows)
+  // (no branch around this load either -- behind one, the compiler waits for every load above before the raw counts are asked
+  // for: without the N marks it reads a word of `as` instead and drops it)
+  const int32_t umax_me = (umax ? umax : (const int32_t*)rs.as)[ix];
+  if (dev_cut) { slope = dev_cut[0]; intercept = dev_cut[1]; }   // the line of find_fsdb_score_cut, left on the device
+  int64_t first = 0, n_local = 0, n_links = -1;
+  if (raw_nb) {
+    // partial[] holds k_slot_count's counts as they are (cull_body.h): the first slot of this block = slot_base + the
+    // sixteens before its own + the blocks before it in its sixteen
+    CullShare sh = cull_share(partial, raw_nb, (int)blockIdx.x, (int)threadIdx.x, 256);
+#pragma unroll
+    for (int o = 32; o; o >>= 1) { sh.pre += __shfl_xor(sh.pre, o); sh.tot += __shfl_xor(sh.tot, o); sh.links += __shfl_xor(sh.links, o); }
+    if (lane == 0) { s_red[0][wv] = sh.pre; s_red[1][wv] = sh.tot; s_red[2][wv] = sh.links; }
+  } else {
+    first = partial[blockIdx.x];
+    n_local = *si.n_local_p;
+  }
+  const bool sk = in && v.sk;
+  const RecGeom g_me = rec_geom(sk ? v.as : 0, sk ? v.ae : 0, L);
   // ---- slot of every read: exclusive scan of the record counts (1, or 2 when split at the origin) over the block
   const int cnt = sk ? (g_me.split ? 2 : 1) : 0;
   const unsigned long long m1 = __ballot(cnt >= 1), m2 = __ballot(cnt == 2), below = (1ull << lane) - 1ull;
   if (lane == 0) wsum[wv] = __popcll(m1) + __popcll(m2);
   __syncthreads();
-  int64_t my_slot = (raw_nb ? s_first : partial[blockIdx.x]) + __popcll(m1 & below) + __popcll(m2 & below);
+  if (raw_nb) {
+    // (every thread adds the four wavefronts' sums itself: this block's own total, not a word another block is writing)
+    first = slot_base + s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
+    n_local = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
+    n_links = s_red[2][0] + s_red[2][1] + s_red[2][2] + s_red[2][3];
+    if (blockIdx.x == 0 && threadIdx.x == 0 && total_out) *total_out = n_local;
+  }
+  v.no_n = umax && umax_me >= 0;
+  const bool lean = lean_ok && raw_nb && with_records && n_links == 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && stats) { stats[0] = (int32_t)(n_links < INT32_MAX ? n_links : INT32_MAX); stats[1] = lean ? 1 : 0; }
+  int64_t my_slot = first + __popcll(m1 & below) + __popcll(m2 & below);
   for (int k = 0; k < wv; k++) my_slot += wsum[k];
-  if (in) slot[me] = my_slot;
+  if (in && !lean) slot[me] = my_slot;
   // ---- record geometry (k_rec_geom)
   int my_flen = 0, my_actf = 0, my_blen = 0;
-  uint32_t my_st = in ? rs.status[me] : 0u;          // (the walk below may rewrite a read's status: its own lane keeps the new one)
   bool walk = false;
   if (in) {
-    if (!sk) { ri.flen[me] = 0; ri.blen[me] = 0; ri.actf[me] = 0; }
-    else if (rs.status[me] & ST_DIAG) {
-      const int len2 = rs.len[me], abr = rs.abr[me];
+    if (!sk) { if (!lean) { ri.flen[me] = 0; ri.blen[me] = 0; ri.actf[me] = 0; } }
+    else if (my_st & ST_DIAG) {
+      const int len2 = v.len, abr = v.abr;
       const int af = (len2 - abr) < g_me.ncols_f ? (len2 - abr) : g_me.ncols_f;
-      rec_store_at(me, g_me, 0, 0, af, len2 - abr, my_slot, ri, si, read_base, flags);
+      rec_store_val(me, g_me, 0, 0, af, len2 - abr, my_slot, ri, si, read_base, flags, n_local, lean);
       my_flen = g_me.ncols_f; my_actf = af; my_blen = g_me.split ? g_me.ncols_b : 0;
-    } else if ((rs.status[me] & ST_ONEGAP) && !g_me.split) {
-      const uint32_t desc = rs.status[me] >> 8;
-      const int len2 = rs.len[me], abr = rs.abr[me], gn = (int)((desc >> 10) & 63u), ins = (int)(desc & 1u);
-      rec_store_at(me, g_me, ins ? gn : 0, 0, len2 - abr - (ins ? gn : 0), len2 - abr, my_slot, ri, si, read_base, flags);
+    } else if ((my_st & ST_ONEGAP) && !g_me.split) {
+      const uint32_t desc = my_st >> 8;
+      const int len2 = v.len, abr = v.abr, gn = (int)((desc >> 10) & 63u), ins = (int)(desc & 1u);
+      rec_store_val(me, g_me, ins ? gn : 0, 0, len2 - abr - (ins ? gn : 0), len2 - abr, my_slot, ri, si, read_base, flags, n_local, lean);
       my_flen = g_me.ncols_f + (ins ? gn : 0); my_actf = len2 - abr;
     } else walk = true;
   }
@@ -526,16 +574,15 @@ __global__ __launch_bounds__(256) void k_cull_records(ReadSet rs, int32_t L, con
       const uint32_t want = one ? (ST_ONEGAP | (((uint32_t)ev_kind | ((uint32_t)ev_row << 1) | ((uint32_t)gn << 10)) << 8)) : ST_OK;
       if (st_new != want) { if (lane == 0) rs.status[i] = want; st_new = want; }
     }
-    if (lane == 0) rec_store_at(i, g, nf, nb, af, len2 - abr, slot_i, ri, si, read_base, flags);
+    if (lane == 0) rec_store_val(i, g, nf, nb, af, len2 - abr, slot_i, ri, si, read_base, flags, n_local, lean);
     if (lane == li) { my_flen = g.ncols_f + nf; my_actf = af + nf; my_blen = g.split ? g.ncols_b + nb : 0; my_st = st_new; }        // (the counts are wave-uniform: the read's own lane keeps them for its link and its record)
   }
   // ---- own dropped marks, the persistent back slot, the links of formerly split reads (k_cull_mark)
   __shared__ int4 s_rec[4][256];              // (rec_store_wave: a wavefront's 64 records)
   int4 r4[4] = {make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0)};
   if (in) {
-  if (dev_cut) { slope = dev_cut[0]; intercept = dev_cut[1]; }
-  const double min_score = hard_cut > 0 ? (double)hard_cut : (double)(intercept + (slope * (double)rs.len[me]));
-  const bool low = (double)rs.score[me] < min_score;
+  const double min_score = hard_cut > 0 ? (double)hard_cut : (double)(intercept + (slope * (double)v.len));
+  const bool low = (double)score_me < min_score;
   auto add_link = [&](int64_t target, int kind, int fl, int ac) {
     const int e = atomicAdd(lk.n, 1);
     if (e < lk.cap) {
@@ -547,9 +594,11 @@ __global__ __launch_bounds__(256) void k_cull_records(ReadSet rs, int32_t L, con
   };
   int32_t p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (!sk) {
-    if (front_slot0[me] >= 0) add_link(front_slot0[me], 1, 0, 0);
-    if (back_slot[me] >= 0) add_link(back_slot[me], 2, 0, 0);
-    if (with_records) rec_make(rs, me, drop_front, drop_back, 0, 0, p, my_st, 0, umax, r4);
+    if (!lean) {                                  // (lean: the count says that neither pointer of any read is set)
+      if (mark_me & 2) add_link(front_slot0[me], 1, 0, 0);
+      if (mark_me & 1) add_link(back_slot[me], 2, 0, 0);
+    }
+    if (with_records) { drop_front[me] = 0; drop_back[me] = 0; rec_make(v, 0, 0, p, my_st, 0, r4); }
   } else {
   // WITH_RECORDS (round 5): the read's tally record and dropped bits as k_rec_params would write them if no link existed -- its own slot(s),
   // its own depth-code parameters, listed once.  k_rec_params then returns at once unless the iteration has a link (a formerly split read, a
@@ -561,22 +610,52 @@ __global__ __launch_bounds__(256) void k_cull_records(ReadSet rs, int32_t L, con
   if (g_me.split) {
     if (low && my_slot + 1 < n_slots) slot_dropped[my_slot + 1] = 1;
     back_slot[me] = my_slot + 1;
-  } else if (back_slot[me] >= 0) add_link(back_slot[me], 0, my_flen, my_actf);
+    if (!(mark_me & 1)) link_mark[me] = (uint8_t)(mark_me | 1);
+  } else if (mark_me & 1) add_link(back_slot[me], 0, my_flen, my_actf);
   if (with_records) {
-    const int64_t ls = my_slot - si.base, n_local = *si.n_local_p;
+    const int64_t ls = my_slot - si.base;
     if (ls >= 0 && ls < n_local) { p[2] = my_flen + my_blen; p[3] = 1; }
     if (g_me.split && ls + 1 < n_local) { p[4] = my_flen; p[5] = my_actf; p[6] = my_flen + my_blen; p[7] = 1; }
-    rec_make(rs, me, drop_front, drop_back, df, db, p, my_st, my_actf, umax, r4);
+    drop_front[me] = df; drop_back[me] = db;
+    rec_make(v, df, db, p, my_st, my_actf, r4);
   }
   }
   }
   if (with_records) rec_store_wave(ri.trec, i0, rs.n, r4, lane, s_rec[wv]);
+  // ---- apply_ticket (mia_hip_iterate without a communicator): the links are this context's own, and the workgroup that finishes last
+  // applies them (k_links_apply's loop over a handful of links) -- one launch fewer on the step's chain.  Only an iteration with a link
+  // takes the ticket: the lean form pays nothing.  *apply_ticket is 0 on entry and 0 again on exit.
+  if (apply_ticket && !lean) {
+    __shared__ bool s_last;
+    __threadfence();                            // this workgroup's side arrays, dropped marks and links, before its arrival
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = atomicAdd(apply_ticket, 1u) == gridDim.x - 1u;
+    __syncthreads();
+    if (s_last) {
+      __threadfence();
+      const int n_apply = min(__hip_atomic_load(lk.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), lk.cap);
+      for (int e = threadIdx.x; e < n_apply; e += 256) {
+        const int64_t* r = lk.rec + (int64_t)e * 4;
+        const int64_t reader = __builtin_nontemporal_load(r), target = __builtin_nontemporal_load(r + 1), low_kind = __builtin_nontemporal_load(r + 3);
+        const int64_t ls = target - si.base;
+        link_len[e] = -1;                                            // -1: the slot is not ours
+        link_act[e] = -1;
+        if (ls < 0 || ls >= n_local) continue;
+        atomicMax(&si.writer[ls], ((unsigned long long)reader << 20) | (unsigned long long)e);
+        atomicAdd(&si.mult[ls], 1);
+        if ((low_kind & 1) && target < n_slots) slot_dropped[target] = 1;
+        link_len[e] = __builtin_nontemporal_load(si.reclen + ls);
+        link_act[e] = __builtin_nontemporal_load(si.recact + ls);
+      }
+      if (threadIdx.x == 0) *apply_ticket = 0;
+    }
+  }
 }
 
 // own dropped marks, the persistent back slot, and the links of formerly split reads
 __global__ void k_cull_mark(ReadSet rs, int32_t L, const int64_t* slot, uint8_t* slot_dropped, int64_t n_slots, int32_t hard_cut, double slope,
                             double intercept, int64_t* back_slot, const int64_t* front_slot0, RecInfo ri, Links lk, int64_t read_base,
-                            uint32_t* flags, const double* dev_cut) {
+                            uint32_t* flags, const double* dev_cut, uint8_t* link_mark = nullptr) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rs.n) return;
   if (dev_cut) { slope = dev_cut[0]; intercept = dev_cut[1]; }   // the line of find_fsdb_score_cut, left on the device
@@ -602,6 +681,7 @@ __global__ void k_cull_mark(ReadSet rs, int32_t L, const int64_t* slot, uint8_t*
   if (split) {
     if (low && s + 1 < n_slots) slot_dropped[s + 1] = 1;
     back_slot[i] = s + 1;                                      // fs->back_asp (src/mia_main.c:266-267)
+    if (link_mark) link_mark[i] |= 1;                          // (cull_link_mark)
   } else if (back_slot[i] >= 0) add_link(back_slot[i], 0, ri.flen[i], ri.actf[i]);   // stale back_asp
 }
 

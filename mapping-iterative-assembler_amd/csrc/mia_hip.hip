@@ -209,6 +209,7 @@ struct mia_hip_ctx {
   // stale back_asp emulation (mia_consensus_kernels.h, k_cull_mark)
   DevBuf<int64_t> d_back_slot;             // per read, persistent across iterations
   DevBuf<int64_t> d_front_slot0;           // per read: pass-1 front slot (followed for strand-unknown reads only)
+  DevBuf<uint8_t> d_link_mark;             // per read: which of the two is set (cull_body.h: cull_link_mark), kept wherever one of them is written
   DevBuf<int32_t> d_link_act;
   // the kernels take ri, si, lk and tb by value: views, set beside their owners' allocation (mia_hip_upload_reads, ensure_tally, ensure_events)
   RecInfo ri{};                            // per read, per iteration
@@ -229,6 +230,13 @@ struct mia_hip_ctx {
   std::vector<DevBuf<int64_t>> owned_links;   // gathered link buffers (mia_hip_set_links)
   bool cull_scan = false, tail_scans = false;
   bool cull_with_records = true;           // k_cull_records writes the tally records of an iteration without links itself
+  // lean cull (k_cull_records, lean_ok): mia_hip_iterate without a communicator lets an iteration without a link leave d_slot and the
+  // side arrays of ri / si unwritten.  d_cull_stats: {links counted before the cull or -1, 1 if the lean form ran}, written by the kernel
+  bool no_cull_lean = false;
+  bool no_cull_apply = false;              // the links of such an iteration by a launch of k_links_apply, not by k_cull_records' last workgroup
+  bool cull_applied = false;               // the last cull was launched with the ticket: its own links are applied already
+  bool cull_lean_ok = false;               // the last cull was launched with lean_ok: whether it ran lean is d_cull_stats[1]
+  DevBuf<int32_t> d_cull_stats;
   int64_t pre_cull_records = 0, pre_cull_links = 0; bool pre_cull_valid = false;   // mia_hip_score_sums' by-products
 
   // ---- tally and consensus -------------------------------------------------------------------------------------------------
@@ -388,6 +396,8 @@ static void read_alt_switches(mia_hip_ctx* ctx) {
   if (on("MIA_HIP_CULL_SCAN")) ctx->cull_scan = true;          // the slot scan as a kernel of its own (k_scan_partials)
   if (on("MIA_HIP_TAIL_SCANS")) ctx->tail_scans = true;        // the consensus tail's scans as single-workgroup kernels of their own
   if (on("MIA_HIP_NO_CULL_RECORDS")) ctx->cull_with_records = false;               // k_rec_params writes every tally record
+  if (on("MIA_HIP_NO_CULL_LEAN")) ctx->no_cull_lean = true;    // k_cull_records writes d_slot and the side arrays in every iteration
+  if (on("MIA_HIP_NO_CULL_APPLY")) ctx->no_cull_apply = true;  // k_links_apply as a launch of its own in every iteration
   if (on("MIA_HIP_NO_BINNED_TALLY")) ctx->use_binned_tally = 0;                    // plain global-atomic tally
   if (on("MIA_HIP_NO_LINEAR_TALLY")) ctx->no_linear_tally = true;                // the tally adds the four scores of every base even where counting would do
   if (on("MIA_HIP_SORT2_UNPACKED")) ctx->sort2_unpacked = true;                  // the second sort's key in a byte array beside the entries, as from 2^24 reads
@@ -662,12 +672,12 @@ extern "C" int mia_hip_upload_reads(mia_hip_ctx* ctx, int64_t n, const char* bas
   nomem |= dev_alloc(ctx, ctx->d_wide_list, n);
   nomem |= dev_alloc(ctx, ctx->d_retry_list, n);
   nomem |= dev_alloc(ctx, ctx->d_slot, n);
-  nomem |= dev_alloc(ctx, ctx->d_partial, (size_t)(n / 256 + n / 4096 + 8));      // per 256 reads, and behind them per 4 096 (k_slot_count)
+  nomem |= dev_alloc(ctx, ctx->d_partial, (size_t)cull_partial_words(n));      // per 256 reads, and behind them twice per 4 096 (k_slot_count, cull_body.h)
   nomem |= dev_alloc(ctx, ctx->d_drop_f, n);
   nomem |= dev_alloc(ctx, ctx->d_drop_b, n);
   nomem |= dev_alloc(ctx, ctx->d_slot_dropped, 2 * n + 16);
   ctx->n_slots = ctx->d_slot_dropped.cap;
-  nomem |= dev_alloc(ctx, ctx->d_back_slot, n) | dev_alloc(ctx, ctx->d_front_slot0, n);
+  nomem |= dev_alloc(ctx, ctx->d_back_slot, n) | dev_alloc(ctx, ctx->d_front_slot0, n) | dev_alloc(ctx, ctx->d_link_mark, n);
   nomem |= dev_alloc(ctx, ctx->d_ri_flen, n) | dev_alloc(ctx, ctx->d_ri_blen, n) | dev_alloc(ctx, ctx->d_ri_actf, n) |
          dev_alloc(ctx, ctx->d_ri_trec, n * 16);
   const int64_t slot_cap = 2 * n + 16;
@@ -693,6 +703,7 @@ extern "C" int mia_hip_upload_reads(mia_hip_ctx* ctx, int64_t n, const char* bas
   HIPCHK(hipMemsetAsync(ctx->d_slot_dropped, 0, (size_t)ctx->n_slots, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_back_slot, 0xFF, (size_t)n * 8, ctx->stream));   // -1: never split
   HIPCHK(hipMemsetAsync(ctx->d_front_slot0, 0xFF, (size_t)n * 8, ctx->stream));
+  HIPCHK(hipMemsetAsync(ctx->d_link_mark, 0, (size_t)n, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_drop_f, 0, (size_t)n, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_drop_b, 0, (size_t)n, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1755,8 +1766,10 @@ static int finish_params(mia_hip_ctx* ctx);
 static int finish_cull(mia_hip_ctx* ctx) {
   const int64_t nl = ctx->links_cap_all;
   if (dev_ensure(ctx, ctx->d_link_len, nl, nl + 64) || dev_ensure(ctx, ctx->d_link_act, nl, nl + 64)) return MIA_HIP_ERR_NOMEM;
-  hipLaunchKernelGGL(k_links_apply, dim3(32), dim3(256), 0, ctx->stream, ctx->d_links_all, ctx->d_n_links_all, (int32_t)ctx->links_cap_all, ctx->si,
-                     ctx->d_slot_dropped, ctx->n_slots, ctx->d_link_len, ctx->d_link_act, ctx->d_cull_flags, ctx->abort_if);
+  // (the context's own links behind a cull that took the ticket: k_cull_records' last workgroup has applied them)
+  if (!(ctx->cull_applied && ctx->d_links_all == ctx->lk.rec))
+    hipLaunchKernelGGL(k_links_apply, dim3(32), dim3(256), 0, ctx->stream, ctx->d_links_all, ctx->d_n_links_all, (int32_t)ctx->links_cap_all, ctx->si,
+                       ctx->d_slot_dropped, ctx->n_slots, ctx->d_link_len, ctx->d_link_act, ctx->d_cull_flags, ctx->abort_if);
   ctx->links_applied = true;
   return finish_params(ctx);
 }
@@ -1797,7 +1810,12 @@ extern "C" int mia_hip_cull(mia_hip_ctx* ctx, int32_t hard_cut, double slope, do
     if (dev_alloc(ctx, ctx->d_cull_sync, 4)) return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipMemsetAsync(ctx->d_cull_sync, 0, 16, ctx->stream));
   }
-  hipLaunchKernelGGL(k_slot_count, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, ctx->stream, ctx->rs, ctx->L, ctx->d_partial, nb, slot_base, ctx->d_total, (uint32_t*)nullptr, ctx->abort_if);
+  if (!ctx->d_cull_stats) {
+    if (dev_alloc(ctx, ctx->d_cull_stats, 4)) return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipMemsetAsync(ctx->d_cull_stats, 0, 16, ctx->stream));
+  }
+  hipLaunchKernelGGL(k_slot_count, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, ctx->stream, ctx->rs, ctx->L, ctx->d_partial, nb, slot_base, ctx->d_total, (uint32_t*)nullptr, ctx->abort_if,
+                     (const uint8_t*)ctx->d_link_mark);
   // (MIA_HIP_CULL_SCAN=1: the counts scanned by a single-workgroup launch in between, as before)
   if (ctx->cull_scan) hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(256), 0, ctx->stream, ctx->d_partial, nb, slot_base, ctx->d_total, ctx->abort_if);
   if (slot_base + 2 * n + 16 > ctx->n_slots) {   // sharded runs: slots are global indices
@@ -1816,12 +1834,23 @@ extern "C" int mia_hip_cull(mia_hip_ctx* ctx, int32_t hard_cut, double slope, do
   ctx->si.base = slot_base;
   ctx->si.n_local_p = ctx->d_total;
   if (!ctx->in_iterate) HIPCHK(hipMemsetAsync(ctx->lk.n, 0, 8, ctx->stream));                     // link count, cull flags (neighbours in the control block)
+  // lean: only where nothing but this call's own finish_cull can want the side arrays -- a sharded iteration applies gathered links
+  // (k_rec_geom, k_links_apply on the full list), a step-wise caller may go on with mia_hip_set_links
+  const bool lean_ok = ctx->in_iterate && !ctx->comm && ctx->cull_with_records && !ctx->cull_scan && !ctx->no_cull_lean;
+  const bool apply = lean_ok && !ctx->no_cull_apply;
+  if (apply && (dev_ensure(ctx, ctx->d_link_len, (int64_t)ctx->lk.cap, (int64_t)ctx->lk.cap + 64) || dev_ensure(ctx, ctx->d_link_act, (int64_t)ctx->lk.cap, (int64_t)ctx->lk.cap + 64)))
+    return MIA_HIP_ERR_NOMEM;
   hipLaunchKernelGGL(k_cull_records, dim3((unsigned)nb), dim3(256), 0, ctx->stream, ctx->rs, ctx->L, (const int64_t*)ctx->d_partial, ctx->d_slot, ctx->ri, ctx->si,
                      ctx->read_base, ctx->d_cull_flags, ctx->d_slot_dropped, ctx->n_slots, hard_cut, slope, intercept, ctx->d_back_slot,
                      (const int64_t*)ctx->d_front_slot0, ctx->lk, ctx->dev_cut, ctx->abort_if, ctx->cull_scan ? 0 : nb, slot_base, ctx->d_total,
                      ctx->cull_with_records ? 1 : 0, ctx->d_drop_f, ctx->d_drop_b,
-                     (ctx->umax_valid && ctx->rs.roff == ctx->d_roff && ctx->d_rplanes && ctx->d_umax) ? ctx->d_umax : (const int32_t*)nullptr);
+                     (ctx->umax_valid && ctx->rs.roff == ctx->d_roff && ctx->d_rplanes && ctx->d_umax) ? ctx->d_umax : (const int32_t*)nullptr,
+                     lean_ok ? 1 : 0, (int32_t*)ctx->d_cull_stats,
+                     apply ? (uint32_t*)ctx->d_cull_sync : (uint32_t*)nullptr, (int32_t*)ctx->d_link_len, (int32_t*)ctx->d_link_act,
+                     (uint8_t*)ctx->d_link_mark);
   HIPCHK(hipGetLastError());
+  ctx->cull_lean_ok = lean_ok;
+  ctx->cull_applied = apply;
   // by default the links to apply are this context's own; a sharded run replaces them with the gathered list (mia_hip_set_links)
   ctx->d_links_all = ctx->lk.rec;
   ctx->d_n_links_all = ctx->lk.n;
@@ -1831,12 +1860,50 @@ extern "C" int mia_hip_cull(mia_hip_ctx* ctx, int32_t hard_cut, double slope, do
   return finish_cull(ctx);
 }
 
+// the reads' mark bytes again, behind a copy into d_back_slot or d_front_slot0
+static int link_marks_launch(mia_hip_ctx* ctx) {
+  const int64_t n = ctx->rs.n;
+  if (n == 0) return MIA_HIP_OK;
+  hipLaunchKernelGGL(k_link_marks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, (const int64_t*)ctx->d_back_slot, (const int64_t*)ctx->d_front_slot0,
+                     (uint8_t*)ctx->d_link_mark);
+  HIPCHK(hipGetLastError());
+  return MIA_HIP_OK;
+}
+// {links counted before the last cull (-1: not counted, MIA_HIP_CULL_SCAN), 1 if that cull ran in its lean form}
+static int cull_stats_read(mia_hip_ctx* ctx, int32_t* st) {
+  st[0] = -1; st[1] = 0;
+  if (!ctx->d_cull_stats) return MIA_HIP_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(st, ctx->d_cull_stats, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return MIA_HIP_OK;
+}
+extern "C" int mia_hip_cull_stats(mia_hip_ctx* ctx, int64_t* links_before, int32_t* lean) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->culled) { ctx->err = "cull first"; return MIA_HIP_ERR_STATE; }
+  int32_t st[2];
+  if (int rc = cull_stats_read(ctx, st)) return rc;
+  if (links_before) *links_before = st[0];
+  if (lean) *lean = st[1];
+  return MIA_HIP_OK;
+}
+// The step-wise calls that go on from a cull's d_slot and side arrays: after a lean cull those hold an earlier iteration's values
+static int refuse_after_lean_cull(mia_hip_ctx* ctx) {
+  if (!ctx->cull_lean_ok) return MIA_HIP_OK;
+  int32_t st[2];
+  if (int rc = cull_stats_read(ctx, st)) return rc;
+  if (!st[1]) return MIA_HIP_OK;
+  ctx->err = "the last cull ran inside mia_hip_iterate without a link and left the slot and link side arrays unwritten: call mia_hip_cull first";
+  return MIA_HIP_ERR_STATE;
+}
+
 extern "C" int mia_hip_set_back_slots(mia_hip_ctx* ctx, const int64_t* back_slot) {
   if (ctx) ctx->pre_cull_valid = false;
   if (!ctx || !back_slot) return MIA_HIP_ERR_ARG;
   if (!ctx->d_back_slot) { ctx->err = "upload_reads first"; return MIA_HIP_ERR_STATE; }
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipMemcpyAsync(ctx->d_back_slot, back_slot, (size_t)ctx->rs.n * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (int rcm = link_marks_launch(ctx)) return rcm;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }
@@ -1850,6 +1917,7 @@ extern "C" int mia_hip_set_pass1_state(mia_hip_ctx* ctx, const int64_t* front_sl
   if (front_slot) HIPCHK(hipMemcpyAsync(ctx->d_front_slot0, front_slot, n * 8, hipMemcpyHostToDevice, ctx->stream));
   if (back_slot) HIPCHK(hipMemcpyAsync(ctx->d_back_slot, back_slot, n * 8, hipMemcpyHostToDevice, ctx->stream));
   if (score) HIPCHK(hipMemcpyAsync(ctx->d_score, score, n * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (int rcm = link_marks_launch(ctx)) return rcm;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }
@@ -1877,6 +1945,7 @@ extern "C" int mia_hip_set_links(mia_hip_ctx* ctx, const int64_t* d_links_all, i
   if (!ctx || n_all < 0 || (n_all > 0 && !d_links_all)) return MIA_HIP_ERR_ARG;
   if (!ctx->culled) { ctx->err = "cull first"; return MIA_HIP_ERR_STATE; }
   if (n_all >= (int64_t)LINK_NONE) { ctx->err = "too many links"; return MIA_HIP_ERR_RANGE; }
+  if (int rcl = refuse_after_lean_cull(ctx)) return rcl;
   HIPCHK(hipSetDevice(ctx->device));
   // own copy of the gathered list (the caller's buffer may be a temporary of the collective)
   if (n_all * 4 > (ctx->owned_links.empty() ? 0 : ctx->owned_links.back().cap)) {      // (a link is four words)
@@ -1905,6 +1974,7 @@ extern "C" int mia_hip_set_links(mia_hip_ctx* ctx, const int64_t* d_links_all, i
 
 extern "C" int mia_hip_link_lengths(mia_hip_ctx* ctx, int32_t** d_len, int32_t** d_act, int64_t* n) {
   if (!ctx || !ctx->links_applied) return MIA_HIP_ERR_STATE;
+  if (int rcl = refuse_after_lean_cull(ctx)) return rcl;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipStreamSynchronize(ctx->stream));   // k_links_apply fills both buffers; the caller reduces them on a stream of its own
   if (d_len) *d_len = ctx->d_link_len;
@@ -1915,6 +1985,7 @@ extern "C" int mia_hip_link_lengths(mia_hip_ctx* ctx, int32_t** d_len, int32_t**
 
 extern "C" int mia_hip_finish_links(mia_hip_ctx* ctx) {
   if (!ctx || !ctx->links_applied) return MIA_HIP_ERR_STATE;
+  if (int rcl = refuse_after_lean_cull(ctx)) return rcl;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(hipMemsetAsync(ctx->d_cull_flags, 0, 4, ctx->stream));
   return finish_params(ctx);
