@@ -465,6 +465,40 @@ int mia_hip_ma_damage(mia_hip_ctx *ctx, const char *ref_seq, const uint8_t *use,
  * mia_hip_ma_tally. */
 int mia_hip_get_ma_damage(mia_hip_ctx *ctx, uint8_t *pos5, uint8_t *pos3, uint8_t *keep, int64_t *hist, int64_t *orphans);
 
+/* The weight table of the damage score from a model of post-mortem damage (ma_hip -K; DESIGN.md, "Damage score").  Host arithmetic
+ * alone: no context, no device.  w[31 * 5 * 5] is indexed like count of mia_hip_ma_profile, [d'][i'][j'], in units of 2^-16 nat.  With
+ * g(k) = p (1 - p)^(k - 1), k5 = d' + 1 for d' <= 14, k3 = 31 - d' for d' >= 16, and
+ * L(D) = (1 - pi)(1 - eps)(1 - D) + (1 - pi) eps D + pi eps (1 - D):
+ *   double-stranded   D_CT(d') = c0 + [d' <= 14] g(k5), D_GA(d') = c0 + [d' >= 16] g(k3)
+ *   single-stranded   D_CT(d') = c0 + [d' <= 14] g(k5) + [d' >= 16] g(k3); the G rows carry no weight
+ *   w[d'][C][C] = q(ln(L(D_CT) / L(0))), w[d'][C][T] = q(ln((1 - L(D_CT)) / (1 - L(0)))), w[d'][G][G] and w[d'][G][A] likewise with
+ *   D_GA; q(x) = floor(x * 65536 + 0.5); every other entry is 0.
+ * The usual parameters are p = 0.3, c0 = 0.01, pi = 0.001, eps = 0.001 / 3.  MIA_HIP_ERR_ARG for w == NULL, a parameter that is not
+ * finite or outside 0 < p < 1, 0 <= c0 < 1, 0 < pi < 1, 0 < eps < 1, for D >= 1 at some code, and for parameters so small that an entry
+ * is no finite number. */
+int mia_hip_ma_pmd_table(double p, double c0, double pi, double eps, int32_t single_stranded, int32_t *w);
+/* The damage score over the records of the last mia_hip_ma_tally (ma_hip -L, -f 97; the reference has no such step, the rule is this
+ * library's own: DESIGN.md, "Damage score").  ref_seq, use[n] and mate[n] as for mia_hip_ma_damage.  w[31 * 5 * 5]: a weight per event
+ * (d', i', j') of mia_hip_ma_profile, in the read's orientation, |w| <= 2^20 (mia_hip_ma_pmd_table makes one; any table will do).
+ *   rec_score[r]       the sum of w[d'][i'][j'] over the record's count events; '-' columns, columns behind the reference and columns
+ *                      with a bad depth code add nothing, INS_POS pairs are not looked at; 0 for a record with use == 0
+ *   mol_score[r]       S of r's molecule: the sum of its records' scores; its strand = revcom of its lower-numbered record; it counts
+ *                      if one of its records has use != 0
+ *   keep[r]            1 if S >= threshold, written to every record of the molecule
+ *   hist[2][64]        [strand][bin] over the molecules that count, bin = clamp(floor(S / 32768) + 20, 0, 63): bin b holds
+ *                      (b - 20) / 2 <= S / 65536 < (b - 19) / 2, bin 0 everything below, bin 63 everything from 21.5 upward
+ *   n_molecules = the molecules that count; n_kept = the records with keep == 1.  Either may be NULL.
+ * All results are exact integers, independent of the records' order.  No records: nothing is launched, every result is zero.
+ * MIA_HIP_ERR_STATE without a mia_hip_ma_tally before; MIA_HIP_ERR_ARG for ref_seq == NULL, w == NULL, an entry of w outside
+ * -2^20 .. 2^20, a mate that is out of range, r itself or not mutual, and for records that were tallied with col_off[0] != 0.  A refused
+ * call leaves no result; the context stays usable. */
+int mia_hip_ma_score(mia_hip_ctx *ctx, const char *ref_seq, const uint8_t *use, const int64_t *mate, const int32_t *w, int64_t threshold,
+                     int64_t *n_molecules, int64_t *n_kept);
+/* rec_score[n], mol_score[n] (per record: its molecule's S), keep[n], hist[2 * 64] and *orphans (the molecules that count whose mate
+ * is -2) of the last mia_hip_ma_score.  Any pointer may be NULL.  MIA_HIP_ERR_STATE without a successful mia_hip_ma_score since the
+ * last mia_hip_ma_tally. */
+int mia_hip_get_ma_score(mia_hip_ctx *ctx, int64_t *rec_score, int64_t *mol_score, uint8_t *keep, int64_t *hist, int64_t *orphans);
+
 /* The end mask over the records of the last mia_hip_ma_tally (ma_hip -E, -x, -f 96; the reference has no such step, the rule is this
  * library's own: DESIGN.md, "End mask").  Column c of a record has the depth code d = smp[c] - 'A' and, in the read's orientation,
  * d' = d (forward) or 30 - d (revcom).  It is in the 5' zone at position k = d' + 1 when d lies in 0 .. 30 and d' < n5, in the 3' zone
@@ -572,7 +606,7 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
  * plan listed for the full-window kernels itself (k_align_open), [30], [31] reads handed to the plan's second / third launch. */
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
- * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_mask_bounds, k_ma_mask_layout, k_ma_mask_apply, k_ma_sam_layout, k_ma_sam_render, k_ma_damage_hits, k_ma_damage_molecules, k_ma_profile, k_ma_dedup_keys, k_ma_dedup_sort, k_ma_dedup_runs, k_ma_dedup_next, k_ma_dedup_anchors, k_ma_dedup_clusters, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
+ * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_mask_bounds, k_ma_mask_layout, k_ma_mask_apply, k_ma_score_cols, k_ma_score_molecules, k_ma_sam_layout, k_ma_sam_render, k_ma_damage_hits, k_ma_damage_molecules, k_ma_profile, k_ma_dedup_keys, k_ma_dedup_sort, k_ma_dedup_runs, k_ma_dedup_next, k_ma_dedup_anchors, k_ma_dedup_clusters, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
  * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few

@@ -121,6 +121,10 @@ def _load(path=None):
     if hasattr(lib, "mia_hip_ma_damage"):
         lib.mia_hip_ma_damage.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, P(C.c_int64), P(C.c_int64)]
         lib.mia_hip_get_ma_damage.argtypes = [vp, vp, vp, vp, vp, P(C.c_int64)]
+    if hasattr(lib, "mia_hip_ma_score"):
+        lib.mia_hip_ma_pmd_table.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, vp]
+        lib.mia_hip_ma_score.argtypes = [vp, vp, vp, vp, vp, C.c_int64, P(C.c_int64), P(C.c_int64)]
+        lib.mia_hip_get_ma_score.argtypes = [vp, vp, vp, vp, vp, P(C.c_int64)]
     if hasattr(lib, "mia_hip_ma_mask"):
         lib.mia_hip_ma_mask.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int64), P(C.c_int64)]
         lib.mia_hip_get_ma_mask.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
@@ -168,7 +172,7 @@ def exported_symbols():
             "mia_hip_upload_reads", "mia_hip_pass1", "mia_hip_realign", "mia_hip_align_windows", "mia_hip_get_alignments", "mia_hip_get_scripts", "mia_hip_cull",
             "mia_hip_get_dropped", "mia_hip_set_slot_dropped", "mia_hip_score_cut", "mia_hip_num_records",
             "mia_hip_tally", "mia_hip_tally_buffers", "mia_hip_ins_events", "mia_hip_set_ins_events",
-            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_ma_mask", "mia_hip_get_ma_mask", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_trim_rerun_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
+            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_ma_pmd_table", "mia_hip_ma_score", "mia_hip_get_ma_score", "mia_hip_ma_mask", "mia_hip_get_ma_mask", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_trim_rerun_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
             "mia_hip_get_record_params", "mia_hip_set_read_base", "mia_hip_links", "mia_hip_set_links", "mia_hip_link_lengths",
             "mia_hip_finish_links", "mia_hip_cull_stats", "mia_hip_plain_stats", "mia_hip_score_sums",
             "mia_hip_score_cut_from_sums", "mia_hip_stage_stats", "mia_hip_measure_peaks", "mia_hip_measure_issue", "mia_hip_set_tally", "mia_hip_iterate", "mia_hip_set_stage_mask", "mia_hip_comm_unique_id", "mia_hip_comm_init", "mia_hip_comm_destroy",
@@ -177,6 +181,18 @@ def exported_symbols():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def ma_pmd_table(p=0.3, c0=0.01, pi=0.001, eps=0.001 / 3, single_stranded=False):
+    """the weight table w[31, 5, 5] (int32, units of 2^-16 nat) of MiaHip.ma_score from the damage model of mia_hip_ma_pmd_table:
+    host arithmetic alone, no GPU.  ValueError for parameters the library refuses."""
+    l = lib()
+    if not hasattr(l, "mia_hip_ma_pmd_table"):
+        raise RuntimeError("this libmia_hip has no mia_hip_ma_pmd_table")
+    w = np.zeros((31, 5, 5), dtype=np.int32)
+    if l.mia_hip_ma_pmd_table(float(p), float(c0), float(pi), float(eps), 1 if single_stranded else 0, _ptr(w)) != 0:
+        raise ValueError("ma_pmd_table: p, c0, pi, eps must be finite, 0 < p < 1, 0 <= c0 < 1, 0 < pi < 1, 0 < eps < 1 and c0 + p < 1")
+    return w
 
 
 def flat_pssm():
@@ -577,7 +593,7 @@ class MiaHip:
         self._chk(self._l.mia_hip_stage_stats(self._h, 1 if reset else 0, cap, names, ms, k, C.byref(n)))
         return {names[i].decode(): (ms[i], k[i]) for i in range(min(n.value, cap))}
 
-    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_mask_bounds", "k_ma_mask_layout", "k_ma_mask_apply", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs", "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
+    STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_mask_bounds", "k_ma_mask_layout", "k_ma_mask_apply", "k_ma_score_cols", "k_ma_score_molecules", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs", "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
 
     def comm_init(self, unique_id, n_ranks, rank):
         """attach an RCCL communicator (ncclCommInitRank on this context's GPU); unique_id: the 128 bytes of comm_unique_id()
@@ -793,6 +809,36 @@ class MiaHip:
         opt = lambda a: _ptr(a) if n else None
         self._chk(self._l.mia_hip_get_ma_damage(self._h, opt(pos5), opt(pos3), opt(keep), _ptr(hist), C.byref(orphans)))
         return pos5, pos3, keep, hist, n_mol.value, n_kept.value, orphans.value
+
+    def ma_score(self, ref_seq, w, threshold, use=None, mate=None):
+        """the damage score (ma_hip -L, -f 97) over the records of the last ma_tally; ref_seq: the reference's characters; w[31, 5, 5]
+        int32: a weight per event [d', i', j'] of ma_profile in units of 2^-16 nat, |w| <= 2^20 (ma_pmd_table makes one); threshold in
+        the same units; use and mate as for ma_damage.  (rec_score[n], mol_score[n] int64, keep[n] uint8, hist[2, 64] int64, n_molecules,
+        n_kept, orphans): the sum of the weights of the record's columns, the sum over its molecule's records, keep = that sum >=
+        threshold, hist[strand, clamp(floor(S / 32768) + 20, 0, 63)] = molecules by strand and score; n_kept = records with keep set."""
+        if not hasattr(self._l, "mia_hip_ma_score"):
+            raise RuntimeError("this libmia_hip has no mia_hip_ma_score")
+        ref = ref_seq.encode("latin1") if isinstance(ref_seq, str) else bytes(ref_seq)
+        if len(ref) != self.L:
+            raise ValueError("ma_score: the reference has %d characters, the tallied job %d columns" % (len(ref), self.L))
+        w = np.ascontiguousarray(w, dtype=np.int32)
+        if w.size != PSSM_WORDS:
+            raise ValueError("ma_score: the weight table holds 31 * 5 * 5 entries")
+        if use is not None:
+            use = np.ascontiguousarray(use, dtype=np.uint8)
+        if mate is not None:
+            mate = np.ascontiguousarray(mate, dtype=np.int64)
+        n = getattr(self, "_ma_n", 0)                      # the records of the last ma_tally
+        if (use is not None and len(use) != n) or (mate is not None and len(mate) != n):
+            raise ValueError("ma_score: use and mate hold one entry per tallied record (%d)" % n)
+        n_mol, n_kept, orphans = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._l.mia_hip_ma_score(self._h, C.c_char_p(ref), _ptr(use) if use is not None and use.size else None,
+                                           _ptr(mate) if mate is not None and mate.size else None, _ptr(w), int(threshold), C.byref(n_mol), C.byref(n_kept)))
+        rec_score, mol_score, keep = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint8)
+        hist = np.zeros((2, 64), dtype=np.int64)
+        opt = lambda a: _ptr(a) if n else None
+        self._chk(self._l.mia_hip_get_ma_score(self._h, opt(rec_score), opt(mol_score), opt(keep), _ptr(hist), C.byref(orphans)))
+        return rec_score, mol_score, keep, hist, n_mol.value, n_kept.value, orphans.value
 
     def ma_mask(self, n5, n3, substitute=False, single_stranded=False):
         """the end mask (ma_hip -E, -x, -f 96) over the records of the last ma_tally; n5, n3 in 0 .. 15, not both 0: the positions

@@ -41,14 +41,15 @@
 #include "mia_ma_dedup_kernels.h"
 #include "mia_ma_damage_kernels.h"
 #include "mia_ma_mask_kernels.h"
+#include "mia_ma_pmd_kernels.h"
 
 using namespace mia;
 
 // timed stages (HIP events on the context's stream around the kernel launches of that kind)
-enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_MASK_BOUNDS, STG_MA_MASK_LAYOUT, STG_MA_MASK_APPLY, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_DAMAGE_HITS, STG_MA_DAMAGE_MOLECULES, STG_MA_PROFILE, STG_MA_DEDUP_KEYS, STG_MA_DEDUP_SORT, STG_MA_DEDUP_RUNS, STG_MA_DEDUP_NEXT, STG_MA_DEDUP_ANCHORS, STG_MA_DEDUP_CLUSTERS, STG_MA_TALLY, STG_MA_COLS, STG_MA_ENDS, STG_COUNT };
+enum Stage { STG_TRACE = 0, STG_PLAIN, STG_FILTER, STG_BAND, STG_BX_PLAN, STG_BX_VALUES, STG_BX_TRACE, STG_TALLY, STG_PASS1, STG_MA_SELECT, STG_MA_RENDER, STG_MA_ACE_LAYOUT, STG_MA_ACE_RENDER, STG_MA_MASK_BOUNDS, STG_MA_MASK_LAYOUT, STG_MA_MASK_APPLY, STG_MA_SCORE_COLS, STG_MA_SCORE_MOLECULES, STG_MA_SAM_LAYOUT, STG_MA_SAM_RENDER, STG_MA_DAMAGE_HITS, STG_MA_DAMAGE_MOLECULES, STG_MA_PROFILE, STG_MA_DEDUP_KEYS, STG_MA_DEDUP_SORT, STG_MA_DEDUP_RUNS, STG_MA_DEDUP_NEXT, STG_MA_DEDUP_ANCHORS, STG_MA_DEDUP_CLUSTERS, STG_MA_TALLY, STG_MA_COLS, STG_MA_ENDS, STG_COUNT };
 static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan",
                                                    "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select",
-                                                   "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_mask_bounds", "k_ma_mask_layout", "k_ma_mask_apply", "k_ma_sam_layout",
+                                                   "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_mask_bounds", "k_ma_mask_layout", "k_ma_mask_apply", "k_ma_score_cols", "k_ma_score_molecules", "k_ma_sam_layout",
                                                    "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs",
                                                    "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"};
 
@@ -301,7 +302,7 @@ struct mia_hip_ctx {
   DevBuf<unsigned long long> d_ma_ctl;
   // what the exports' calls found, per export (the big results are further down): mia_hip_ma_tally forgets all of it at once
   struct MaOut {
-    bool region_done = false, ace_done = false, sam_done = false, prof_done = false, ends_done = false, cols_done = false, damage_done = false, mask_done = false;
+    bool region_done = false, ace_done = false, sam_done = false, prof_done = false, ends_done = false, cols_done = false, damage_done = false, mask_done = false, score_done = false;
     int32_t first = 0, last = -1; int64_t rows = 0, width = 0, ace_bytes = 0, sam_bytes = 0;
   } ma_out;
   // ... and for mia_hip_ma_ace: whether the job has an ACE export at all (GAPS, the records' columns), the running sum of ref->gaps,
@@ -353,6 +354,14 @@ struct mia_hip_ctx {
     DevBuf<unsigned long long> d_ctl, d_bins;
     int64_t bins[MA_MASK_BINS] = {0}, cols_kept = 0; int32_t mode = 0;
   } mask;
+
+  // ... and mia_hip_ma_score, which reads the tallied records and shares the reference's and the selection's buffers with the profile:
+  // the pairing, the 775 weights, per record the sum of its weights (zeroed before the launch), its molecule's score and keep, which
+  // stay on the device until mia_hip_get_ma_score; the 130 bins (ma_pmd_body.h) on the device and, after the call, here
+  struct MaScore {
+    DevBuf<int64_t> d_mate, d_mol; DevBuf<int32_t> d_w; DevBuf<uint8_t> d_keep; DevBuf<unsigned long long> d_rec, d_bins;
+    int64_t bins[MA_PMD_BINS] = {0};
+  } score;
 
   // ---- comm: sharded runs, one context per GPU; the exchanges go through a table of collectives (RCCL over xGMI from
   // mia_hip_comm_init, or whatever mia_hip_comm_attach was given), on the context's own stream ------------------------------------

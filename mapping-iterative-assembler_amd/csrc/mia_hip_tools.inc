@@ -811,6 +811,87 @@ extern "C" int mia_hip_get_ma_mask(mia_hip_ctx* ctx, int32_t* first, int32_t* co
   return MIA_HIP_OK;
 }
 
+// The table of the damage model (ma_hip -K, ma_pmd_body.h): host arithmetic alone, no context and no device.
+extern "C" int mia_hip_ma_pmd_table(double p, double c0, double pi, double eps, int32_t single_stranded, int32_t* w) {
+  if (!w) return MIA_HIP_ERR_ARG;
+  return ma_pmd_model(p, c0, pi, eps, single_stranded != 0, w) ? MIA_HIP_OK : MIA_HIP_ERR_ARG;
+}
+
+// The damage score (ma_hip -L, -K, -S, -f 97) of the records of the last mia_hip_ma_tally: see mia_ma_pmd_kernels.h.  Columns, depth
+// codes and strands are on the device already; the reference, the selection, the pairing and the weights go up.
+extern "C" int mia_hip_ma_score(mia_hip_ctx* ctx, const char* ref_seq, const uint8_t* use, const int64_t* mate, const int32_t* w, int64_t threshold,
+                                int64_t* n_molecules, int64_t* n_kept) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  ctx->ma_out.score_done = false;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_score"; return MIA_HIP_ERR_STATE; }
+  if (!ref_seq) { ctx->err = "ma_score: no reference sequence"; return MIA_HIP_ERR_ARG; }
+  if (!w) { ctx->err = "ma_score: no weight table"; return MIA_HIP_ERR_ARG; }
+  if (!ma_pmd_weights_ok(w)) { ctx->err = "ma_score: a weight lies outside -2^20 .. 2^20"; return MIA_HIP_ERR_ARG; }
+  if (ctx->ma_n > 0 && ctx->ma_cols < 0) { ctx->err = "ma_score: col_off[0] of the tallied records is not 0"; return MIA_HIP_ERR_ARG; }
+  const int64_t n = ctx->ma_n, T = ctx->ma_cols;
+  const int32_t L = ctx->ma_L;
+  if (!ma_dmg_mate_ok(mate, n)) { ctx->err = "ma_score: mate is out of range, the record itself or not mutual"; return MIA_HIP_ERR_ARG; }
+  auto& sc = ctx->score;
+  memset(sc.bins, 0, sizeof sc.bins);
+  if (n > 0) {                                               // without records there is no launch and every result is zero
+    HIPCHK(hipSetDevice(ctx->device));
+    MaSelection sel;
+    if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, sc.d_w, MA_PMD_WEIGHTS) || dev_ensure(ctx, sc.d_rec, n) || dev_ensure(ctx, sc.d_mol, n) ||
+        dev_ensure(ctx, sc.d_keep, n) || dev_ensure(ctx, sc.d_bins, MA_PMD_BINS) || (mate && dev_ensure(ctx, sc.d_mate, n)))
+      return MIA_HIP_ERR_NOMEM;
+    if (const int rc = ma_selection(ctx, nullptr, use, &sel)) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(sc.d_w, w, (size_t)MA_PMD_WEIGHTS * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (mate) HIPCHK(hipMemcpyAsync(sc.d_mate, mate, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(sc.d_rec, 0, (size_t)n * 8, ctx->stream));
+    HIPCHK(hipMemsetAsync(sc.d_mol, 0, (size_t)n * 8, ctx->stream));
+    HIPCHK(hipMemsetAsync(sc.d_keep, 0, (size_t)n, ctx->stream));
+    HIPCHK(hipMemsetAsync(sc.d_bins, 0, (size_t)MA_PMD_BINS * 8, ctx->stream));
+    const MaRecords mr = ma_records(ctx);
+    const int64_t wide = (int64_t)ctx->cus * MAQ_WGS_PER_CU;
+    // persistent grids: the workgroups that are resident at once, or one per chunk (per 256 records) when there are fewer
+    int64_t grid = ma_pmd_chunks(T) < wide ? ma_pmd_chunks(T) : wide;
+    if (grid < 1) grid = 1;                                  // (records that all lack columns: one workgroup that finds no chunk)
+    MaProfView v{mr, T, ctx->d_prof_ref, sel.use};
+    if (stage_launch(ctx, STG_MA_SCORE_COLS, k_ma_score_cols, dim3((unsigned)grid), dim3(MAQ_THREADS), 0, ctx->stream, v, (const int32_t*)sc.d_w,
+                     (unsigned long long*)sc.d_rec))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    MaPmdMolView mv{n, mr.revcom, sel.use, mate ? (const int64_t*)sc.d_mate : nullptr, (const int64_t*)sc.d_rec.p, threshold, (int64_t*)sc.d_mol,
+                    (uint8_t*)sc.d_keep};
+    grid = ma_pmd_record_wgs(n) < wide ? ma_pmd_record_wgs(n) : wide;
+    if (stage_launch(ctx, STG_MA_SCORE_MOLECULES, k_ma_score_molecules, dim3((unsigned)grid), dim3(MAQ_THREADS), 0, ctx->stream, mv,
+                     (unsigned long long*)sc.d_bins))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sc.bins, sc.d_bins, (size_t)MA_PMD_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  int64_t molecules = 0;
+  for (int b = 0; b < MA_PMD_HIST; b++) molecules += sc.bins[b];
+  ctx->ma_out.score_done = true;
+  if (n_molecules) *n_molecules = molecules;
+  if (n_kept) *n_kept = sc.bins[MA_PMD_KEPT];
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_score(mia_hip_ctx* ctx, int64_t* rec_score, int64_t* mol_score, uint8_t* keep, int64_t* hist, int64_t* orphans) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  if (!ctx->ma_resident || !ctx->ma_out.score_done) { ctx->err = "ma_score first"; return MIA_HIP_ERR_STATE; }
+  const int64_t n = ctx->ma_n;
+  auto& sc = ctx->score;
+  if (n > 0 && (rec_score || mol_score || keep)) {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (rec_score) HIPCHK(hipMemcpyAsync(rec_score, sc.d_rec, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (mol_score) HIPCHK(hipMemcpyAsync(mol_score, sc.d_mol, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (keep) HIPCHK(hipMemcpyAsync(keep, sc.d_keep, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  if (hist) memcpy(hist, sc.bins, sizeof(int64_t) * MA_PMD_HIST);
+  if (orphans) *orphans = sc.bins[MA_PMD_ORPHANS];
+  return MIA_HIP_OK;
+}
+
 extern "C" int mia_hip_get_ins_tally(mia_hip_ctx* ctx, int32_t* ins_off, int32_t* ins_tally, int64_t cap_slots, int64_t* n_slots) {
   if (!ctx) return MIA_HIP_ERR_ARG;
   if (!ctx->tallied || !ctx->consensus_done) { ctx->err = "consensus first"; return MIA_HIP_ERR_STATE; }

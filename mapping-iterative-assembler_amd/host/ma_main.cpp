@@ -23,6 +23,10 @@
 // lies within n5 positions of the read's 5' end or n3 of its 3' end leave the record (with -x: a T there at the 5' end, an A -- -S: a T --
 // at the 3' end becomes N), so that the consensus is not called from deaminated bases.  The new record view is made on the GPU
 // (mia_hip_ma_mask) and put back into the file here (host/maln_mask.h); -f 96 prints what left.
+// -L T keeps only the molecules whose damage score reaches T nat ("Damage score": a likelihood ratio of post-mortem damage
+// against none, summed over every C and G column of the read, from the model -K p,c0,pi,eps fills a weight table with; -S: a
+// single-stranded library): behind -u and -D and in front of -E, scored on the GPU (mia_hip_ma_score) over the records of a tally of the
+// file as it stands; the records that are not kept leave as for -u.  -f 97 prints the molecules' scores as a histogram.
 // No CPU fallback.
 #include <ctype.h>
 #include <float.h>
@@ -50,6 +54,7 @@
 #include "../csrc/ma_dedup_body.h"
 #include "../csrc/ma_damage_body.h"
 #include "../csrc/ma_mask_body.h"
+#include "../csrc/ma_pmd_body.h"
 
 namespace {
 
@@ -58,12 +63,14 @@ using namespace maln_text;
 typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92, 93, 95 or 96>\n   -R <REGION_START:REGION_END>\n"
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92, 93, 95, 96 or 97>\n   -R <REGION_START:REGION_END>\n"
          "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
-         "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 42, 9, 91, 92, 93 and 95)\n"
+         "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 42, 9, 91, 92, 93, 95 and 97)\n"
          "   -u remove duplicate molecules first\n   -t <tolerance of -u in columns, 0 .. 100, default 0>\n"
          "   -D <N: keep only deaminated fragments, a hit within N = 1 .. 15 positions of a read end>\n"
-         "   -e <ends of -D that must show a hit: 5, 3, any (default) or both>\n   -S single-stranded library (-D, format 95, -x)\n"
+         "   -e <ends of -D that must show a hit: 5, 3, any (default) or both>\n   -S single-stranded library (-D, -L, formats 95 and 97, -x)\n"
+         "   -L <T: keep only the molecules whose damage score is at least T nat>\n"
+         "   -K <p,c0,pi,eps: the damage model of -L and format 97, default 0.3,0.01,0.001,0.000333333>\n"
          "   -E <n5[,n3]: mask n5 positions at the reads' 5' end and n3 (default n5) at their 3' end, 0 .. 15, not both 0>\n"
          "   -x with -E: do not trim, write N over the bases deamination makes\n"
          "ma_hip reports from a .maln file written by mia, as the reference's ma does: the alignment of consensus and reference\n"
@@ -102,8 +109,15 @@ void help() {
          "Those columns at either end of a record leave it, with the '-' columns next to them; START, END and the inserts' positions move,\n"
          "an insert in front of the new first column leaves, a record that keeps no base leaves the file, GAPS shrinks as for -u.  With -x\n"
          "nothing leaves: a T at the 5' end and an A (-S: a T) at the 3' end, in the read's orientation, become N.  Every format and -m see\n"
-         "the masked file; formats 92, 93 and 95 describe real fragment ends and refuse -E.  The mask is made on the MI355X.  -f 96 prints\n"
+         "the masked file; formats 92, 93, 95 and 97 describe real fragment ends and refuse -E.  The mask is made on the MI355X.  -f 96 prints\n"
          "what the mask took: per position 1 .. 15 the columns removed (-x: set to N) at the 5' and 3' ends of forward and reverse records.\n"
+         "-L T keeps only the molecules whose damage score is at least T nat, behind -u and -D and in front of -E.  The score is a log\n"
+         "likelihood ratio of post-mortem damage against none over all of the read: every reference C read as C or T, and every reference G\n"
+         "read as G or A (-S: C columns only), in the read's orientation, adds a weight that depends on its position as mia scored it.  -K\n"
+         "sets the model the weights come from: C>T with probability c0 + p (1-p)^(k-1) at position k from the 5' end (G>A likewise from\n"
+         "the 3' end; -S: C>T at both ends), polymorphism rate pi, error rate eps.  A read split at the origin is one molecule.  What is not\n"
+         "kept leaves as for -u.  The score is summed on the MI355X.  -f 97 prints the scores of the file as it stands behind -u, -D and -L:\n"
+         "per strand and for both the molecules in every half-nat bin from -10 to 21.5 nat, and those in this bin or above.\n"
          "Format 3 (format 2's summary plus\n"
          "a table of coverage and of the records that start and end at every column) is outside the accelerated path.\n");
 }
@@ -381,6 +395,33 @@ void damage_table(int64_t n_molecules, int64_t orphans, int64_t n_used, bool sin
   o.flush();
 }
 
+// -f 97: the molecules' scores per bin, from hist[strand][bin] alone
+void score_table(int64_t n_molecules, int64_t orphans, int64_t n_used, bool single_stranded, const double model[4], const int64_t* hist) {
+  Out o;
+  o.fmt("# ma_hip damage scores: %lld molecules, %lld orphan halves, %lld records, library %s, p %g c0 %g pi %g eps %g\n", (long long)n_molecules,
+        (long long)orphans, (long long)n_used, single_stranded ? "ss" : "ds", model[0], model[1], model[2], model[3]);
+  o.buf += "# from\t+\t-\tall\tfrom+\tfrom-\tfrom_all\n";
+  for (int b = 0; b < mia::MA_PMD_HIST_BINS; b++) {
+    if (b == 0) o.buf += "-inf"; else o.fmt("%.1f", mia::ma_pmd_bin_from(b));
+    int64_t row[3][2];
+    for (int strand = 0; strand < 3; strand++) mia::ma_pmd_row(hist, strand, b, row[strand]);
+    for (int k = 0; k < 2; k++) for (int strand = 0; strand < 3; strand++) o.fmt("\t%lld", (long long)row[strand][k]);
+    o.buf += '\n';
+  }
+  o.flush();
+}
+
+// -K p,c0,pi,eps: four numbers and nothing else
+bool parse_model(const char* s, double out[4]) {
+  for (int k = 0; k < 4; k++) {
+    char* end = nullptr;
+    out[k] = strtod(s, &end);
+    if (end == s || *end != (k < 3 ? ',' : '\0')) return false;
+    s = end + 1;
+  }
+  return true;
+}
+
 void die(mia_hip_ctx* g, const char* what) {
   fprintf(stderr, "%s: %s\n", what, g ? mia_hip_last_error(g) : "no context");
   exit(1);
@@ -398,10 +439,12 @@ int main(int argc, char* argv[]) {
   int ends_mode = mia::MA_DMG_ANY;
   bool mask = false, mask_ok = false, substitute = false;
   long mask_n5 = 0, mask_n3 = 0;
+  bool score = false, score_ok = false, model_given = false, model_ok = false;
+  double score_nat = 0.0, model[4] = {0.3, 0.01, 0.001, 0.001 / 3};
   double score_int = -1.0, score_slo = -1.0, alpha = 1.0;
   int ich;
-  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount>, -A, -u, -t <tolerance>, -D <N>, -e <ends>, -S, -E <n5[,n3]> and -x
-  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:Aut:D:e:SE:x")) != -1) {
+  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount>, -A, -u, -t <tolerance>, -D <N>, -e <ends>, -S, -E <n5[,n3]>, -x, -L <T> and -K <p,c0,pi,eps>
+  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:Aut:D:e:SE:xL:K:")) != -1) {
     switch (ich) {
       case 'I': assign_id = optarg; id_assigned = true; break;
       case 'c': cons_scheme = atoi(optarg); any_arg = true; break;
@@ -427,12 +470,14 @@ int main(int argc, char* argv[]) {
       case 'S': single_stranded = true; break;
       case 'E': mask = true; mask_ok = parse_mask_ends(optarg, &mask_n5, &mask_n3); any_arg = true; break;
       case 'x': substitute = true; break;
+      case 'L': { char* end = nullptr; score_nat = strtod(optarg, &end); score_ok = end != optarg && !*end && isfinite(score_nat) && fabs(score_nat) <= 1e12; score = true; any_arg = true; } break;
+      case 'K': model_given = true; model_ok = parse_model(optarg, model); break;
       default: help(); exit(0);
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 42 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93 && out_format != 95 && out_format != 96) {
-    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 42, 8, 9, 91, 92, 93, 95 and 96, which the reference does not have); use the reference's ma\n", out_format);
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 42 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93 && out_format != 95 && out_format != 96 && out_format != 97) {
+    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 42, 8, 9, 91, 92, 93, 95, 96 and 97, which the reference does not have); use the reference's ma\n", out_format);
     exit(1);
   }
   if (out_format == 91 && !mia::ma_prof_alpha_ok(alpha)) {
@@ -448,16 +493,25 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "ma_hip: -E must be n5 or n5,n3: whole numbers from 0 to %d, not both 0\n", mia::MA_MASK_MAX_POS);
     exit(1);
   }
-  if (mask && (out_format == 92 || out_format == 93 || out_format == 95)) {
+  if (mask && (out_format == 92 || out_format == 93 || out_format == 95 || out_format == 97)) {
     fprintf(stderr, "ma_hip: -f %d describes real fragment ends and cannot follow -E, which masks them\n", out_format);
     exit(1);
   }
-  if (single_stranded && !damage && out_format != 95 && !substitute) { fprintf(stderr, "ma_hip: -S is the library type of -D and of -f 95, neither of which is given\n"); exit(1); }
+  if (single_stranded && !damage && out_format != 95 && !substitute && !score && out_format != 97) { fprintf(stderr, "ma_hip: -S is the library type of -D and of -f 95, neither of which is given\n"); exit(1); }
   if (damage && !mia::ma_dmg_pos_ok((int)(damage_n < 0 || damage_n > 1000 ? -1 : damage_n))) {
     fprintf(stderr, "ma_hip: -D must be a whole number from 1 to %d\n", mia::MA_DMG_MAX_POS);
     exit(1);
   }
   if (ends_given && ends_mode < 0) { fprintf(stderr, "ma_hip: -e (the ends of -D) must be 5, 3, any or both\n"); exit(1); }
+  if (model_given && !score && out_format != 97) { fprintf(stderr, "ma_hip: -K is the damage model of -L and of -f 97, neither of which is given\n"); exit(1); }
+  if (score && !score_ok) { fprintf(stderr, "ma_hip: -L must be a finite decimal number, the least damage score in nat\n"); exit(1); }
+  if (model_given && !model_ok) { fprintf(stderr, "ma_hip: -K must be p,c0,pi,eps: four numbers, the damage model of -L and of -f 97\n"); exit(1); }
+  std::vector<int32_t> weights((size_t)mia::MA_PMD_WEIGHTS, 0);
+  if ((score || out_format == 97) &&
+      (mia_hip_ma_pmd_table(model[0], model[1], model[2], model[3], single_stranded ? 1 : 0, weights.data()) != MIA_HIP_OK || !mia::ma_pmd_weights_ok(weights.data()))) {
+    fprintf(stderr, "ma_hip: -K must hold 0 < p < 1, 0 <= c0 < 1, 0 < pi < 1, 0 < eps < 1 and c0 + p < 1, and give weights of at most 16 nat\n");
+    exit(1);
+  }
   Maln m;
   read_ma(ma_in_fn.c_str(), &m);
   if (id_assigned) m.ref_id = assign_id.substr(0, 256);
@@ -500,6 +554,19 @@ int main(int argc, char* argv[]) {
     if (mia_hip_ma_damage(g, m.ref_seq.data(), nullptr, mate.data(), (int32_t)damage_n, single_stranded ? 1 : 0, ends_mode, nullptr, nullptr) != MIA_HIP_OK)
       die(g, "ma_damage");
     if (mia_hip_get_ma_damage(g, nullptr, nullptr, keep.data(), nullptr, nullptr) != MIA_HIP_OK) die(g, "get_ma_damage");
+    keep.resize(m.rec.size());
+    remove_records(&m, keep);
+  }
+  if (score) {
+    // the damage score filter, behind -u and -D and in front of the mask: the score per molecule over all records (dropped or not) on
+    // the device, then what stays below the threshold leaves as for -u
+    tally_file();
+    std::vector<int64_t> mate;
+    pair_halves(m, &mate);
+    std::vector<uint8_t> keep(m.rec.size() + 1, 0);
+    if (mia_hip_ma_score(g, m.ref_seq.data(), nullptr, mate.data(), weights.data(), (int64_t)floor(score_nat * 65536.0 + 0.5), nullptr, nullptr) != MIA_HIP_OK)
+      die(g, "ma_score");
+    if (mia_hip_get_ma_score(g, nullptr, nullptr, keep.data(), nullptr, nullptr) != MIA_HIP_OK) die(g, "get_ma_score");
     keep.resize(m.rec.size());
     remove_records(&m, keep);
   }
@@ -592,6 +659,18 @@ int main(int argc, char* argv[]) {
       die(g, "ma_damage");
     if (mia_hip_get_ma_damage(g, nullptr, nullptr, nullptr, hist.data(), &orphans) != MIA_HIP_OK) die(g, "get_ma_damage");
     damage_table(n_molecules, orphans, n_used, single_stranded, hist.data());
+    return finish(g);
+  }
+  if (out_format == 97) {
+    std::vector<uint8_t> use((size_t)n + 1, 1);
+    int64_t n_used = 0;
+    for (int64_t r = 0; r < n; r++) n_used += use[(size_t)r] = use_dropped || !m.rec[(size_t)r].dropped ? 1 : 0;
+    std::vector<int64_t> mate, hist((size_t)mia::MA_PMD_HIST);
+    pair_halves(m, &mate);
+    int64_t n_molecules = 0, orphans = 0;
+    if (mia_hip_ma_score(g, m.ref_seq.data(), use.data(), mate.data(), weights.data(), 0, &n_molecules, nullptr) != MIA_HIP_OK) die(g, "ma_score");
+    if (mia_hip_get_ma_score(g, nullptr, nullptr, nullptr, hist.data(), &orphans) != MIA_HIP_OK) die(g, "get_ma_score");
+    score_table(n_molecules, orphans, n_used, single_stranded, model, hist.data());
     return finish(g);
   }
   if (out_format == 42) {
