@@ -441,6 +441,27 @@ int mia_hip_ma_dedup(mia_hip_ctx *ctx, int32_t ref_len, int64_t n_records, const
  * mia_hip_ma_dedup before. */
 int mia_hip_get_ma_dedup(mia_hip_ctx *ctx, uint8_t *keep, int64_t *rep, int64_t *size_hist, int64_t *orphans);
 
+/* The duplicate consensus over the clusters of the last mia_hip_ma_dedup and the records of the last mia_hip_ma_tally (ma_hip -u -j,
+ * -f 98; the rule is this library's own: DESIGN.md, "Duplicate consensus").  It needs a mia_hip_ma_tally and, after it, a
+ * mia_hip_ma_dedup over the same number of records.  rec_of[f] = the tallied record that the filter's record f is (NULL: the same
+ * number); vote[r], per TALLIED record: 0 = the molecule whose whole or front record r is votes nowhere (NULL: everyone votes).  For
+ * every record of the representative of a cluster of two or more molecules and every column of it, each molecule of the cluster
+ * casts the character its whole or front record, else its back half, has on that reference column: A, C, G, T or '-' in either case
+ * ('-' does not count at the record's first and last column; anything else is no vote).  One class strictly ahead replaces the
+ * column unless it is the record's own character (lower case survives); of several classes ahead the own one stays, else the column
+ * becomes N.  n_collapsed = the clusters of two or more molecules, n_changed = the bytes of SEQ that changed (either may be NULL).
+ * Without such a cluster nothing is launched and SEQ stays.  MIA_HIP_ERR_STATE: no mia_hip_ma_tally, no mia_hip_ma_dedup, or one
+ * made before the last tally; MIA_HIP_ERR_ARG: the two calls were given different numbers of records, rec_of is no permutation, or
+ * START or END of a record as the filter was given it is not the tallied record's start and start + columns - 1.  The context
+ * stays usable.  The next mia_hip_ma_tally or mia_hip_ma_dedup invalidates the result. */
+int mia_hip_ma_collapse(mia_hip_ctx *ctx, const int64_t *rec_of, const uint8_t *vote, int64_t *n_collapsed, int64_t *n_changed);
+/* Of the last mia_hip_ma_collapse: seq[col_off[n]] (the SEQ strings of the tallied records with the representatives' columns
+ * decided; cap_bytes = the bytes seq holds), members[n] (per tallied record: the molecules of its cluster if it is a record of the
+ * representative of a cluster of two or more, else 0) and hist[2 * 6 * 6] ([strand of the representative][molecules in the cluster:
+ * 2, 3, 4, 5-8, 9-16, 17 and more][clusters, columns with a vote, columns whose votes were not unanimous, columns changed to a
+ * base, to '-', to N]).  Any pointer may be NULL.  MIA_HIP_ERR_STATE without a successful mia_hip_ma_collapse before. */
+int mia_hip_get_ma_collapse(mia_hip_ctx *ctx, char *seq, int64_t cap_bytes, int32_t *members, int64_t *hist);
+
 /* The deaminated-fragment filter over the records of the last mia_hip_ma_tally (ma_hip -D, -e, -S, -f 95; the reference has no such
  * filter, the rule is this library's own: DESIGN.md, "Deaminated fragments").  ref_seq: the ref_len characters of the reference;
  * use[n]: 0 = the record yields no hits and does not make its molecule count (NULL: every record counts); mate[n] as for
@@ -607,7 +628,8 @@ int mia_hip_bx_stats(mia_hip_ctx *ctx, int reset, int64_t *reads4, double *kerne
 int mia_hip_bx_counters(mia_hip_ctx *ctx, uint32_t *out32);
 /* Every timed stage at once: names[k] (static strings: k_align_quad, k_align_quad_plain, k_diag_filter, k_band_align,
  * k_bx_plan, k_bx_values, k_bx_trace, k_tally_binned, k_pass1, k_ma_region_select, k_ma_region_render, k_ma_ace_layout, k_ma_ace_render, k_ma_mask_bounds, k_ma_mask_layout, k_ma_mask_apply, k_ma_score_cols, k_ma_score_molecules, k_ma_sam_layout, k_ma_sam_render, k_ma_damage_hits, k_ma_damage_molecules, k_ma_profile, k_ma_dedup_keys, k_ma_dedup_sort, k_ma_dedup_runs, k_ma_dedup_next, k_ma_dedup_anchors, k_ma_dedup_clusters, k_ma_tally, k_ma_cols, k_ma_ends), accumulated milliseconds and launches since the last
- * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL. */
+ * reset; *n_stages = how many there are, at most cap are written.  Any pointer may be NULL.  Behind the 32 stages that
+ * mia_hip_set_stage_mask has a bit for come k_ma_collapse_plan, k_ma_collapse_count and k_ma_collapse_decide, which are always timed. */
 int mia_hip_stage_stats(mia_hip_ctx *ctx, int reset, int32_t cap, const char **names, double *ms, int64_t *launches, int32_t *n_stages);
 /* Which stages are timed: bit k = stage k of mia_hip_stage_stats (default: all).  An event pair costs the stream a few
  * microseconds of idle time; a caller that wants the duration of one kernel over a timed region switches the others off. */

@@ -118,6 +118,9 @@ def _load(path=None):
     if hasattr(lib, "mia_hip_ma_dedup"):
         lib.mia_hip_ma_dedup.argtypes = [vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, C.c_int32, P(C.c_int64), P(C.c_int64)]
         lib.mia_hip_get_ma_dedup.argtypes = [vp, vp, vp, vp, P(C.c_int64)]
+    if hasattr(lib, "mia_hip_ma_collapse"):
+        lib.mia_hip_ma_collapse.argtypes = [vp, vp, vp, P(C.c_int64), P(C.c_int64)]
+        lib.mia_hip_get_ma_collapse.argtypes = [vp, vp, C.c_int64, vp, vp]
     if hasattr(lib, "mia_hip_ma_damage"):
         lib.mia_hip_ma_damage.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, P(C.c_int64), P(C.c_int64)]
         lib.mia_hip_get_ma_damage.argtypes = [vp, vp, vp, vp, vp, P(C.c_int64)]
@@ -172,7 +175,7 @@ def exported_symbols():
             "mia_hip_upload_reads", "mia_hip_pass1", "mia_hip_realign", "mia_hip_align_windows", "mia_hip_get_alignments", "mia_hip_get_scripts", "mia_hip_cull",
             "mia_hip_get_dropped", "mia_hip_set_slot_dropped", "mia_hip_score_cut", "mia_hip_num_records",
             "mia_hip_tally", "mia_hip_tally_buffers", "mia_hip_ins_events", "mia_hip_set_ins_events",
-            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_ma_pmd_table", "mia_hip_ma_score", "mia_hip_get_ma_score", "mia_hip_ma_mask", "mia_hip_get_ma_mask", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_trim_rerun_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
+            "mia_hip_get_tally", "mia_hip_consensus", "mia_hip_myers", "mia_hip_myers_packed", "mia_hip_myers_align", "mia_hip_filter_stats", "mia_hip_band_stats", "mia_hip_bx_stats", "mia_hip_bx_counters", "mia_hip_kernel_time", "mia_hip_pass1_time", "mia_hip_myers_time", "mia_hip_pass1_filtered", "mia_hip_pass1_anchored", "mia_hip_pre_cull_counts", "mia_hip_ma_tally", "mia_hip_get_ins_tally", "mia_hip_ma_region", "mia_hip_get_ma_region", "mia_hip_ma_ace", "mia_hip_get_ma_ace", "mia_hip_ma_sam", "mia_hip_get_ma_sam", "mia_hip_ma_profile", "mia_hip_get_ma_profile", "mia_hip_ma_ends", "mia_hip_get_ma_ends", "mia_hip_ma_cols", "mia_hip_get_ma_cols", "mia_hip_ma_dedup", "mia_hip_get_ma_dedup", "mia_hip_ma_collapse", "mia_hip_get_ma_collapse", "mia_hip_ma_damage", "mia_hip_get_ma_damage", "mia_hip_ma_pmd_table", "mia_hip_ma_score", "mia_hip_get_ma_score", "mia_hip_ma_mask", "mia_hip_get_ma_mask", "mia_hip_trim", "mia_hip_trim_stats", "mia_hip_trim_rerun_stats", "mia_hip_set_back_slots", "mia_hip_set_pass1_state",
             "mia_hip_get_record_params", "mia_hip_set_read_base", "mia_hip_links", "mia_hip_set_links", "mia_hip_link_lengths",
             "mia_hip_finish_links", "mia_hip_cull_stats", "mia_hip_plain_stats", "mia_hip_score_sums",
             "mia_hip_score_cut_from_sums", "mia_hip_stage_stats", "mia_hip_measure_peaks", "mia_hip_measure_issue", "mia_hip_set_tally", "mia_hip_iterate", "mia_hip_set_stage_mask", "mia_hip_comm_unique_id", "mia_hip_comm_init", "mia_hip_comm_destroy",
@@ -585,7 +588,7 @@ class MiaHip:
 
     def stage_stats(self, reset=False):
         """{stage name: (milliseconds, launches)} of every timed kernel since the last reset (HIP events on the context's stream)"""
-        cap = 32
+        cap = 64
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         k = (C.c_int64 * cap)()
@@ -594,6 +597,8 @@ class MiaHip:
         return {names[i].decode(): (ms[i], k[i]) for i in range(min(n.value, cap))}
 
     STAGES = ["k_align_quad", "k_align_quad_plain", "k_diag_filter", "k_band_align", "k_bx_plan", "k_bx_values", "k_bx_trace", "k_tally_binned", "k_pass1", "k_ma_region_select", "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_mask_bounds", "k_ma_mask_layout", "k_ma_mask_apply", "k_ma_score_cols", "k_ma_score_molecules", "k_ma_sam_layout", "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs", "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"]
+
+    STAGES_ALWAYS_TIMED = ["k_ma_collapse_plan", "k_ma_collapse_count", "k_ma_collapse_decide"]      # behind STAGES in stage_stats(); no bit in the stage mask
 
     def comm_init(self, unique_id, n_ranks, rank):
         """attach an RCCL communicator (ncclCommInitRank on this context's GPU); unique_id: the 128 bytes of comm_unique_id()
@@ -650,6 +655,7 @@ class MiaHip:
                                            _ptr(ir) if len(ir) else None, _ptr(ip) if len(ip) else None, _ptr(io),
                                            _ptr(ib) if len(ib) else None))
         self._ma_n, self._ma_n_ins = len(start), len(ir)
+        self._ma_cols = int(col_off[-1]) if len(start) else 0
 
     def ma_region(self, first, last):
         """print_region's record lines (reference src/map_align.c:660-750) over the records of the last ma_tally, for the
@@ -776,6 +782,30 @@ class MiaHip:
                                            _ptr(mate) if mate is not None and n else None, int(tolerance), C.byref(n_mol), C.byref(n_clu)))
         self._chk(self._l.mia_hip_get_ma_dedup(self._h, opt(keep), opt(rep), _ptr(hist), C.byref(orphans)))
         return keep, rep, hist, n_mol.value, n_clu.value, orphans.value
+
+    def ma_collapse(self, rec_of=None, vote=None):
+        """the duplicate consensus (ma_hip -u -j, -f 98) over the clusters of the last ma_dedup and the records of the last ma_tally,
+        which must come first, in that order, over the same number of records.  rec_of: per record of ma_dedup the tallied record it
+        is (None: the same number); vote: per tallied record 0 = its molecule does not vote (None: everyone votes).  (seq uint8,
+        members[n] int32, hist[2, 6, 6] int64, n_collapsed, n_changed): the SEQ strings with the columns of every representative of a
+        cluster of two or more molecules decided by its members' votes; members = the cluster's molecules for a record of such a
+        representative, else 0; hist[strand, size bin (2, 3, 4, 5-8, 9-16, 17+), (clusters, columns with a vote, columns not
+        unanimous, to a base, to '-', to N)]; n_collapsed = such clusters; n_changed = bytes of seq that changed."""
+        if not hasattr(self._l, "mia_hip_ma_collapse"):
+            raise RuntimeError("this libmia_hip has no mia_hip_ma_collapse")
+        n, cols = getattr(self, "_ma_n", 0), getattr(self, "_ma_cols", 0)
+        if rec_of is not None:
+            rec_of = np.ascontiguousarray(rec_of, dtype=np.int64)
+        if vote is not None:
+            vote = np.ascontiguousarray(vote, dtype=np.uint8)
+        if (rec_of is not None and len(rec_of) != n) or (vote is not None and len(vote) != n):
+            raise ValueError("ma_collapse: rec_of and vote hold one entry per tallied record (%d)" % n)
+        n_col, n_chg = C.c_int64(), C.c_int64()
+        self._chk(self._l.mia_hip_ma_collapse(self._h, _ptr(rec_of) if rec_of is not None and n else None, _ptr(vote) if vote is not None and n else None,
+                                              C.byref(n_col), C.byref(n_chg)))
+        seq, members, hist = np.zeros(cols, dtype=np.uint8), np.zeros(n, dtype=np.int32), np.zeros((2, 6, 6), dtype=np.int64)
+        self._chk(self._l.mia_hip_get_ma_collapse(self._h, _ptr(seq) if cols else None, cols, _ptr(members) if n else None, _ptr(hist)))
+        return seq, members, hist, n_col.value, n_chg.value
 
     DAMAGE_MODES = {"any": 0, "5": 1, "3": 2, "both": 3}
 

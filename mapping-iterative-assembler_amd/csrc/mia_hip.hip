@@ -42,6 +42,7 @@
 #include "mia_ma_damage_kernels.h"
 #include "mia_ma_mask_kernels.h"
 #include "mia_ma_pmd_kernels.h"
+#include "mia_ma_collapse_kernels.h"
 
 using namespace mia;
 
@@ -52,6 +53,10 @@ static const char* const STAGE_NAMES[STG_COUNT] = {"k_align_quad", "k_align_quad
                                                    "k_ma_region_render", "k_ma_ace_layout", "k_ma_ace_render", "k_ma_mask_bounds", "k_ma_mask_layout", "k_ma_mask_apply", "k_ma_score_cols", "k_ma_score_molecules", "k_ma_sam_layout",
                                                    "k_ma_sam_render", "k_ma_damage_hits", "k_ma_damage_molecules", "k_ma_profile", "k_ma_dedup_keys", "k_ma_dedup_sort", "k_ma_dedup_runs",
                                                    "k_ma_dedup_next", "k_ma_dedup_anchors", "k_ma_dedup_clusters", "k_ma_tally", "k_ma_cols", "k_ma_ends"};
+// The stages behind the 32 that mia_hip_set_stage_mask has a bit for: always timed, listed behind the others by mia_hip_stage_stats.
+enum StageMore { STG_MA_COLLAPSE_PLAN = STG_COUNT, STG_MA_COLLAPSE_COUNT, STG_MA_COLLAPSE_DECIDE, STG_ALL };
+static const char* const STAGE_NAMES_MORE[STG_ALL - STG_COUNT] = {"k_ma_collapse_plan", "k_ma_collapse_count", "k_ma_collapse_decide"};
+static inline const char* stage_name(int k) { return k < STG_COUNT ? STAGE_NAMES[k] : STAGE_NAMES_MORE[k - STG_COUNT]; }
 
 // One device block for every small counter of an iteration (planner bins and header, filter / band-pipeline counters, link
 // count, cull and tally flags, insert-event count): one memset at the start of the alignment clears them all, and one copy
@@ -110,7 +115,8 @@ struct mia_hip_ctx {
   // HIP-event timers of the kernels bench.py reports, one per stage (mia_hip_stage_stats); pairs are recycled through ev_free
   uint32_t stage_mask = ~0u;               // timed stages (mia_hip_set_stage_mask): an event pair costs the stream a few microseconds
   struct StageTimer { std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; double ms = 0; int64_t launches = 0; };
-  StageTimer stg[STG_COUNT];
+  StageTimer stg[STG_ALL];
+  bool stage_timed(int st) const { return st >= STG_COUNT || ((stage_mask >> st) & 1u); }
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
 
   // ---- reads (and the matrices they are scored with), reference --------------------------------------------------------------
@@ -335,7 +341,22 @@ struct mia_hip_ctx {
     DevBuf<unsigned long long> d_key[2], d_runkey, d_best, d_ctl, d_hist;
     DevBuf<uint32_t> d_val[2], d_jump[2], d_counts, d_runid, d_first, d_mark, d_cluster, d_anchor;
     int64_t hist[MA_DEDUP_HIST] = {0};
+    // ... and what mia_hip_ma_collapse needs of the call behind it: the side of the sort that holds the sorted order, the runs, whether
+    // mates were given, the reference length, and the tally the call came after (0: none)
+    int sorted_side = 0; int64_t runs = 0; bool has_mate = false; int32_t L = 0; uint64_t tally_no = 0;
   } dedup;
+  uint64_t ma_tally_no = 0;                 // counts the successful mia_hip_ma_tally calls
+
+  // ... and mia_hip_ma_collapse, which reads the tallied records and what mia_hip_ma_dedup left: the tallied record of every record of
+  // the filter and the votes, per cluster the representative's records and the place of its counts, the count array, members, SEQ', the
+  // scan's control words, and the 72 bins (ma_collapse_body.h) on the device and, after the call, here.  The next mia_hip_ma_tally or
+  // mia_hip_ma_dedup invalidates it.
+  struct MaCollapse {
+    bool done = false, launched = false; int64_t n = 0, cols = 0, collapsed = 0, changed = 0;
+    DevBuf<int32_t> d_rec_of, d_rep_f, d_rep_b, d_members; DevBuf<uint8_t> d_vote; DevBuf<int64_t> d_cnt_off; DevBuf<uint32_t> d_cnt; DevBuf<char> d_seq;
+    DevBuf<unsigned long long> d_ctl, d_hist;
+    int64_t hist[MA_COL_HIST] = {0};
+  } collapse;
 
   // ... and mia_hip_ma_damage, which reads the tallied records and shares the reference's and the selection's buffers with the profile:
   // the pairing, per record 16 - k of its best hit at either end (hit5 | hit3, zeroed before the launch), pos5 | pos3 and keep, which
@@ -745,8 +766,8 @@ static void launch_k(void (*kernel)(KArgs...), dim3 g, dim3 b, size_t shm, hipSt
 }
 
 // an event pair for one launch of stage `st`; the start event is recorded here, the end event by stage_end
-static int stage_begin(mia_hip_ctx* ctx, Stage st, hipStream_t on = nullptr) {
-  if (!((ctx->stage_mask >> st) & 1u)) return 0;
+static int stage_begin(mia_hip_ctx* ctx, int st, hipStream_t on = nullptr) {
+  if (!ctx->stage_timed(st)) return 0;
   if (ctx->ev_free.empty()) {
     hipEvent_t x, y;
     if (hipEventCreate(&x) != hipSuccess || hipEventCreate(&y) != hipSuccess) return -1;
@@ -758,8 +779,8 @@ static int stage_begin(mia_hip_ctx* ctx, Stage st, hipStream_t on = nullptr) {
   (void)hipEventRecord(p.first, on ? on : ctx->stream);
   return 0;
 }
-static void stage_end(mia_hip_ctx* ctx, Stage st, hipStream_t on = nullptr) {
-  if (((ctx->stage_mask >> st) & 1u) && !ctx->stg[st].pending.empty()) (void)hipEventRecord(ctx->stg[st].pending.back().second, on ? on : ctx->stream);
+static void stage_end(mia_hip_ctx* ctx, int st, hipStream_t on = nullptr) {
+  if (ctx->stage_timed(st) && !ctx->stg[st].pending.empty()) (void)hipEventRecord(ctx->stg[st].pending.back().second, on ? on : ctx->stream);
 }
 
 // One launch of a timed stage whose kernel carries no event for another stream: the event pair rides on the launch itself
@@ -767,9 +788,9 @@ static void stage_end(mia_hip_ctx* ctx, Stage st, hipStream_t on = nullptr) {
 // the step 10-20 us each, and the timed region of bench.py times the dominant stage in every step); an untimed stage: the
 // launch as it is, between stage_begin / stage_end.
 template <typename... KArgs, typename... Args>
-static int stage_launch(mia_hip_ctx* ctx, Stage st, void (*kernel)(KArgs...), dim3 g, dim3 b, size_t shm, hipStream_t s, Args&&... args) {
+static int stage_launch(mia_hip_ctx* ctx, int st, void (*kernel)(KArgs...), dim3 g, dim3 b, size_t shm, hipStream_t s, Args&&... args) {
   static_assert(sizeof...(KArgs) == sizeof...(Args), "every kernel argument, defaults included");
-  if (!((ctx->stage_mask >> st) & 1u)) {
+  if (!ctx->stage_timed(st)) {
     if (stage_begin(ctx, st, s)) return -1;
     hipLaunchKernelGGL(kernel, g, b, shm, s, static_cast<KArgs>(args)...);
     stage_end(ctx, st, s);
@@ -789,7 +810,7 @@ static int stage_launch(mia_hip_ctx* ctx, Stage st, void (*kernel)(KArgs...), di
 
 // what the recorded event pairs measured goes into their stages' sums; `except`: one stage whose pairs stay pending (its end is not recorded yet)
 static void drain_events(mia_hip_ctx* ctx, int except = -1) {
-  for (int k = 0; k < STG_COUNT; k++) {
+  for (int k = 0; k < STG_ALL; k++) {
     if (k == except) continue;
     auto& t = ctx->stg[k];
     for (auto& e : t.pending) {
@@ -816,9 +837,9 @@ extern "C" int mia_hip_stage_stats(mia_hip_ctx* ctx, int reset, int32_t cap, con
   if (!ctx) return MIA_HIP_ERR_ARG;
   HIPCHK(hipSetDevice(ctx->device));
   drain_events(ctx);
-  if (n_stages) *n_stages = STG_COUNT;
-  for (int k = 0; k < STG_COUNT && k < cap; k++) {
-    if (names) names[k] = STAGE_NAMES[k];
+  if (n_stages) *n_stages = STG_ALL;
+  for (int k = 0; k < STG_ALL && k < cap; k++) {
+    if (names) names[k] = stage_name(k);
     if (ms) ms[k] = ctx->stg[k].ms;
     if (launches) launches[k] = ctx->stg[k].launches;
   }

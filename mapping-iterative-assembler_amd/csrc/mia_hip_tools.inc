@@ -155,6 +155,7 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   // and so are the pairs' characters (k_ma_ends counts their '-' in such words too).
   ctx->ma_resident = false;
   ctx->ma_out = {};
+  ctx->collapse.done = false;
   ctx->ma_ace_gaps_ok = ma_ace_gaps_ok(gaps, ref_len);
   ctx->ma_ace_cols_ok = cols_ok;
   ctx->ma_sam_gaps_ok = ma_sam_gaps_ok(gaps, ref_len);
@@ -207,6 +208,7 @@ extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t
   ctx->tallied = true;
   ctx->consensus_done = false;
   ctx->ma_resident = true;
+  ctx->ma_tally_no++;
   ctx->ma_cols = n == 0 ? 0 : col_off[0] == 0 ? chars : -1;         // (mia_hip_ma_profile takes flat position 0 as record 0's first column)
   return MIA_HIP_OK;
 }
@@ -517,6 +519,7 @@ extern "C" int mia_hip_ma_dedup(mia_hip_ctx* ctx, int32_t ref_len, int64_t n_rec
   if (!ctx) return MIA_HIP_ERR_ARG;
   auto& dd = ctx->dedup;
   dd.done = false;
+  ctx->collapse.done = false;
   if (tolerance < 0 || tolerance > MA_DEDUP_MAX_TOL) { ctx->err = "ma_dedup: the tolerance must lie in 0 .. 100"; return MIA_HIP_ERR_ARG; }
   if (ref_len < 1 || ref_len > MA_DEDUP_MAX_L) { ctx->err = "ma_dedup: reference length out of range"; return MIA_HIP_ERR_ARG; }
   if (n_records < 0 || n_records >= ((int64_t)1 << 31)) { ctx->err = "ma_dedup: record count out of range"; return MIA_HIP_ERR_ARG; }
@@ -534,6 +537,7 @@ extern "C" int mia_hip_ma_dedup(mia_hip_ctx* ctx, int32_t ref_len, int64_t n_rec
     if (end[r] >= L) { ctx->err = "ma_dedup: the back half of a pair ends behind the reference"; return MIA_HIP_ERR_ARG; }
   }
   dd.n = n; dd.molecules = M; dd.orphans = orphans; dd.clusters = 0;
+  dd.sorted_side = 0; dd.runs = 0; dd.has_mate = mate != nullptr; dd.L = L; dd.tally_no = ctx->ma_resident ? ctx->ma_tally_no : 0;
   memset(dd.hist, 0, sizeof dd.hist);
   if (n > 0) {
     HIPCHK(hipSetDevice(ctx->device));
@@ -573,6 +577,7 @@ extern "C" int mia_hip_ma_dedup(mia_hip_ctx* ctx, int32_t ref_len, int64_t n_rec
     HIPCHK(hipGetLastError());
     const unsigned long long* sk = dd.d_key[cur];
     const uint32_t* sm = dd.d_val[cur];
+    dd.sorted_side = cur;
     if (M > 0) {
       const int64_t run_wgs = ma_dedup_wgs(M);
       HIPCHK(hipMemsetAsync(dd.d_ctl, 0, (size_t)(MAR_STATE + run_wgs) * 8, s));
@@ -586,6 +591,7 @@ extern "C" int mia_hip_ma_dedup(mia_hip_ctx* ctx, int32_t ref_len, int64_t n_rec
       HIPCHK(hipStreamSynchronize(s));
       const int64_t R = (int64_t)runs;
       if (R < 1 || R > M) { ctx->err = "ma_dedup: the run count came back inconsistent"; return MIA_HIP_ERR_DEVICE; }
+      dd.runs = R;
       if (stage_launch(ctx, STG_MA_DEDUP_NEXT, k_ma_dedup_next, grid_for(R + 1), dim3(MAD_THREADS), 0, s, (const unsigned long long*)dd.d_runkey, R, W, tolerance,
                        (uint32_t*)dd.d_jump[0], (uint32_t*)dd.d_mark))
         return MIA_HIP_ERR_NOMEM;
@@ -633,6 +639,117 @@ extern "C" int mia_hip_get_ma_dedup(mia_hip_ctx* ctx, uint8_t* keep, int64_t* re
   }
   if (size_hist) memcpy(size_hist, dd.hist, sizeof dd.hist);
   if (orphans) *orphans = dd.orphans;
+  return MIA_HIP_OK;
+}
+
+// The duplicate consensus (ma_hip -u -j, -f 98): see mia_ma_collapse_kernels.h.  Everything it reads is on the device already -- the
+// tallied records and what mia_hip_ma_dedup left --; rec_of and vote go up, SEQ' and members stay there until mia_hip_get_ma_collapse.
+extern "C" int mia_hip_ma_collapse(mia_hip_ctx* ctx, const int64_t* rec_of, const uint8_t* vote, int64_t* n_collapsed, int64_t* n_changed) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  auto& cc = ctx->collapse;
+  auto& dd = ctx->dedup;
+  cc.done = false;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_collapse"; return MIA_HIP_ERR_STATE; }
+  if (!dd.done) { ctx->err = "ma_dedup must precede ma_collapse"; return MIA_HIP_ERR_STATE; }
+  if (dd.tally_no != ctx->ma_tally_no) { ctx->err = "ma_collapse: the last ma_dedup is older than the last ma_tally"; return MIA_HIP_ERR_STATE; }
+  if (dd.n != ctx->ma_n) { ctx->err = "ma_collapse: ma_dedup and ma_tally were given different numbers of records"; return MIA_HIP_ERR_ARG; }
+  if (ctx->ma_n > 0 && ctx->ma_cols < 0) { ctx->err = "ma_collapse: col_off[0] of the tallied records is not 0"; return MIA_HIP_ERR_ARG; }
+  const int64_t n = ctx->ma_n, T = ctx->ma_cols, M = dd.molecules, C = dd.clusters;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  std::vector<int32_t> rec32;
+  if (n > 0) {
+    // rec_of is a permutation, and every record of the filter has the coordinates of the tallied record it names
+    std::vector<int32_t> d_start((size_t)n), d_end((size_t)n), t_start((size_t)n);
+    std::vector<int64_t> t_off((size_t)n + 1);
+    HIPCHK(hipMemcpyAsync(d_start.data(), dd.d_start, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(d_end.data(), dd.d_end, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(t_start.data(), ctx->d_ma_start, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(t_off.data(), ctx->d_ma_coff, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<uint8_t> seen(rec_of ? (size_t)n : 0, 0);
+    if (rec_of) rec32.resize((size_t)n);
+    for (int64_t f = 0; f < n; f++) {
+      const int64_t r = rec_of ? rec_of[f] : f;
+      if (r < 0 || r >= n || (rec_of && seen[(size_t)r])) { ctx->err = "ma_collapse: rec_of is no permutation of the tallied records"; return MIA_HIP_ERR_ARG; }
+      if (rec_of) { seen[(size_t)r] = 1; rec32[(size_t)f] = (int32_t)r; }
+      if (d_start[(size_t)f] != t_start[(size_t)r] || (int64_t)d_end[(size_t)f] != (int64_t)t_start[(size_t)r] + (t_off[(size_t)r + 1] - t_off[(size_t)r]) - 1) {
+        ctx->err = "ma_collapse: a record's START or END as ma_dedup was given it disagrees with the tallied record's start + columns - 1";
+        return MIA_HIP_ERR_ARG;
+      }
+    }
+  }
+  cc.n = n; cc.cols = T; cc.collapsed = cc.changed = 0; cc.launched = false;
+  memset(cc.hist, 0, sizeof cc.hist);
+  const int64_t lone = dd.hist[ma_dedup_size_bin(true, 1)] + dd.hist[ma_dedup_size_bin(false, 1)];
+  if (n > 0 && M > 0 && C > lone) {                          // without a cluster of two or more nothing is launched and SEQ' is SEQ
+    const int32_t n_wgs = (int32_t)ma_collapse_wgs(C);
+    const int64_t words = (T + MA_REC_LANE - 1) / MA_REC_LANE;
+    if (dev_ensure(ctx, cc.d_rep_f, C) || dev_ensure(ctx, cc.d_rep_b, C) || dev_ensure(ctx, cc.d_cnt_off, C + 1) || dev_ensure(ctx, cc.d_members, n) ||
+        dev_ensure(ctx, cc.d_seq, (words + 1) * MA_REC_LANE) || dev_ensure(ctx, cc.d_ctl, (int64_t)MAR_STATE + n_wgs) || dev_ensure(ctx, cc.d_hist, MA_COL_HIST) ||
+        (rec_of && dev_ensure(ctx, cc.d_rec_of, n)) || (vote && dev_ensure(ctx, cc.d_vote, n)))
+      return MIA_HIP_ERR_NOMEM;
+    if (rec_of) HIPCHK(hipMemcpyAsync(cc.d_rec_of, rec32.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (vote) HIPCHK(hipMemcpyAsync(cc.d_vote, vote, (size_t)n, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(cc.d_members, 0, (size_t)n * 4, s));
+    HIPCHK(hipMemsetAsync(cc.d_hist, 0, (size_t)MA_COL_HIST * 8, s));
+    HIPCHK(hipMemsetAsync(cc.d_ctl, 0, (size_t)(MAR_STATE + n_wgs) * 8, s));
+    const MaRecords v = ma_records(ctx);
+    const MaColDedup d{M, C, dd.d_val[dd.sorted_side], dd.d_runid, dd.d_first, dd.d_cluster, dd.d_anchor, dd.d_best, dd.has_mate ? (const int64_t*)dd.d_mate : nullptr,
+                       dd.d_start, rec_of ? (const int32_t*)cc.d_rec_of : nullptr, vote ? (const uint8_t*)cc.d_vote : nullptr};
+    const int64_t wide = (int64_t)ctx->cus * MAJ_WGS_PER_CU;
+    auto grid_for = [&](int64_t wgs) { return dim3((unsigned)(wgs < 1 ? 1 : (wgs < wide ? wgs : wide))); };
+    if (stage_launch(ctx, STG_MA_COLLAPSE_PLAN, k_ma_collapse_copy, grid_for(ma_collapse_wgs(words)), dim3(MAJ_THREADS), 0, s, v.seq, (char*)cc.d_seq, words) ||
+        stage_launch(ctx, STG_MA_COLLAPSE_PLAN, k_ma_collapse_plan, dim3((unsigned)n_wgs), dim3(MAJ_THREADS), 0, s, v, d, (unsigned long long*)cc.d_ctl, n_wgs,
+                     (int32_t*)cc.d_rep_f, (int32_t*)cc.d_rep_b, (int64_t*)cc.d_cnt_off, (int32_t*)cc.d_members, (unsigned long long*)cc.d_hist))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    unsigned long long total = 0;
+    HIPCHK(hipMemcpyAsync(&total, cc.d_ctl + MAR_ROWS, 8, hipMemcpyDeviceToHost, s));      // the one read-back: the count array's size hangs on it
+    HIPCHK(hipStreamSynchronize(s));
+    const int64_t Q = (int64_t)total;
+    if (Q < 0 || Q > T) { ctx->err = "ma_collapse: the plan came back inconsistent"; return MIA_HIP_ERR_DEVICE; }
+    if (dev_ensure(ctx, cc.d_cnt, Q * MA_COL_CLASSES + 1)) return MIA_HIP_ERR_NOMEM;
+    if (Q > 0) HIPCHK(hipMemsetAsync(cc.d_cnt, 0, (size_t)Q * MA_COL_CLASSES * 4, s));
+    if (stage_launch(ctx, STG_MA_COLLAPSE_COUNT, k_ma_collapse_count, grid_for((ma_col_chunks(M) + MAJ_WAVES - 1) / MAJ_WAVES), dim3(MAJ_THREADS), 0, s, v, d,
+                     (const int32_t*)cc.d_rep_f, (const int32_t*)cc.d_rep_b, (const int64_t*)cc.d_cnt_off, (uint32_t*)cc.d_cnt, (char*)cc.d_seq,
+                     (unsigned long long*)cc.d_hist))
+      return MIA_HIP_ERR_NOMEM;
+    if (Q > 0 && stage_launch(ctx, STG_MA_COLLAPSE_DECIDE, k_ma_collapse_decide, grid_for(ma_collapse_wgs(Q)), dim3(MAJ_THREADS), 0, s, v, d, (const int32_t*)cc.d_rep_f,
+                              (const int32_t*)cc.d_rep_b, (const int64_t*)cc.d_cnt_off, (const uint32_t*)cc.d_cnt, Q, (char*)cc.d_seq, (unsigned long long*)cc.d_hist))
+      return MIA_HIP_ERR_NOMEM;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cc.hist, cc.d_hist, sizeof cc.hist, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    drain_events(ctx);
+    cc.launched = true;
+    for (int b = 0; b < 2 * MA_COL_SIZE_BINS; b++) {
+      const int64_t* row = cc.hist + b * MA_COL_COUNTS;
+      for (int k = 0; k < MA_COL_COUNTS; k++) if (row[k] < 0) { ctx->err = "ma_collapse: the counts came back inconsistent"; return MIA_HIP_ERR_DEVICE; }
+      cc.collapsed += row[MA_COL_CLUSTERS];
+      cc.changed += row[MA_COL_TO_BASE] + row[MA_COL_TO_GAP] + row[MA_COL_TO_N];
+    }
+  }
+  cc.done = true;
+  if (n_collapsed) *n_collapsed = cc.collapsed;
+  if (n_changed) *n_changed = cc.changed;
+  return MIA_HIP_OK;
+}
+
+extern "C" int mia_hip_get_ma_collapse(mia_hip_ctx* ctx, char* seq, int64_t cap_bytes, int32_t* members, int64_t* hist) {
+  if (!ctx) return MIA_HIP_ERR_ARG;
+  auto& cc = ctx->collapse;
+  if (!ctx->ma_resident || !ctx->dedup.done || !cc.done) { ctx->err = "ma_collapse first"; return MIA_HIP_ERR_STATE; }
+  if (seq && cap_bytes < cc.cols) { ctx->err = "get_ma_collapse: buffer too small"; return MIA_HIP_ERR_ARG; }
+  HIPCHK(hipSetDevice(ctx->device));
+  if (seq && cc.cols > 0)
+    HIPCHK(hipMemcpyAsync(seq, cc.launched ? (const char*)cc.d_seq : (const char*)ctx->d_ma_seq, (size_t)cc.cols, hipMemcpyDeviceToHost, ctx->stream));
+  if (members && cc.n > 0) {
+    if (cc.launched) HIPCHK(hipMemcpyAsync(members, cc.d_members, (size_t)cc.n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    else memset(members, 0, (size_t)cc.n * 4);
+  }
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (hist) memcpy(hist, cc.hist, sizeof cc.hist);
   return MIA_HIP_OK;
 }
 

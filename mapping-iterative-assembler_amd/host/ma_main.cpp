@@ -27,6 +27,11 @@
 // against none, summed over every C and G column of the read, from the model -K p,c0,pi,eps fills a weight table with; -S: a
 // single-stranded library): behind -u and -D and in front of -E, scored on the GPU (mia_hip_ma_score) over the records of a tally of the
 // file as it stands; the records that are not kept leave as for -u.  -f 97 prints the molecules' scores as a histogram.
+// -j (with -u) makes the copy that stays the consensus of its cluster ("Duplicate consensus"; the reference's idea is mia -C,
+// collapse_FSDB, src/mia.c:140-233, on raw reads with qualities -- a .maln holds none, so the rule is this tool's own): the whole file is
+// tallied first, the clusters are formed as for -u, every molecule of a cluster of two or more votes base by base on the columns of the
+// representative's records on the GPU (mia_hip_ma_collapse; a dropped copy does not vote), and the new SEQ strings and NUM_INPUTS go
+// into the records that stay (host/maln_collapse.h) before the others leave.  -f 98 prints what the votes changed.
 // No CPU fallback.
 #include <ctype.h>
 #include <float.h>
@@ -46,6 +51,7 @@
 #include "maln_text.h"
 #include "maln_dedup.h"
 #include "maln_mask.h"
+#include "maln_collapse.h"
 #include "../csrc/ma_ace_body.h"
 #include "../csrc/ma_sam_body.h"
 #include "../csrc/ma_profile_body.h"
@@ -63,10 +69,11 @@ using namespace maln_text;
 typedef MalnFile Maln;
 
 void help() {
-  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92, 93, 95, 96 or 97>\n   -R <REGION_START:REGION_END>\n"
+  printf("ma_hip -M <maln input file>\n   -c <consensus code>\n   -f <output format: 1, 2, 4, 41, 42, 5, 6, 61, 7, 8, 9, 91, 92, 93, 95, 96, 97 or 98>\n   -R <REGION_START:REGION_END>\n"
          "   -I <ID to assign to assembly sequence>\n   -C colour format 6 output\n   -m <maln output file>\n"
          "   -P <pseudocount of format 91, default 1>\n   -A count dropped records too (formats 42, 9, 91, 92, 93, 95 and 97)\n"
          "   -u remove duplicate molecules first\n   -t <tolerance of -u in columns, 0 .. 100, default 0>\n"
+         "   -j with -u: the copy that stays becomes the consensus of its cluster\n"
          "   -D <N: keep only deaminated fragments, a hit within N = 1 .. 15 positions of a read end>\n"
          "   -e <ends of -D that must show a hit: 5, 3, any (default) or both>\n   -S single-stranded library (-D, -L, formats 95 and 97, -x)\n"
          "   -L <T: keep only the molecules whose damage score is at least T nat>\n"
@@ -118,6 +125,13 @@ void help() {
          "the 3' end; -S: C>T at both ends), polymorphism rate pi, error rate eps.  A read split at the origin is one molecule.  What is not\n"
          "kept leaves as for -u.  The score is summed on the MI355X.  -f 97 prints the scores of the file as it stands behind -u, -D and -L:\n"
          "per strand and for both the molecules in every half-nat bin from -10 to 21.5 nat, and those in this bin or above.\n"
+         "-j (with -u) does not throw the other copies' information away: every molecule of a cluster of two or more votes, base by base,\n"
+         "on the columns of the copy that stays.  A, C, G, T and '-' are votes ('-' not at a record's first and last column), anything else is\n"
+         "none, a dropped copy does not vote.  One character strictly ahead replaces the column (the copy's own lower case survives when it\n"
+         "wins); when several tie the copy's own stays if it is one of them, otherwise the column becomes N.  NUM_INPUTS becomes the sum over\n"
+         "the voting copies; inserted bases, depth codes and everything else stay the kept copy's.  It runs before -D, -L and -E, so that an\n"
+         "error in one copy is not taken for damage.  The votes are counted on the MI355X.  -f 98 prints, per cluster size (2, 3, 4, 5-8, 9-16,\n"
+         "17+) and strand, the clusters, the columns with a vote, those not unanimous and those changed to a base, to '-' and to N.\n"
          "Format 3 (format 2's summary plus\n"
          "a table of coverage and of the records that start and end at every column) is outside the accelerated path.\n");
 }
@@ -433,7 +447,7 @@ int main(int argc, char* argv[]) {
   std::string ma_in_fn, assign_id, ma_out_fn;
   bool id_assigned = false, in_ma = false, any_arg = false, out_ma = false;
   int cons_scheme = 1, out_format = 1, gpu = 0, reg_start = 90, reg_end = 109;
-  bool in_color = false, use_dropped = false, region_given = false, dedup = false, tol_given = false;
+  bool in_color = false, use_dropped = false, region_given = false, dedup = false, tol_given = false, collapse = false;
   long tolerance = 0, damage_n = 0;
   bool damage = false, ends_given = false, single_stranded = false;
   int ends_mode = mia::MA_DMG_ANY;
@@ -443,8 +457,8 @@ int main(int argc, char* argv[]) {
   double score_nat = 0.0, model[4] = {0.3, 0.01, 0.001, 0.001 / 3};
   double score_int = -1.0, score_slo = -1.0, alpha = 1.0;
   int ich;
-  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount>, -A, -u, -t <tolerance>, -D <N>, -e <ends>, -S, -E <n5[,n3]>, -x, -L <T> and -K <p,c0,pi,eps>
-  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:Aut:D:e:SE:xL:K:")) != -1) {
+  // the reference's option string (src/map_assembler.c:113) plus -g <gpu>, -P <pseudocount>, -A, -u, -t <tolerance>, -D <N>, -e <ends>, -S, -E <n5[,n3]>, -x, -L <T>, -K <p,c0,pi,eps> and -j
+  while ((ich = getopt(argc, argv, "I:c:i:f:R:s:m:M:Cb:s:dg:P:Aut:D:e:SE:xL:K:j")) != -1) {
     switch (ich) {
       case 'I': assign_id = optarg; id_assigned = true; break;
       case 'c': cons_scheme = atoi(optarg); any_arg = true; break;
@@ -470,14 +484,15 @@ int main(int argc, char* argv[]) {
       case 'S': single_stranded = true; break;
       case 'E': mask = true; mask_ok = parse_mask_ends(optarg, &mask_n5, &mask_n3); any_arg = true; break;
       case 'x': substitute = true; break;
+      case 'j': collapse = true; break;
       case 'L': { char* end = nullptr; score_nat = strtod(optarg, &end); score_ok = end != optarg && !*end && isfinite(score_nat) && fabs(score_nat) <= 1e12; score = true; any_arg = true; } break;
       case 'K': model_given = true; model_ok = parse_model(optarg, model); break;
       default: help(); exit(0);
     }
   }
   if (!any_arg || ((score_slo == -1) && (score_int != -1)) || ((score_slo != -1) && (score_int == -1)) || !in_ma) { help(); exit(0); }
-  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 42 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93 && out_format != 95 && out_format != 96 && out_format != 97) {
-    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 42, 8, 9, 91, 92, 93, 95, 96 and 97, which the reference does not have); use the reference's ma\n", out_format);
+  if (out_format != 1 && out_format != 2 && out_format != 5 && out_format != 4 && out_format != 41 && out_format != 42 && out_format != 6 && out_format != 61 && out_format != 7 && out_format != 8 && out_format != 9 && out_format != 91 && out_format != 92 && out_format != 93 && out_format != 95 && out_format != 96 && out_format != 97 && out_format != 98) {
+    fprintf(stderr, "output format %d is outside the MI355X-accelerated path (formats 1, 2, 4, 41, 5, 6, 61 and 7 are, and 42, 8, 9, 91, 92, 93, 95, 96, 97 and 98, which the reference does not have); use the reference's ma\n", out_format);
     exit(1);
   }
   if (out_format == 91 && !mia::ma_prof_alpha_ok(alpha)) {
@@ -486,6 +501,8 @@ int main(int argc, char* argv[]) {
   }
   if (tol_given && !dedup) { fprintf(stderr, "ma_hip: -t is the tolerance of -u, which is not given\n"); exit(1); }
   if (tolerance < 0 || tolerance > mia::MA_DEDUP_MAX_TOL) { fprintf(stderr, "ma_hip: -t must be a whole number from 0 to %d\n", mia::MA_DEDUP_MAX_TOL); exit(1); }
+  if (collapse && !dedup) { fprintf(stderr, "ma_hip: -j is the consensus of the clusters of -u, which is not given\n"); exit(1); }
+  if (out_format == 98 && !collapse) { fprintf(stderr, "ma_hip: -f 98 is the report of -j, which is not given\n"); exit(1); }
   if (ends_given && !damage) { fprintf(stderr, "ma_hip: -e names the ends of -D, which is not given\n"); exit(1); }
   if (substitute && !mask) { fprintf(stderr, "ma_hip: -x is the substitution mode of -E, which is not given\n"); exit(1); }
   if (out_format == 96 && !mask) { fprintf(stderr, "ma_hip: -f 96 is the report of -E, which is not given\n"); exit(1); }
@@ -519,23 +536,6 @@ int main(int argc, char* argv[]) {
   auto open_gpu = [&]() {
     if (!g && mia_hip_create(&g, gpu) != MIA_HIP_OK) { fprintf(stderr, "ma_hip: no usable MI355X (gfx950) device %d; there is no CPU fallback\n", gpu); exit(1); }
   };
-  if (dedup) {
-    // the duplicate filter, in front of everything: clusters over all records (dropped or not) on the device, then -u takes out what
-    // is not kept and every check and report below sees the smaller file
-    DedupInput in;
-    std::string why;
-    if (!dedup_input(m, &in, &why)) { fprintf(stderr, "ma_hip: %s has no duplicate filter: %s\n", ma_in_fn.c_str(), why.c_str()); exit(1); }
-    open_gpu();
-    const int64_t n_all = (int64_t)m.rec.size();
-    int64_t n_molecules = 0, n_clusters = 0;
-    std::vector<uint8_t> keep_file((size_t)n_all + 1, 1), keep((size_t)n_all);
-    if (mia_hip_ma_dedup(g, m.L, n_all, in.start.data(), in.end.data(), in.revcom.data(), in.score.data(), in.mate.data(), (int32_t)tolerance, &n_molecules,
-                         &n_clusters) != MIA_HIP_OK)
-      die(g, "ma_dedup");
-    if (mia_hip_get_ma_dedup(g, keep_file.data(), nullptr, nullptr, nullptr) != MIA_HIP_OK) die(g, "get_ma_dedup");
-    for (int64_t f = 0; f < n_all; f++) keep[in.at[(size_t)f]] = keep_file[(size_t)f];
-    remove_records(&m, keep);
-  }
   // the file as it stands goes to the device: the PSSMs and the records (mia_hip_ma_tally, which also validates them)
   auto tally_file = [&]() {
     open_gpu();
@@ -544,6 +544,40 @@ int main(int argc, char* argv[]) {
                          (int64_t)m.ins_record.size(), m.ins_record.data(), m.ins_pos.data(), m.ins_off.data(), m.ins_bases.data()) != MIA_HIP_OK)
       die(g, "ma_tally");
   };
+  CollapseResult collapsed;
+  if (dedup) {
+    // the duplicate filter, in front of everything: clusters over all records (dropped or not) on the device, then -u takes out what
+    // is not kept and every check and report below sees the smaller file
+    DedupInput in;
+    std::string why;
+    if (!dedup_input(m, &in, &why)) { fprintf(stderr, "ma_hip: %s has no duplicate filter: %s\n", ma_in_fn.c_str(), why.c_str()); exit(1); }
+    open_gpu();
+    if (collapse) tally_file();                        // -j: the votes are read from the tallied records of the whole file
+    const int64_t n_all = (int64_t)m.rec.size();
+    int64_t n_molecules = 0, n_clusters = 0;
+    std::vector<uint8_t> keep_file((size_t)n_all + 1, 1), keep((size_t)n_all);
+    if (mia_hip_ma_dedup(g, m.L, n_all, in.start.data(), in.end.data(), in.revcom.data(), in.score.data(), in.mate.data(), (int32_t)tolerance, &n_molecules,
+                         &n_clusters) != MIA_HIP_OK)
+      die(g, "ma_dedup");
+    if (mia_hip_get_ma_dedup(g, keep_file.data(), nullptr, nullptr, nullptr) != MIA_HIP_OK) die(g, "get_ma_dedup");
+    for (int64_t f = 0; f < n_all; f++) keep[in.at[(size_t)f]] = keep_file[(size_t)f];
+    if (collapse) {
+      // the duplicate consensus: the clusters' votes on the device, SEQ' and NUM_INPUTS into the records that stay, then -u as ever
+      std::vector<int64_t> rec_of((size_t)n_all + 1, 0);
+      std::vector<uint8_t> vote((size_t)n_all + 1, 1);
+      for (int64_t f = 0; f < n_all; f++) rec_of[(size_t)f] = (int64_t)in.at[(size_t)f];
+      for (int64_t k = 0; k < n_all; k++) vote[(size_t)k] = m.rec[(size_t)k].dropped ? 0 : 1;
+      collapsed.keep.assign(keep_file.begin(), keep_file.end());
+      collapsed.rep.assign((size_t)n_all + 1, 0);
+      collapsed.molecules = n_molecules; collapsed.clusters = n_clusters;
+      if (mia_hip_get_ma_dedup(g, nullptr, collapsed.rep.data(), nullptr, &collapsed.orphans) != MIA_HIP_OK) die(g, "get_ma_dedup");
+      if (mia_hip_ma_collapse(g, rec_of.data(), vote.data(), &collapsed.collapsed, nullptr) != MIA_HIP_OK) die(g, "ma_collapse");
+      collapsed.seq.assign(m.seq.size() + 1, '\0');
+      if (mia_hip_get_ma_collapse(g, &collapsed.seq[0], (int64_t)m.seq.size(), nullptr, collapsed.hist) != MIA_HIP_OK) die(g, "get_ma_collapse");
+      apply_collapse(&m, in, collapsed, vote);
+    }
+    remove_records(&m, keep);
+  }
   if (damage) {
     // the deaminated-fragment filter, behind -u and in front of everything else: the decision per molecule over all records (dropped
     // or not) on the device, then what is not kept leaves as for -u
@@ -645,6 +679,11 @@ int main(int argc, char* argv[]) {
   }
   if (out_format == 96) {
     mask_report(stdout, mask_n_in, masked, substitute, substitute && single_stranded);
+    fflush(stdout);
+    return finish(g);
+  }
+  if (out_format == 98) {
+    collapse_report(stdout, collapsed, tolerance);
     fflush(stdout);
     return finish(g);
   }
