@@ -8,25 +8,26 @@
 // Per record the smallest k of either end is kept as 16 - k (0 = no hit), so that a maximum over a zeroed array finds it.
 //
 // Plain C++ behind MIA_HD.  k_ma_damage_hits (mia_ma_damage_kernels.h) gives every lane a stretch of MA_DMG_LANE flat positions:
-// ma_dmg_stretch walks it as ma_prof_stretch does, keeps the best hit of either end of the record it is in in registers and hands
-// them to its caller when the record changes and at the stretch's end -- at most one call per record of the stretch, and none for a
-// record without a hit.  k_ma_damage_molecules gives every lane a record: ma_dmg_record joins the halves of a read split at the origin
-// (mate, as for the duplicate filter), decides keep for N and the ends mode, and names the molecule's class.  A host caller
+// ma_dmg_stretch is the shared walk (ma_flat_body.h) with this rule: it keeps the best hit of either end of the record it is in in
+// registers and hands them to its caller when the walk leaves the record -- at most one call per record of the stretch, and none for
+// a record without a hit.  k_ma_damage_molecules gives every lane a record: ma_dmg_record is the shared join of the halves of a read
+// split at the origin (ma_molecule_body.h) with this rule: keep for N and the ends mode, and the molecule's class.  A host caller
 // (tests/ma_damage_driver.cpp) runs the same code stretch by stretch and record by record.
 #pragma once
 #include <stdint.h>
 
+#include "ma_molecule_body.h"
 #include "ma_profile_body.h"
 
 namespace mia {
 
-constexpr int MA_DMG_LANE = MA_PROF_LANE;
+constexpr int MA_DMG_LANE = MA_FLAT_LANE;
 constexpr int MA_DMG_MAX_POS = 15;                                     // k and N lie in 1 .. 15
 constexpr int MA_DMG_CLASSES = MA_DMG_MAX_POS + 1;                     // m5, m3 = 0 .. 15
 constexpr int MA_DMG_HIST = 2 * MA_DMG_CLASSES * MA_DMG_CLASSES;       // hist[strand][m5][m3]
 constexpr int MA_DMG_ORPHANS = MA_DMG_HIST, MA_DMG_KEPT = MA_DMG_ORPHANS + 1, MA_DMG_BINS = MA_DMG_KEPT + 1;   // 514: hist | orphans | kept records
 constexpr int MA_DMG_ANY = 0, MA_DMG_5 = 1, MA_DMG_3 = 2, MA_DMG_BOTH = 3;
-constexpr int64_t MA_DMG_NONE = -1, MA_DMG_ORPHAN = -2;                // mate[r]: a molecule of its own, a half without its other half
+inline bool ma_dmg_mate_ok(const int64_t* mate, int64_t n) { return ma_mate_ok(mate, n); }   // (the name it had while it lived here)
 
 MIA_HD inline bool ma_dmg_pos_ok(int n_pos) { return n_pos >= 1 && n_pos <= MA_DMG_MAX_POS; }
 MIA_HD inline bool ma_dmg_mode_ok(int mode) { return mode >= MA_DMG_ANY && mode <= MA_DMG_BOTH; }
@@ -44,38 +45,22 @@ MIA_HD inline int ma_dmg_hit(int bin, bool single_stranded) {
 // The stretch of flat positions base .. base + MA_DMG_LANE - 1 (base a multiple of MA_DMG_LANE): found(r, h5, h3) is called once for
 // every record r of the stretch that has a hit there, h5 / h3 = 16 - (its smallest k at that end inside the stretch), 0 for none.
 template <class Found>
-MIA_HD inline void ma_dmg_stretch(const MaProfView& v, bool single_stranded, int64_t base, Found&& found) {
-  if (base >= v.T) return;
-  const MaRecWord sq = ma_rec_load(v.seq + base), sm = ma_rec_load(v.smp + base);
-  int64_t r = ma_prof_record_of(v, base);
-  int64_t o0 = v.col_off[r], end = v.col_off[r + 1];
-  int32_t start = v.start[r];
-  bool rc = v.revcom[r] != 0, used = !v.use || v.use[r] != 0;
+MIA_HD inline void ma_dmg_stretch(const MaFlatView& v, bool single_stranded, int64_t base, Found&& found) {
   uint32_t h5 = 0, h3 = 0;
-  MA_PROF_UNROLL
-  for (int w = 0; w < MA_DMG_LANE / 4; w++) {
-    uint32_t a = sq.w[w], b = sm.w[w];
-    MA_PROF_NOUNROLL
-    for (int q = 0; q < 4; q++, a >>= 8, b >>= 8) {
-      const int64_t pos = base + w * 4 + q;
-      if (pos >= v.T) continue;
-      if (pos >= end) {                    // (pos < T = col_off[n]: r stays below n)
+  ma_flat_stretch<false>(
+      v, base,
+      [&](const MaFlatColumn& c) {
+        if (!c.used) return;
+        const bool beyond = c.p >= v.L;
+        const int hit = ma_dmg_hit(ma_prof_bin(beyond, beyond ? '\0' : v.ref[c.p], c.seq_ch, c.smp_ch, c.rc), single_stranded);
+        const uint32_t val = (uint32_t)(MA_DMG_CLASSES - (hit < 0 ? -hit : hit));
+        if (hit > 0 && val > h5) h5 = val;
+        if (hit < 0 && val > h3) h3 = val;
+      },
+      [&](int64_t r, bool) {
         if (h5 | h3) found(r, h5, h3);
         h5 = h3 = 0;
-        do { r++; end = v.col_off[r + 1]; } while (pos >= end);
-        o0 = v.col_off[r];
-        start = v.start[r]; rc = v.revcom[r] != 0; used = !v.use || v.use[r] != 0;
-      }
-      if (!used) continue;
-      const int64_t p = (int64_t)start + (pos - o0);
-      const bool beyond = p >= v.L;
-      const int hit = ma_dmg_hit(ma_prof_bin(beyond, beyond ? '\0' : v.ref[p], (char)(a & 0xffu), (char)(b & 0xffu), rc), single_stranded);
-      const uint32_t val = (uint32_t)(MA_DMG_CLASSES - (hit < 0 ? -hit : hit));
-      if (hit > 0 && val > h5) h5 = val;
-      if (hit < 0 && val > h3) h3 = val;
-    }
-  }
-  if (h5 | h3) found(r, h5, h3);
+      });
 }
 
 // The molecule stage's view: what the hits stage left per record, the pairing and the question asked.
@@ -83,7 +68,7 @@ struct MaDmgMolView {
   int64_t n;
   const uint8_t* revcom;     // [n]
   const uint8_t* use;        // [n] or NULL
-  const int64_t* mate;       // [n] or NULL: MA_DMG_NONE, MA_DMG_ORPHAN or the other half (validated by the caller)
+  const int64_t* mate;       // [n] or NULL: MA_MOL_NONE, MA_MOL_ORPHAN or the other half (validated by the caller)
   const uint32_t* hit5;      // [n]: 16 - k of the record's smallest 5' hit, 0 for none
   const uint32_t* hit3;      // [n]
   int32_t n_pos, mode;
@@ -105,35 +90,22 @@ MIA_HD inline void ma_dmg_record(const MaDmgMolView& v, int64_t r, Count&& count
   uint32_t h5 = v.hit5[r], h3 = v.hit3[r];
   v.pos5[r] = (uint8_t)(h5 ? MA_DMG_CLASSES - h5 : 0);
   v.pos3[r] = (uint8_t)(h3 ? MA_DMG_CLASSES - h3 : 0);
-  const int64_t m = v.mate ? v.mate[r] : MA_DMG_NONE;
-  if (m >= 0 && m < r) return;             // the other half decides
-  bool counts = !v.use || v.use[r] != 0;
-  if (m >= 0) {
-    const uint32_t o5 = v.hit5[m], o3 = v.hit3[m];
-    if (o5 > h5) h5 = o5;
-    if (o3 > h3) h3 = o3;
-    counts = counts || !v.use || v.use[m] != 0;
-  }
-  const int m5 = h5 ? MA_DMG_CLASSES - (int)h5 : 0, m3 = h3 ? MA_DMG_CLASSES - (int)h3 : 0;
-  const bool k = ma_dmg_keep(m5, m3, v.n_pos, v.mode);
-  v.keep[r] = k ? 1 : 0;
-  if (m >= 0) v.keep[m] = k ? 1 : 0;
-  if (counts) {
-    count(ma_dmg_hist_bin(v.revcom[r] != 0 ? 1 : 0, m5, m3));
-    if (m == MA_DMG_ORPHAN) count(MA_DMG_ORPHANS);
-  }
-  if (k) { count(MA_DMG_KEPT); if (m >= 0) count(MA_DMG_KEPT); }
-}
-
-// mate[r] for every r: MA_DMG_NONE, MA_DMG_ORPHAN, or another record whose mate is r (host: the entry point's check)
-inline bool ma_dmg_mate_ok(const int64_t* mate, int64_t n) {
-  if (!mate) return true;
-  for (int64_t r = 0; r < n; r++) {
-    const int64_t m = mate[r];
-    if (m == MA_DMG_NONE || m == MA_DMG_ORPHAN) continue;
-    if (m < 0 || m >= n || m == r || mate[m] != r) return false;
-  }
-  return true;
+  ma_molecule_join(
+      v.mate, v.use, r, MA_DMG_ORPHANS, MA_DMG_KEPT,
+      [&](int64_t m, int* bin) {
+        if (m >= 0) {
+          const uint32_t o5 = v.hit5[m], o3 = v.hit3[m];
+          if (o5 > h5) h5 = o5;
+          if (o3 > h3) h3 = o3;
+        }
+        const int m5 = h5 ? MA_DMG_CLASSES - (int)h5 : 0, m3 = h3 ? MA_DMG_CLASSES - (int)h3 : 0;
+        const bool k = ma_dmg_keep(m5, m3, v.n_pos, v.mode);
+        v.keep[r] = k ? 1 : 0;
+        if (m >= 0) v.keep[m] = k ? 1 : 0;
+        *bin = ma_dmg_hist_bin(v.revcom[r] != 0 ? 1 : 0, m5, m3);
+        return k;
+      },
+      count);
 }
 
 // ---- the report (host) ------------------------------------------------------------------------------------------------------------

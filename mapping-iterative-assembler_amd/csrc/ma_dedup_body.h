@@ -22,11 +22,11 @@
 #pragma once
 #include <stdint.h>
 
-#include "ma_records.h"                    // MIA_HD
+#include "ma_molecule_body.h"
 
 namespace mia {
 
-constexpr int64_t MA_DEDUP_NONE = -1, MA_DEDUP_ORPHAN = -2;
+constexpr int64_t MA_DEDUP_NONE = MA_MOL_NONE, MA_DEDUP_ORPHAN = MA_MOL_ORPHAN;   // the one encoding of mate (ma_molecule_body.h)
 constexpr int MA_DEDUP_MAX_TOL = 100;
 constexpr int MA_DEDUP_SIZES = 1025;                       // bins 1 .. 1023, bin 1024 = larger; bin 0 unused
 constexpr int MA_DEDUP_HIST = 2 * MA_DEDUP_SIZES;          // [strand][size]

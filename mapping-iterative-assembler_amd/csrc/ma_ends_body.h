@@ -19,7 +19,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "ma_profile_body.h"               // ma_prof_class, ma_prof_mirror and MA_PROF_UNROLL
+#include "ma_profile_body.h"               // ma_prof_class, ma_prof_mirror and MA_FLAT_UNROLL
 #include "ma_records.h"
 
 namespace mia {
@@ -71,7 +71,7 @@ MIA_HD inline int64_t ma_ends_bases(const char* seq, int64_t off, int64_t n) {
   for (int64_t base = off & ~(int64_t)(MA_REC_LANE - 1); base < end; base += MA_REC_LANE) {
     const MaRecWord x = ma_rec_load(seq + base);
     uint32_t m = 0;                        // bit b: byte b of the word is '-'
-    MA_PROF_UNROLL
+    MA_FLAT_UNROLL
     for (int w = 0; w < MA_REC_LANE / 4; w++) m |= (((ma_ends_dash_flags(x.w[w]) >> 7) * 0x00204081u >> 21) & 0xfu) << (4 * w);
     const int lo = off > base ? (int)(off - base) : 0, hi = end - base < MA_REC_LANE ? (int)(end - base) : MA_REC_LANE;
     dashes += __builtin_popcount(m & ((1u << hi) - 1u) & ~((1u << lo) - 1u));

@@ -9,8 +9,8 @@
 // deamination makes (5': T; 3': A, single-stranded T).
 //
 // Plain C++ behind MIA_HD.  k_ma_mask_bounds (mia_ma_mask_kernels.h) gives every lane a stretch of MA_MASK_LANE flat positions:
-// ma_mask_stretch walks it as ma_prof_stretch does, keeps a1 / b1 of the record it is in in registers, hands them to its caller when
-// the record changes and at the stretch's end, and hands every zone column (substitution mode: every substituted column) to a counter.
+// ma_mask_stretch is the shared walk (ma_flat_body.h) with this rule: it keeps a1 / b1 of the record it is in in registers, hands them
+// to its caller when the walk leaves the record, and hands every zone column (substitution mode: every substituted column) to a counter.
 // k_ma_mask_layout gives every lane a record: ma_mask_record walks the '-' columns and decides.  k_ma_mask_apply gives every lane a
 // stretch of the NEW layout: ma_mask_gather reads its 16 columns from where they were.  The counts of trim mode are a difference: the
 // bounds stage counts every zone column, the apply stage every zone column that stays (in a mia-written file: none), since a column's
@@ -22,7 +22,7 @@
 
 namespace mia {
 
-constexpr int MA_MASK_LANE = MA_PROF_LANE;
+constexpr int MA_MASK_LANE = MA_FLAT_LANE;
 constexpr int MA_MASK_MAX_POS = 15;                                    // n5, n3 lie in 0 .. 15, k in 1 .. 15
 constexpr int MA_MASK_K = MA_MASK_MAX_POS + 1;
 constexpr int MA_MASK_HIST = 2 * 2 * MA_MASK_K;                        // hist[strand][end][k]
@@ -61,43 +61,29 @@ MIA_HD inline bool ma_mask_substituted(char seq_ch, int zone, bool rc, bool sing
 // (MA_MASK_NO_COLUMN: none), hi = one behind the last such column (0: none), whole = every column of r lies inside the stretch; and
 // count(bin) for every zone column.  Substitution mode: no found, count(bin) for every substituted column.
 template <class Found, class Count>
-MIA_HD inline void ma_mask_stretch(const MaProfView& v, int n5, int n3, int mode, bool single_stranded, int64_t base, Found&& found, Count&& count) {
-  if (base >= v.T) return;
-  const MaRecWord sq = ma_rec_load(v.seq + base), sm = ma_rec_load(v.smp + base);
-  int64_t r = ma_prof_record_of(v, base);
-  int64_t o0 = v.col_off[r], end = v.col_off[r + 1];
-  bool rc = v.revcom[r] != 0;
+MIA_HD inline void ma_mask_stretch(const MaFlatView& v, int n5, int n3, int mode, bool single_stranded, int64_t base, Found&& found, Count&& count) {
   uint32_t lo = MA_MASK_NO_COLUMN, hi = 0;
-  MA_PROF_UNROLL
-  for (int w = 0; w < MA_MASK_LANE / 4; w++) {
-    uint32_t a = sq.w[w], b = sm.w[w];
-    MA_PROF_NOUNROLL
-    for (int q = 0; q < 4; q++, a >>= 8, b >>= 8) {
-      const int64_t pos = base + w * 4 + q;
-      if (pos >= v.T) continue;
-      if (pos >= end) {                    // (pos < T = col_off[n]: r stays below n)
-        if (mode == MA_MASK_TRIM) found(r, lo, hi, o0 >= base);
+  ma_flat_stretch<false>(
+      v, base,
+      [&](const MaFlatColumn& c) {
+        const int zone = ma_mask_zone(c.smp_ch, c.rc, n5, n3);
+        const uint32_t col = (uint32_t)c.col;
+        if (mode == MA_MASK_TRIM) {
+          if (zone) count(ma_mask_hist_bin(c.rc, zone));
+          else { if (lo == MA_MASK_NO_COLUMN) lo = col; hi = col + 1; }
+        } else if (zone && ma_mask_substituted(c.seq_ch, zone, c.rc, single_stranded)) {
+          count(ma_mask_hist_bin(c.rc, zone));
+        }
+      },
+      [&](int64_t r, bool whole) {
+        if (mode == MA_MASK_TRIM) found(r, lo, hi, whole);
         lo = MA_MASK_NO_COLUMN; hi = 0;
-        do { r++; end = v.col_off[r + 1]; } while (pos >= end);
-        o0 = v.col_off[r];
-        rc = v.revcom[r] != 0;
-      }
-      const int zone = ma_mask_zone((char)(b & 0xffu), rc, n5, n3);
-      const uint32_t c = (uint32_t)(pos - o0);
-      if (mode == MA_MASK_TRIM) {
-        if (zone) count(ma_mask_hist_bin(rc, zone));
-        else { if (lo == MA_MASK_NO_COLUMN) lo = c; hi = c + 1; }
-      } else if (zone && ma_mask_substituted((char)(a & 0xffu), zone, rc, single_stranded)) {
-        count(ma_mask_hist_bin(rc, zone));
-      }
-    }
-  }
-  if (mode == MA_MASK_TRIM) found(r, lo, hi, o0 >= base && end <= base + MA_MASK_LANE);
+      });
 }
 
 // The layout stage's view: the records, what the bounds stage left per record, and the new record view's scalars per record.
 struct MaMaskRecView {
-  MaProfView v;
+  MaFlatView v;
   int32_t n5, n3, mode;
   const uint32_t* lo;        // [n]: a1, or MA_MASK_NO_COLUMN (trim mode)
   const uint32_t* hi;        // [n]: b1, or 0
@@ -138,7 +124,7 @@ MIA_HD inline int64_t ma_mask_record(const MaMaskRecView& m, int64_t r, Count&& 
 
 // The apply stage's view: the records as they were, where every record's columns go, and the question asked.
 struct MaMaskApplyView {
-  MaProfView v;              // the records as tallied
+  MaFlatView v;              // the records as tallied
   int32_t n5, n3, mode, single_stranded;
   const int32_t* first;      // [n]
   const int64_t* new_off;    // [n+1]: record r's kept columns are flat positions new_off[r] .. new_off[r+1) of the new strings
@@ -188,10 +174,10 @@ MIA_HD inline void ma_mask_gather(const MaMaskApplyView& m, int64_t base, MaRecW
     bool rc = m.v.revcom[r] != 0, head = true;
     const int64_t limit = (m.v.T + MA_REC_LANE - 1) & ~(int64_t)(MA_REC_LANE - 1);
     const MaRecWord sq = ma_mask_load_unaligned(m.v.seq, base + delta, limit), sm = ma_mask_load_unaligned(m.v.smp, base + delta, limit);
-    MA_PROF_UNROLL
+    MA_FLAT_UNROLL
     for (int w = 0; w < MA_MASK_LANE / 4; w++) {
       uint32_t a = sq.w[w], b = sm.w[w], sa = 0, sb = 0;
-      MA_PROF_NOUNROLL
+      MA_FLAT_NOUNROLL
       for (int q = 0; q < 4; q++, a >>= 8, b >>= 8) {
         const int64_t pos = base + w * 4 + q;
         if (pos >= m.new_T) continue;

@@ -7,11 +7,11 @@
 // when S >= threshold, and hist[strand][bin] counts the molecules by bin = clamp(floor(S / 32768) + 20, 0, 63), half a nat per bin.
 //
 // Plain C++ behind MIA_HD.  k_ma_score_cols (mia_ma_pmd_kernels.h) gives every lane a stretch of MA_PMD_LANE flat positions:
-// ma_pmd_stretch walks it as ma_dmg_stretch does, sums the weights of the record it is in in a register and hands the sum to its caller
-// when the record changes and at the stretch's end -- at most one call per record of the stretch, and none for a sum of zero.
-// k_ma_score_molecules gives every lane a record: ma_pmd_record adds the halves, decides keep and names the molecule's bin.  A host
-// caller (tests/ma_pmd_driver.cpp) runs the same code stretch by stretch and record by record.  The model that fills the table from
-// four parameters (ma_pmd_model, host only) is at the end.
+// ma_pmd_stretch is the shared walk (ma_flat_body.h) with this rule: it sums the weights of the record it is in in a register and hands
+// the sum to its caller when the walk leaves the record -- at most one call per record of the stretch, and none for a sum of zero.
+// k_ma_score_molecules gives every lane a record: ma_pmd_record is the shared join (ma_molecule_body.h) with this rule: it adds the
+// halves, decides keep and names the molecule's bin.  A host caller (tests/ma_pmd_driver.cpp) runs the same code stretch by stretch
+// and record by record.  The model that fills the table from four parameters (ma_pmd_model, host only) is at the end.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -20,7 +20,7 @@
 
 namespace mia {
 
-constexpr int MA_PMD_LANE = MA_PROF_LANE;
+constexpr int MA_PMD_LANE = MA_FLAT_LANE;
 constexpr int MA_PMD_WEIGHTS = MA_PROF_COUNTS;                         // 775: w[31][5][5]
 constexpr int32_t MA_PMD_MAX_WEIGHT = 1 << 20;                         // |w| of an entry: 16 positions of a lane stay inside int32
 constexpr int MA_PMD_HIST_BINS = 64, MA_PMD_HIST = 2 * MA_PMD_HIST_BINS;           // hist[strand][bin]
@@ -44,35 +44,19 @@ MIA_HD inline int32_t ma_pmd_weight(const int32_t* w, bool beyond, char ref_ch, 
 // The stretch of flat positions base .. base + MA_PMD_LANE - 1 (base a multiple of MA_PMD_LANE): found(r, sum) is called once for
 // every record r of the stretch whose columns there add up to something other than zero (|sum| <= 16 * MA_PMD_MAX_WEIGHT).
 template <class Found>
-MIA_HD inline void ma_pmd_stretch(const MaProfView& v, const int32_t* w, int64_t base, Found&& found) {
-  if (base >= v.T) return;
-  const MaRecWord sq = ma_rec_load(v.seq + base), sm = ma_rec_load(v.smp + base);
-  int64_t r = ma_prof_record_of(v, base);
-  int64_t o0 = v.col_off[r], end = v.col_off[r + 1];
-  int32_t start = v.start[r];
-  bool rc = v.revcom[r] != 0, used = !v.use || v.use[r] != 0;
+MIA_HD inline void ma_pmd_stretch(const MaFlatView& v, const int32_t* w, int64_t base, Found&& found) {
   int32_t sum = 0;
-  MA_PROF_UNROLL
-  for (int k = 0; k < MA_PMD_LANE / 4; k++) {
-    uint32_t a = sq.w[k], b = sm.w[k];
-    MA_PROF_NOUNROLL
-    for (int q = 0; q < 4; q++, a >>= 8, b >>= 8) {
-      const int64_t pos = base + k * 4 + q;
-      if (pos >= v.T) continue;
-      if (pos >= end) {                    // (pos < T = col_off[n]: r stays below n)
+  ma_flat_stretch<false>(
+      v, base,
+      [&](const MaFlatColumn& c) {
+        if (!c.used) return;
+        const bool beyond = c.p >= v.L;
+        sum += ma_pmd_weight(w, beyond, beyond ? '\0' : v.ref[c.p], c.seq_ch, c.smp_ch, c.rc);
+      },
+      [&](int64_t r, bool) {
         if (sum) found(r, sum);
         sum = 0;
-        do { r++; end = v.col_off[r + 1]; } while (pos >= end);
-        o0 = v.col_off[r];
-        start = v.start[r]; rc = v.revcom[r] != 0; used = !v.use || v.use[r] != 0;
-      }
-      if (!used) continue;
-      const int64_t p = (int64_t)start + (pos - o0);
-      const bool beyond = p >= v.L;
-      sum += ma_pmd_weight(w, beyond, beyond ? '\0' : v.ref[p], (char)(a & 0xffu), (char)(b & 0xffu), rc);
-    }
-  }
-  if (sum) found(r, sum);
+      });
 }
 
 // The molecule stage's view: what the column stage left per record, the pairing and the threshold.
@@ -80,7 +64,7 @@ struct MaPmdMolView {
   int64_t n;
   const uint8_t* revcom;     // [n]
   const uint8_t* use;        // [n] or NULL
-  const int64_t* mate;       // [n] or NULL: MA_DMG_NONE, MA_DMG_ORPHAN or the other half (validated by the caller)
+  const int64_t* mate;       // [n] or NULL: MA_MOL_NONE, MA_MOL_ORPHAN or the other half (validated by the caller)
   const int64_t* rec_score;  // [n]: the sum of the record's weights
   int64_t threshold;
   int64_t* mol_score;        // [n] out: the score of the record's molecule
@@ -100,23 +84,19 @@ MIA_HD inline int ma_pmd_hist_bin(int strand, int64_t S) { return strand * MA_PM
 // it, and count(bin) for every bin the molecule adds to (its bin if it counts, the orphans, the records kept).
 template <class Count>
 MIA_HD inline void ma_pmd_record(const MaPmdMolView& v, int64_t r, Count&& count) {
-  const int64_t m = v.mate ? v.mate[r] : MA_DMG_NONE;
-  if (m >= 0 && m < r) return;             // the other half decides
-  int64_t S = v.rec_score[r];
-  bool counts = !v.use || v.use[r] != 0;
-  if (m >= 0) {
-    S += v.rec_score[m];
-    counts = counts || !v.use || v.use[m] != 0;
-  }
-  const bool k = S >= v.threshold;
-  v.mol_score[r] = S;
-  v.keep[r] = k ? 1 : 0;
-  if (m >= 0) { v.mol_score[m] = S; v.keep[m] = k ? 1 : 0; }
-  if (counts) {
-    count(ma_pmd_hist_bin(v.revcom[r] != 0 ? 1 : 0, S));
-    if (m == MA_DMG_ORPHAN) count(MA_PMD_ORPHANS);
-  }
-  if (k) { count(MA_PMD_KEPT); if (m >= 0) count(MA_PMD_KEPT); }
+  ma_molecule_join(
+      v.mate, v.use, r, MA_PMD_ORPHANS, MA_PMD_KEPT,
+      [&](int64_t m, int* bin) {
+        int64_t S = v.rec_score[r];
+        if (m >= 0) S += v.rec_score[m];
+        const bool k = S >= v.threshold;
+        v.mol_score[r] = S;
+        v.keep[r] = k ? 1 : 0;
+        if (m >= 0) { v.mol_score[m] = S; v.keep[m] = k ? 1 : 0; }
+        *bin = ma_pmd_hist_bin(v.revcom[r] != 0 ? 1 : 0, S);
+        return k;
+      },
+      count);
 }
 
 // ---- the model and the report (host) ----------------------------------------------------------------------------------------------

@@ -9,43 +9,26 @@
 // The 808 bins are count[31][5][5] | del[31] | bad_code | beyond.
 //
 // Plain C++ behind MIA_HD.  k_ma_profile (mia_ma_profile_kernels.h) gives every lane a stretch of MA_PROF_LANE flat positions of
-// the records' concatenated SEQ / SMP strings: ma_prof_stretch finds the record of the first by bisection, walks on from there and
-// hands every position's bin to its caller; a host caller (tests/ma_profile_driver.cpp) runs the same code stretch by stretch.
+// the records' concatenated SEQ / SMP strings: ma_prof_stretch is the shared walk (ma_flat_body.h) that hands every position's bin
+// to its caller; a host caller (tests/ma_profile_driver.cpp) runs the same code stretch by stretch.
 // Labels and scores of the two reports (host/ma_main.cpp) are at the end.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
-#include "ma_records.h"
-
-#if defined(__clang__)
-#define MA_PROF_UNROLL _Pragma("unroll")
-#define MA_PROF_NOUNROLL _Pragma("nounroll")
-#else
-#define MA_PROF_UNROLL
-#define MA_PROF_NOUNROLL
-#endif
+#include "ma_flat_body.h"
 
 namespace mia {
 
 constexpr int MA_PROF_DEPTHS = 31, MA_PROF_CLASSES = 5, MA_PROF_MIDDLE = 15;
 constexpr int MA_PROF_COUNTS = MA_PROF_DEPTHS * MA_PROF_CLASSES * MA_PROF_CLASSES;                 // 775
 constexpr int MA_PROF_DEL = MA_PROF_COUNTS, MA_PROF_BAD = MA_PROF_DEL + MA_PROF_DEPTHS, MA_PROF_BEYOND = MA_PROF_BAD + 1, MA_PROF_BINS = MA_PROF_BEYOND + 1;   // 808
-constexpr int MA_PROF_LANE = MA_REC_LANE;  // flat positions of one stretch: one 16-byte word of SEQ and one of SMP
+constexpr int MA_PROF_LANE = MA_FLAT_LANE;
+// the view and the bisection under the names they had while they lived here (ma_flat_body.h has them now): callers written for those
+using MaProfView = MaFlatView;
+MIA_HD inline int64_t ma_prof_record_of(const MaFlatView& v, int64_t pos) { return ma_flat_record_of(v, pos); }
 constexpr int MA_PROF_HOT = 4;             // (MIDDLE, X, X) for X in ACGT: where most events of a real assembly fall
-
-// The records (ma_records.h: seq and smp are loaded in whole 16-byte words), the reference and the selection.
-struct MaProfView : MaRecords {
-  int64_t T;                 // col_off[n] flat positions
-  const char* ref;           // [L]
-  const uint8_t* use;        // [n]: 0 = the record is left out; NULL = every record counts
-  MaProfView(const MaRecords& recs, int64_t T, const char* ref, const uint8_t* use) : MaRecords(recs), T(T), ref(ref), use(use) {}
-  // ... or from the arrays this export reads alone, for a caller that holds no more (the host drivers): the rest of MaRecords is null
-  MaProfView(int64_t n, int64_t T, int32_t L, const int32_t* start, const uint8_t* revcom, const int64_t* col_off, const char* seq, const char* smp,
-             const char* ref, const uint8_t* use)
-      : MaRecords{n, L, start, revcom, col_off, seq, nullptr, nullptr, nullptr, nullptr, nullptr, smp}, T(T), ref(ref), use(use) {}
-};
 
 MIA_HD inline int ma_prof_class(char c) {
   switch (c) {
@@ -77,56 +60,23 @@ MIA_HD inline int ma_prof_hot(int bin) {
 }
 MIA_HD inline int ma_prof_hot_bin(int h) { return MA_PROF_MIDDLE * MA_PROF_CLASSES * MA_PROF_CLASSES + h * (MA_PROF_CLASSES + 1); }
 
-// the record that holds flat position pos (0 <= pos < T): the last r with col_off[r] <= pos -- records without columns hold none
-MIA_HD inline int64_t ma_prof_record_of(const MaProfView& v, int64_t pos) {
-  int64_t lo = 0, hi = v.n;                // col_off[lo] <= pos < col_off[hi]
-  while (hi - lo > 1) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (v.col_off[mid] <= pos) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// The stretch of flat positions base .. base + MA_PROF_LANE - 1 (base a multiple of MA_PROF_LANE): emit(bin) is called
-// MA_PROF_LANE times, in order, with the position's bin -- or with -1 for a position at or behind T and for a column of a record
-// that is left out.  One bisection per stretch, then forward from record to record.  Every caller makes all MA_PROF_LANE calls
-// whatever its base, so a wavefront's lanes reach each of them together.
+// The stretch of flat positions base .. base + MA_PROF_LANE - 1 (base a multiple of MA_PROF_LANE; the walk: ma_flat_body.h): emit(bin)
+// is called MA_PROF_LANE times, in order, with the position's bin -- or with -1 for a position at or behind T and for a column of a
+// record that is left out.  Every caller makes all MA_PROF_LANE calls whatever its base, so a wavefront's lanes reach each of them
+// together.
 template <class Emit>
-MIA_HD inline void ma_prof_stretch(const MaProfView& v, int64_t base, Emit&& emit) {
-  MaRecWord sq{{0, 0, 0, 0}}, sm{{0, 0, 0, 0}};
-  int64_t r = 0, end = 0, o0 = 0;
-  int32_t start = 0;
-  bool rc = false, used = false;
-  if (base < v.T) {
-    sq = ma_rec_load(v.seq + base);
-    sm = ma_rec_load(v.smp + base);
-    r = ma_prof_record_of(v, base);
-    o0 = v.col_off[r]; end = v.col_off[r + 1];
-    start = v.start[r]; rc = v.revcom[r] != 0; used = !v.use || v.use[r] != 0;
-  }
-  // (the four words unrolled, so that each is a register; the four characters of a word one loop, so that the code stays short)
-  MA_PROF_UNROLL
-  for (int w = 0; w < MA_PROF_LANE / 4; w++) {
-    uint32_t a = sq.w[w], b = sm.w[w];
-    MA_PROF_NOUNROLL
-    for (int q = 0; q < 4; q++, a >>= 8, b >>= 8) {
-      const int64_t pos = base + w * 4 + q;
-      int bin = -1;
-      if (pos < v.T) {
-        if (pos >= end) {                  // (pos < T = col_off[n]: r stays below n)
-          do { r++; end = v.col_off[r + 1]; } while (pos >= end);
-          o0 = v.col_off[r];
-          start = v.start[r]; rc = v.revcom[r] != 0; used = !v.use || v.use[r] != 0;
+MIA_HD inline void ma_prof_stretch(const MaFlatView& v, int64_t base, Emit&& emit) {
+  ma_flat_stretch<true>(
+      v, base,
+      [&](const MaFlatColumn& c) {
+        int bin = -1;
+        if (c.live && c.used) {
+          const bool beyond = c.p >= v.L;
+          bin = ma_prof_bin(beyond, beyond ? '\0' : v.ref[c.p], c.seq_ch, c.smp_ch, c.rc);
         }
-        if (used) {
-          const int64_t p = (int64_t)start + (pos - o0);
-          const bool beyond = p >= v.L;
-          bin = ma_prof_bin(beyond, beyond ? '\0' : v.ref[p], (char)(a & 0xffu), (char)(b & 0xffu), rc);
-        }
-      }
-      emit(bin);
-    }
-  }
+        emit(bin);
+      },
+      [](int64_t, bool) {});
 }
 
 // ---- the two reports (host) ---------------------------------------------------------------------------------------------------

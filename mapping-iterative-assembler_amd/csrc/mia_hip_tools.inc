@@ -121,6 +121,47 @@ static int ma_selection(mia_hip_ctx* ctx, const uint8_t* segment, const uint8_t*
   return MIA_HIP_OK;
 }
 
+// A persistent grid: the workgroups that are resident at once (per_cu on every compute unit), or `wgs`, one per chunk of the work,
+// when there are fewer -- and one workgroup that finds no chunk where there is no work (records that all lack columns).
+static dim3 ma_grid(const mia_hip_ctx* ctx, int64_t wgs, int per_cu) {
+  const int64_t wide = (int64_t)ctx->cus * per_cu;
+  return dim3((unsigned)(wgs < 1 ? 1 : wgs < wide ? wgs : wide));
+}
+
+// A result's way down, queued on the context's stream: nothing for a caller who passed no buffer and for an empty result.
+static hipError_t ma_down(mia_hip_ctx* ctx, void* host, const void* dev, size_t bytes) {
+  return host && bytes ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+}
+
+// What the two filters by molecule (damage, score) share in front of their launches.  The checks, in the order the callers always
+// had them: the records are resident, there is a reference, the caller's own arguments are right (own_error: what is wrong with
+// them, or NULL), col_off starts at 0, mate pairs the records.  Then, with records: the reference, the selection and the pairing go
+// up (mate into the caller's own buffer), and the view of the flat columns and the two grids -- over col_wgs chunks of columns and
+// rec_wgs chunks of records -- are made.
+struct MaMolFrame { MaFlatView v{MaRecords{}, 0, nullptr, nullptr}; const int64_t* mate = nullptr; dim3 col_grid, rec_grid; };
+static int ma_mol_frame(mia_hip_ctx* ctx, const char* who, const char* ref_seq, const uint8_t* use, const int64_t* mate, const char* own_error,
+                        DevBuf<int64_t>& d_mate, int64_t col_wgs, int64_t rec_wgs, int per_cu, MaMolFrame* f) {
+  const std::string name = who;
+  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede " + name; return MIA_HIP_ERR_STATE; }
+  if (!ref_seq) { ctx->err = name + ": no reference sequence"; return MIA_HIP_ERR_ARG; }
+  if (own_error) { ctx->err = name + ": " + own_error; return MIA_HIP_ERR_ARG; }
+  if (ctx->ma_n > 0 && ctx->ma_cols < 0) { ctx->err = name + ": col_off[0] of the tallied records is not 0"; return MIA_HIP_ERR_ARG; }
+  const int64_t n = ctx->ma_n;
+  if (!ma_mate_ok(mate, n)) { ctx->err = name + ": mate is out of range, the record itself or not mutual"; return MIA_HIP_ERR_ARG; }
+  if (n == 0) return MIA_HIP_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  MaSelection sel;
+  if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)ctx->ma_L) || (mate && dev_ensure(ctx, d_mate, n))) return MIA_HIP_ERR_NOMEM;
+  if (const int rc = ma_selection(ctx, nullptr, use, &sel)) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)ctx->ma_L, hipMemcpyHostToDevice, ctx->stream));
+  if (mate) HIPCHK(hipMemcpyAsync(d_mate, mate, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  f->v = MaFlatView{ma_records(ctx), ctx->ma_cols, ctx->d_prof_ref, sel.use};
+  f->mate = mate ? (const int64_t*)d_mate : nullptr;
+  f->col_grid = ma_grid(ctx, col_wgs, per_cu);
+  f->rec_grid = ma_grid(ctx, rec_wgs, per_cu);
+  return MIA_HIP_OK;
+}
+
 extern "C" int mia_hip_ma_tally(mia_hip_ctx* ctx, int32_t ref_len, const int32_t* gaps, int64_t n, const int32_t* start,
                                 const uint8_t* revcom, const int64_t* col_off, const char* seq, const char* smp, int64_t n_ins,
                                 const int32_t* ins_record, const int32_t* ins_pos, const int64_t* ins_off, const char* ins_bases) {
@@ -254,9 +295,8 @@ extern "C" int mia_hip_get_ma_region(mia_hip_ctx* ctx, int64_t* rows, char* text
   if (!ctx->ma_resident || !ctx->ma_out.region_done) { ctx->err = "ma_region first"; return MIA_HIP_ERR_STATE; }
   if (cap_rows < ctx->ma_out.rows) { ctx->err = "get_ma_region: buffers too small"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
-  if (rows && ctx->ma_out.rows > 0) HIPCHK(hipMemcpyAsync(rows, ctx->d_ma_rows, (size_t)ctx->ma_out.rows * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (text && ctx->ma_out.rows > 0 && ctx->ma_out.width > 0)
-    HIPCHK(hipMemcpyAsync(text, ctx->d_ma_text, (size_t)(ctx->ma_out.rows * ctx->ma_out.width), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ma_down(ctx, rows, ctx->d_ma_rows, (size_t)ctx->ma_out.rows * 8));
+  HIPCHK(ma_down(ctx, text, ctx->d_ma_text, (size_t)(ctx->ma_out.rows * ctx->ma_out.width)));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }
@@ -310,10 +350,10 @@ extern "C" int mia_hip_get_ma_ace(mia_hip_ctx* ctx, int64_t* af_pos, int64_t* pa
   if (body && cap_bytes < ctx->ma_out.ace_bytes) { ctx->err = "get_ma_ace: buffer too small"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = ctx->ma_n;
-  if (af_pos && n > 0) HIPCHK(hipMemcpyAsync(af_pos, ctx->d_ace_af, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (padded_len && n > 0) HIPCHK(hipMemcpyAsync(padded_len, ctx->d_ace_len, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (body_off) HIPCHK(hipMemcpyAsync(body_off, ctx->d_ace_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (body && ctx->ma_out.ace_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_ace_body, (size_t)ctx->ma_out.ace_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ma_down(ctx, af_pos, ctx->d_ace_af, (size_t)n * 8));
+  HIPCHK(ma_down(ctx, padded_len, ctx->d_ace_len, (size_t)n * 8));
+  HIPCHK(ma_down(ctx, body_off, ctx->d_ace_off, (size_t)(n + 1) * 8));
+  HIPCHK(ma_down(ctx, body, ctx->d_ace_body, (size_t)ctx->ma_out.ace_bytes));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }
@@ -367,9 +407,9 @@ extern "C" int mia_hip_get_ma_sam(mia_hip_ctx* ctx, int32_t* nm, int64_t* body_o
   if (body && cap_bytes < ctx->ma_out.sam_bytes) { ctx->err = "get_ma_sam: buffer too small"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t n = ctx->ma_n;
-  if (nm && n > 0) HIPCHK(hipMemcpyAsync(nm, ctx->d_sam_nm, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (body_off) HIPCHK(hipMemcpyAsync(body_off, ctx->d_sam_off, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (body && ctx->ma_out.sam_bytes > 0) HIPCHK(hipMemcpyAsync(body, ctx->d_sam_body, (size_t)ctx->ma_out.sam_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ma_down(ctx, nm, ctx->d_sam_nm, (size_t)n * 4));
+  HIPCHK(ma_down(ctx, body_off, ctx->d_sam_off, (size_t)(n + 1) * 8));
+  HIPCHK(ma_down(ctx, body, ctx->d_sam_body, (size_t)ctx->ma_out.sam_bytes));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return MIA_HIP_OK;
 }
@@ -390,12 +430,8 @@ extern "C" int mia_hip_ma_profile(mia_hip_ctx* ctx, const char* ref_seq, const u
   HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(hipMemsetAsync(ctx->d_prof_bins, 0, (size_t)MA_PROF_BINS * 8, ctx->stream));
   if (n > 0) {                                              // (records that all lack columns: one workgroup that finds no chunk)
-    MaProfView v{ma_records(ctx), T, ctx->d_prof_ref, sel.use};
-    // persistent grid: the workgroups that are resident at once, or one per chunk when there are fewer chunks
-    int64_t grid = (int64_t)ctx->cus * MAP_WGS_PER_CU;
-    if (grid > ma_prof_chunks(T)) grid = ma_prof_chunks(T);
-    if (grid < 1) grid = 1;
-    if (stage_launch(ctx, STG_MA_PROFILE, k_ma_profile, dim3((unsigned)grid), dim3(MAP_THREADS), 0, ctx->stream, v, (unsigned long long*)ctx->d_prof_bins))
+    MaFlatView v{ma_records(ctx), T, ctx->d_prof_ref, sel.use};
+    if (stage_launch(ctx, STG_MA_PROFILE, k_ma_profile, ma_grid(ctx, ma_prof_chunks(T), MAP_WGS_PER_CU), dim3(MAP_THREADS), 0, ctx->stream, v, (unsigned long long*)ctx->d_prof_bins))
       return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipGetLastError());
   }
@@ -437,10 +473,7 @@ extern "C" int mia_hip_ma_ends(mia_hip_ctx* ctx, const char* ref_seq, const uint
   HIPCHK(hipMemsetAsync(ctx->d_ends_bins, 0, (size_t)MA_ENDS_BINS * 8, ctx->stream));
   if (n > 0) {
     MaEndsView v{ma_records(ctx), ctx->d_prof_ref, sel.segment, sel.use};
-    // persistent grid: the workgroups that are resident at once, or one per 256 records when there are fewer
-    int64_t grid = (int64_t)ctx->cus * MAE_WGS_PER_CU;
-    if (grid > ma_ends_chunks(n)) grid = ma_ends_chunks(n);
-    if (stage_launch(ctx, STG_MA_ENDS, k_ma_ends, dim3((unsigned)grid), dim3(MAE_THREADS), 0, ctx->stream, v, (unsigned long long*)ctx->d_ends_bins))
+    if (stage_launch(ctx, STG_MA_ENDS, k_ma_ends, ma_grid(ctx, ma_ends_chunks(n), MAE_WGS_PER_CU), dim3(MAE_THREADS), 0, ctx->stream, v, (unsigned long long*)ctx->d_ends_bins))
       return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipGetLastError());
   }
@@ -486,8 +519,7 @@ extern "C" int mia_hip_ma_cols(mia_hip_ctx* ctx, const uint8_t* segment, const u
     MaColsView v{ma_records(ctx), sel.segment, sel.use};
     // persistent grid over (tile, slice) jobs: the workgroups that are resident at once, or one per job when there are fewer
     const int64_t wgs = (int64_t)ctx->cus * MAC_WGS_PER_CU, slices = ma_cols_slices(n, L, wgs), per_slice = (n + slices - 1) / slices;
-    const int64_t jobs = ma_cols_tiles(L) * slices, grid = jobs < wgs ? jobs : wgs;
-    if (stage_launch(ctx, STG_MA_COLS, k_ma_cols, dim3((unsigned)grid), dim3(MAC_THREADS), 0, ctx->stream, v, slices, per_slice, (uint32_t*)ctx->d_cols_tab,
+    if (stage_launch(ctx, STG_MA_COLS, k_ma_cols, ma_grid(ctx, ma_cols_tiles(L) * slices, MAC_WGS_PER_CU), dim3(MAC_THREADS), 0, ctx->stream, v, slices, per_slice, (uint32_t*)ctx->d_cols_tab,
                      (unsigned long long*)ctx->d_cols_out))
       return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipGetLastError());
@@ -529,11 +561,10 @@ extern "C" int mia_hip_ma_dedup(mia_hip_ctx* ctx, int32_t ref_len, int64_t n_rec
   int64_t M = 0, orphans = 0;
   for (int64_t r = 0; r < n; r++) {
     if (start[r] < 0 || (int64_t)end[r] < (int64_t)start[r] - 1 || (int64_t)end[r] >= 2ll * L) { ctx->err = "ma_dedup: a record's START or END is out of range"; return MIA_HIP_ERR_ARG; }
-    const int64_t m = mate ? mate[r] : MA_DEDUP_NONE;
-    if (m == MA_DEDUP_ORPHAN) { orphans++; continue; }
-    if (m == MA_DEDUP_NONE) { M++; continue; }
-    if (m < 0 || m >= n || m == r || mate[m] != r) { ctx->err = "ma_dedup: mate is out of range, the record itself or not mutual"; return MIA_HIP_ERR_ARG; }
-    if (ma_dedup_front(start, r, m)) { M++; continue; }
+    if (!ma_mate_record_ok(mate, n, r)) { ctx->err = "ma_dedup: mate is out of range, the record itself or not mutual"; return MIA_HIP_ERR_ARG; }
+    const int64_t m = mate ? mate[r] : MA_MOL_NONE;
+    if (m == MA_MOL_ORPHAN) { orphans++; continue; }
+    if (m == MA_MOL_NONE || ma_dedup_front(start, r, m)) { M++; continue; }
     if (end[r] >= L) { ctx->err = "ma_dedup: the back half of a pair ends behind the reference"; return MIA_HIP_ERR_ARG; }
   }
   dd.n = n; dd.molecules = M; dd.orphans = orphans; dd.clusters = 0;
@@ -559,8 +590,7 @@ extern "C" int mia_hip_ma_dedup(mia_hip_ctx* ctx, int32_t ref_len, int64_t n_rec
     if (mate) HIPCHK(hipMemcpyAsync(dd.d_mate, mate, (size_t)n * 8, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(dd.d_hist, 0, (size_t)MA_DEDUP_HIST * 8, s));
     const int64_t* d_mate = mate ? (const int64_t*)dd.d_mate : nullptr;
-    const int64_t wide = (int64_t)ctx->cus * MAD_WGS_PER_CU;
-    auto grid_for = [&](int64_t items) { const int64_t g = ma_dedup_wgs(items); return dim3((unsigned)(g < 1 ? 1 : (g < wide ? g : wide))); };
+    auto grid_for = [&](int64_t items) { return ma_grid(ctx, ma_dedup_wgs(items), MAD_WGS_PER_CU); };
     if (stage_launch(ctx, STG_MA_DEDUP_KEYS, k_ma_dedup_keys, grid_for(n), dim3(MAD_THREADS), 0, s, n, L, W, (const int32_t*)dd.d_start, (const int32_t*)dd.d_end,
                      (const uint8_t*)dd.d_rc, d_mate, (unsigned long long*)dd.d_key[0], (uint32_t*)dd.d_val[0], (uint8_t*)dd.d_keep, (int64_t*)dd.d_rep))
       return MIA_HIP_ERR_NOMEM;
@@ -633,8 +663,8 @@ extern "C" int mia_hip_get_ma_dedup(mia_hip_ctx* ctx, uint8_t* keep, int64_t* re
   if (!dd.done) { ctx->err = "ma_dedup first"; return MIA_HIP_ERR_STATE; }
   if (dd.n > 0 && (keep || rep)) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (keep) HIPCHK(hipMemcpyAsync(keep, dd.d_keep, (size_t)dd.n, hipMemcpyDeviceToHost, ctx->stream));
-    if (rep) HIPCHK(hipMemcpyAsync(rep, dd.d_rep, (size_t)dd.n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ma_down(ctx, keep, dd.d_keep, (size_t)dd.n));
+    HIPCHK(ma_down(ctx, rep, dd.d_rep, (size_t)dd.n * 8));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   if (size_hist) memcpy(size_hist, dd.hist, sizeof dd.hist);
@@ -697,8 +727,7 @@ extern "C" int mia_hip_ma_collapse(mia_hip_ctx* ctx, const int64_t* rec_of, cons
     const MaRecords v = ma_records(ctx);
     const MaColDedup d{M, C, dd.d_val[dd.sorted_side], dd.d_runid, dd.d_first, dd.d_cluster, dd.d_anchor, dd.d_best, dd.has_mate ? (const int64_t*)dd.d_mate : nullptr,
                        dd.d_start, rec_of ? (const int32_t*)cc.d_rec_of : nullptr, vote ? (const uint8_t*)cc.d_vote : nullptr};
-    const int64_t wide = (int64_t)ctx->cus * MAJ_WGS_PER_CU;
-    auto grid_for = [&](int64_t wgs) { return dim3((unsigned)(wgs < 1 ? 1 : (wgs < wide ? wgs : wide))); };
+    auto grid_for = [&](int64_t wgs) { return ma_grid(ctx, wgs, MAJ_WGS_PER_CU); };
     if (stage_launch(ctx, STG_MA_COLLAPSE_PLAN, k_ma_collapse_copy, grid_for(ma_collapse_wgs(words)), dim3(MAJ_THREADS), 0, s, v.seq, (char*)cc.d_seq, words) ||
         stage_launch(ctx, STG_MA_COLLAPSE_PLAN, k_ma_collapse_plan, dim3((unsigned)n_wgs), dim3(MAJ_THREADS), 0, s, v, d, (unsigned long long*)cc.d_ctl, n_wgs,
                      (int32_t*)cc.d_rep_f, (int32_t*)cc.d_rep_b, (int64_t*)cc.d_cnt_off, (int32_t*)cc.d_members, (unsigned long long*)cc.d_hist))
@@ -742,12 +771,9 @@ extern "C" int mia_hip_get_ma_collapse(mia_hip_ctx* ctx, char* seq, int64_t cap_
   if (!ctx->ma_resident || !ctx->dedup.done || !cc.done) { ctx->err = "ma_collapse first"; return MIA_HIP_ERR_STATE; }
   if (seq && cap_bytes < cc.cols) { ctx->err = "get_ma_collapse: buffer too small"; return MIA_HIP_ERR_ARG; }
   HIPCHK(hipSetDevice(ctx->device));
-  if (seq && cc.cols > 0)
-    HIPCHK(hipMemcpyAsync(seq, cc.launched ? (const char*)cc.d_seq : (const char*)ctx->d_ma_seq, (size_t)cc.cols, hipMemcpyDeviceToHost, ctx->stream));
-  if (members && cc.n > 0) {
-    if (cc.launched) HIPCHK(hipMemcpyAsync(members, cc.d_members, (size_t)cc.n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    else memset(members, 0, (size_t)cc.n * 4);
-  }
+  HIPCHK(ma_down(ctx, seq, cc.launched ? (const char*)cc.d_seq : (const char*)ctx->d_ma_seq, (size_t)cc.cols));
+  if (cc.launched) HIPCHK(ma_down(ctx, members, cc.d_members, (size_t)cc.n * 4));
+  else if (members && cc.n > 0) memset(members, 0, (size_t)cc.n * 4);
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (hist) memcpy(hist, cc.hist, sizeof cc.hist);
   return MIA_HIP_OK;
@@ -759,43 +785,29 @@ extern "C" int mia_hip_ma_damage(mia_hip_ctx* ctx, const char* ref_seq, const ui
                                  int32_t ends_mode, int64_t* n_molecules, int64_t* n_kept) {
   if (!ctx) return MIA_HIP_ERR_ARG;
   ctx->ma_out.damage_done = false;
-  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_damage"; return MIA_HIP_ERR_STATE; }
-  if (!ref_seq) { ctx->err = "ma_damage: no reference sequence"; return MIA_HIP_ERR_ARG; }
-  if (!ma_dmg_pos_ok(n_pos)) { ctx->err = "ma_damage: the number of positions must lie in 1 .. 15"; return MIA_HIP_ERR_ARG; }
-  if (!ma_dmg_mode_ok(ends_mode)) { ctx->err = "ma_damage: the ends mode must be 0 (any), 1 (5'), 2 (3') or 3 (both)"; return MIA_HIP_ERR_ARG; }
-  if (ctx->ma_n > 0 && ctx->ma_cols < 0) { ctx->err = "ma_damage: col_off[0] of the tallied records is not 0"; return MIA_HIP_ERR_ARG; }
-  const int64_t n = ctx->ma_n, T = ctx->ma_cols;
-  const int32_t L = ctx->ma_L;
-  if (!ma_dmg_mate_ok(mate, n)) { ctx->err = "ma_damage: mate is out of range, the record itself or not mutual"; return MIA_HIP_ERR_ARG; }
   auto& dg = ctx->damage;
+  const char* const own_error = !ma_dmg_pos_ok(n_pos)      ? "the number of positions must lie in 1 .. 15"
+                                : !ma_dmg_mode_ok(ends_mode) ? "the ends mode must be 0 (any), 1 (5'), 2 (3') or 3 (both)"
+                                                             : nullptr;
+  MaMolFrame f;
+  if (const int rc = ma_mol_frame(ctx, "ma_damage", ref_seq, use, mate, own_error, dg.d_mate, ma_dmg_chunks(ctx->ma_cols), ma_dmg_record_wgs(ctx->ma_n),
+                                  MAG_WGS_PER_CU, &f))
+    return rc;
+  const int64_t n = ctx->ma_n;
   memset(dg.bins, 0, sizeof dg.bins);
   if (n > 0) {                                               // without records there is no launch and every result is zero
-    HIPCHK(hipSetDevice(ctx->device));
-    MaSelection sel;
-    if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, dg.d_hit, 2 * n) || dev_ensure(ctx, dg.d_pos, 2 * n) || dev_ensure(ctx, dg.d_keep, n) ||
-        dev_ensure(ctx, dg.d_bins, MA_DMG_BINS) || (mate && dev_ensure(ctx, dg.d_mate, n)))
+    if (dev_ensure(ctx, dg.d_hit, 2 * n) || dev_ensure(ctx, dg.d_pos, 2 * n) || dev_ensure(ctx, dg.d_keep, n) || dev_ensure(ctx, dg.d_bins, MA_DMG_BINS))
       return MIA_HIP_ERR_NOMEM;
-    if (const int rc = ma_selection(ctx, nullptr, use, &sel)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
-    if (mate) HIPCHK(hipMemcpyAsync(dg.d_mate, mate, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemsetAsync(dg.d_hit, 0, (size_t)n * 2 * 4, ctx->stream));
     HIPCHK(hipMemsetAsync(dg.d_keep, 0, (size_t)n, ctx->stream));
     HIPCHK(hipMemsetAsync(dg.d_bins, 0, (size_t)MA_DMG_BINS * 8, ctx->stream));
-    const MaRecords mr = ma_records(ctx);
-    const int64_t wide = (int64_t)ctx->cus * MAG_WGS_PER_CU;
-    // persistent grids: the workgroups that are resident at once, or one per chunk (per 256 records) when there are fewer
-    int64_t grid = ma_dmg_chunks(T) < wide ? ma_dmg_chunks(T) : wide;
-    if (grid < 1) grid = 1;                                  // (records that all lack columns: one workgroup that finds no chunk)
-    MaProfView v{mr, T, ctx->d_prof_ref, sel.use};
-    if (stage_launch(ctx, STG_MA_DAMAGE_HITS, k_ma_damage_hits, dim3((unsigned)grid), dim3(MAG_THREADS), 0, ctx->stream, v, single_stranded ? 1 : 0,
-                     (uint32_t*)dg.d_hit, (uint32_t*)dg.d_hit + n))
+    if (stage_launch(ctx, STG_MA_DAMAGE_HITS, k_ma_damage_hits, f.col_grid, dim3(MAG_THREADS), 0, ctx->stream, f.v, single_stranded ? 1 : 0, (uint32_t*)dg.d_hit,
+                     (uint32_t*)dg.d_hit + n))
       return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipGetLastError());
-    MaDmgMolView mv{n, mr.revcom, sel.use, mate ? (const int64_t*)dg.d_mate : nullptr, (const uint32_t*)dg.d_hit, (const uint32_t*)dg.d_hit + n, n_pos, ends_mode,
+    MaDmgMolView mv{n, f.v.revcom, f.v.use, f.mate, (const uint32_t*)dg.d_hit, (const uint32_t*)dg.d_hit + n, n_pos, ends_mode,
                     (uint8_t*)dg.d_pos, (uint8_t*)dg.d_pos + n, (uint8_t*)dg.d_keep};
-    grid = ma_dmg_record_wgs(n) < wide ? ma_dmg_record_wgs(n) : wide;
-    if (stage_launch(ctx, STG_MA_DAMAGE_MOLECULES, k_ma_damage_molecules, dim3((unsigned)grid), dim3(MAG_THREADS), 0, ctx->stream, mv,
-                     (unsigned long long*)dg.d_bins))
+    if (stage_launch(ctx, STG_MA_DAMAGE_MOLECULES, k_ma_damage_molecules, f.rec_grid, dim3(MAG_THREADS), 0, ctx->stream, mv, (unsigned long long*)dg.d_bins))
       return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(dg.bins, dg.d_bins, (size_t)MA_DMG_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -816,9 +828,9 @@ extern "C" int mia_hip_get_ma_damage(mia_hip_ctx* ctx, uint8_t* pos5, uint8_t* p
   auto& dg = ctx->damage;
   if (n > 0 && (pos5 || pos3 || keep)) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (pos5) HIPCHK(hipMemcpyAsync(pos5, dg.d_pos, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (pos3) HIPCHK(hipMemcpyAsync(pos3, dg.d_pos + n, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    if (keep) HIPCHK(hipMemcpyAsync(keep, dg.d_keep, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ma_down(ctx, pos5, dg.d_pos, (size_t)n));
+    HIPCHK(ma_down(ctx, pos3, dg.d_pos + n, (size_t)n));
+    HIPCHK(ma_down(ctx, keep, dg.d_keep, (size_t)n));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   if (hist) memcpy(hist, dg.bins, sizeof(int64_t) * MA_DMG_HIST);
@@ -856,12 +868,8 @@ extern "C" int mia_hip_ma_mask(mia_hip_ctx* ctx, int32_t n5, int32_t n3, int32_t
     HIPCHK(hipMemsetAsync(hi, 0, (size_t)n * 4, ctx->stream));
     HIPCHK(hipMemsetAsync(mk.d_bins, 0, (size_t)MA_MASK_BINS * 8, ctx->stream));
     HIPCHK(hipMemsetAsync(mk.d_ctl, 0, ((size_t)MAR_STATE + (size_t)n_wgs) * 8, ctx->stream));
-    const MaProfView v{ma_records(ctx), T, nullptr, nullptr};
-    const int64_t wide = (int64_t)ctx->cus * MAM_WGS_PER_CU;
-    // persistent grids: the workgroups that are resident at once, or one per chunk when there are fewer
-    int64_t grid = ma_mask_chunks(T) < wide ? ma_mask_chunks(T) : wide;
-    if (grid < 1) grid = 1;                                  // (records that all lack columns: one workgroup that finds no chunk)
-    if (stage_launch(ctx, STG_MA_MASK_BOUNDS, k_ma_mask_bounds, dim3((unsigned)grid), dim3(MAM_THREADS), 0, ctx->stream, v, n5, n3, mode, single_stranded ? 1 : 0,
+    const MaFlatView v{ma_records(ctx), T, nullptr, nullptr};
+    if (stage_launch(ctx, STG_MA_MASK_BOUNDS, k_ma_mask_bounds, ma_grid(ctx, ma_mask_chunks(T), MAM_WGS_PER_CU), dim3(MAM_THREADS), 0, ctx->stream, v, n5, n3, mode, single_stranded ? 1 : 0,
                      lo, hi, (unsigned long long*)mk.d_bins))
       return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipGetLastError());
@@ -877,10 +885,7 @@ extern "C" int mia_hip_ma_mask(mia_hip_ctx* ctx, int32_t n5, int32_t n3, int32_t
     if (new_T < 0 || new_T > T) { ctx->err = "ma_mask: the layout came back inconsistent"; return MIA_HIP_ERR_DEVICE; }
     const MaMaskApplyView av{v, n5, n3, mode, single_stranded ? 1 : 0, first, (const int64_t*)mk.d_off, new_T};
     const int64_t pieces = ma_mask_chunks(ma_mask_padded(new_T)), pair_wgs = (n_ins + MAM_THREADS - 1) / MAM_THREADS;
-    grid = pieces > pair_wgs ? pieces : pair_wgs;
-    if (grid > wide) grid = wide;
-    if (grid < 1) grid = 1;
-    if (stage_launch(ctx, STG_MA_MASK_APPLY, k_ma_mask_apply, dim3((unsigned)grid), dim3(MAM_THREADS), 0, ctx->stream, av, (const int32_t*)count, n_ins,
+    if (stage_launch(ctx, STG_MA_MASK_APPLY, k_ma_mask_apply, ma_grid(ctx, std::max(pieces, pair_wgs), MAM_WGS_PER_CU), dim3(MAM_THREADS), 0, ctx->stream, av, (const int32_t*)count, n_ins,
                      (char*)mk.d_seq, (char*)mk.d_smp, (uint8_t*)mk.d_pair_keep, (int32_t*)mk.d_ipos, (unsigned long long*)mk.d_bins))
       return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipGetLastError());
@@ -907,15 +912,14 @@ extern "C" int mia_hip_get_ma_mask(mia_hip_ctx* ctx, int32_t* first, int32_t* co
   const int64_t n = ctx->ma_n, n_ins = ctx->ma_n_ins;
   if (n > 0) {
     HIPCHK(hipSetDevice(ctx->device));
-    auto down = [&](void* h, const void* d, size_t b) { return h && b ? hipMemcpyAsync(h, d, b, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; };
-    HIPCHK(down(first, mk.d_rec, (size_t)n * 4));
-    HIPCHK(down(count, (int32_t*)mk.d_rec + n, (size_t)n * 4));
-    HIPCHK(down(start, (int32_t*)mk.d_rec + 2 * n, (size_t)n * 4));
-    HIPCHK(down(col_off, mk.d_off, (size_t)(n + 1) * 8));
-    HIPCHK(down(seq, mk.d_seq, (size_t)mk.cols_kept));
-    HIPCHK(down(smp, mk.d_smp, (size_t)mk.cols_kept));
-    HIPCHK(down(pair_keep, mk.d_pair_keep, (size_t)n_ins));
-    HIPCHK(down(ins_pos, mk.d_ipos, (size_t)n_ins * 4));
+    HIPCHK(ma_down(ctx, first, mk.d_rec, (size_t)n * 4));
+    HIPCHK(ma_down(ctx, count, (int32_t*)mk.d_rec + n, (size_t)n * 4));
+    HIPCHK(ma_down(ctx, start, (int32_t*)mk.d_rec + 2 * n, (size_t)n * 4));
+    HIPCHK(ma_down(ctx, col_off, mk.d_off, (size_t)(n + 1) * 8));
+    HIPCHK(ma_down(ctx, seq, mk.d_seq, (size_t)mk.cols_kept));
+    HIPCHK(ma_down(ctx, smp, mk.d_smp, (size_t)mk.cols_kept));
+    HIPCHK(ma_down(ctx, pair_keep, mk.d_pair_keep, (size_t)n_ins));
+    HIPCHK(ma_down(ctx, ins_pos, mk.d_ipos, (size_t)n_ins * 4));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   } else if (col_off) {
     col_off[0] = 0;
@@ -940,45 +944,29 @@ extern "C" int mia_hip_ma_score(mia_hip_ctx* ctx, const char* ref_seq, const uin
                                 int64_t* n_molecules, int64_t* n_kept) {
   if (!ctx) return MIA_HIP_ERR_ARG;
   ctx->ma_out.score_done = false;
-  if (!ctx->ma_resident) { ctx->err = "ma_tally must precede ma_score"; return MIA_HIP_ERR_STATE; }
-  if (!ref_seq) { ctx->err = "ma_score: no reference sequence"; return MIA_HIP_ERR_ARG; }
-  if (!w) { ctx->err = "ma_score: no weight table"; return MIA_HIP_ERR_ARG; }
-  if (!ma_pmd_weights_ok(w)) { ctx->err = "ma_score: a weight lies outside -2^20 .. 2^20"; return MIA_HIP_ERR_ARG; }
-  if (ctx->ma_n > 0 && ctx->ma_cols < 0) { ctx->err = "ma_score: col_off[0] of the tallied records is not 0"; return MIA_HIP_ERR_ARG; }
-  const int64_t n = ctx->ma_n, T = ctx->ma_cols;
-  const int32_t L = ctx->ma_L;
-  if (!ma_dmg_mate_ok(mate, n)) { ctx->err = "ma_score: mate is out of range, the record itself or not mutual"; return MIA_HIP_ERR_ARG; }
   auto& sc = ctx->score;
+  const char* const own_error = !w ? "no weight table" : !ma_pmd_weights_ok(w) ? "a weight lies outside -2^20 .. 2^20" : nullptr;
+  MaMolFrame f;
+  if (const int rc = ma_mol_frame(ctx, "ma_score", ref_seq, use, mate, own_error, sc.d_mate, ma_pmd_chunks(ctx->ma_cols), ma_pmd_record_wgs(ctx->ma_n),
+                                  MAQ_WGS_PER_CU, &f))
+    return rc;
+  const int64_t n = ctx->ma_n;
   memset(sc.bins, 0, sizeof sc.bins);
   if (n > 0) {                                               // without records there is no launch and every result is zero
-    HIPCHK(hipSetDevice(ctx->device));
-    MaSelection sel;
-    if (dev_ensure(ctx, ctx->d_prof_ref, (int64_t)L) || dev_ensure(ctx, sc.d_w, MA_PMD_WEIGHTS) || dev_ensure(ctx, sc.d_rec, n) || dev_ensure(ctx, sc.d_mol, n) ||
-        dev_ensure(ctx, sc.d_keep, n) || dev_ensure(ctx, sc.d_bins, MA_PMD_BINS) || (mate && dev_ensure(ctx, sc.d_mate, n)))
+    if (dev_ensure(ctx, sc.d_w, MA_PMD_WEIGHTS) || dev_ensure(ctx, sc.d_rec, n) || dev_ensure(ctx, sc.d_mol, n) || dev_ensure(ctx, sc.d_keep, n) ||
+        dev_ensure(ctx, sc.d_bins, MA_PMD_BINS))
       return MIA_HIP_ERR_NOMEM;
-    if (const int rc = ma_selection(ctx, nullptr, use, &sel)) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->d_prof_ref, ref_seq, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(sc.d_w, w, (size_t)MA_PMD_WEIGHTS * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (mate) HIPCHK(hipMemcpyAsync(sc.d_mate, mate, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemsetAsync(sc.d_rec, 0, (size_t)n * 8, ctx->stream));
     HIPCHK(hipMemsetAsync(sc.d_mol, 0, (size_t)n * 8, ctx->stream));
     HIPCHK(hipMemsetAsync(sc.d_keep, 0, (size_t)n, ctx->stream));
     HIPCHK(hipMemsetAsync(sc.d_bins, 0, (size_t)MA_PMD_BINS * 8, ctx->stream));
-    const MaRecords mr = ma_records(ctx);
-    const int64_t wide = (int64_t)ctx->cus * MAQ_WGS_PER_CU;
-    // persistent grids: the workgroups that are resident at once, or one per chunk (per 256 records) when there are fewer
-    int64_t grid = ma_pmd_chunks(T) < wide ? ma_pmd_chunks(T) : wide;
-    if (grid < 1) grid = 1;                                  // (records that all lack columns: one workgroup that finds no chunk)
-    MaProfView v{mr, T, ctx->d_prof_ref, sel.use};
-    if (stage_launch(ctx, STG_MA_SCORE_COLS, k_ma_score_cols, dim3((unsigned)grid), dim3(MAQ_THREADS), 0, ctx->stream, v, (const int32_t*)sc.d_w,
+    if (stage_launch(ctx, STG_MA_SCORE_COLS, k_ma_score_cols, f.col_grid, dim3(MAQ_THREADS), 0, ctx->stream, f.v, (const int32_t*)sc.d_w,
                      (unsigned long long*)sc.d_rec))
       return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipGetLastError());
-    MaPmdMolView mv{n, mr.revcom, sel.use, mate ? (const int64_t*)sc.d_mate : nullptr, (const int64_t*)sc.d_rec.p, threshold, (int64_t*)sc.d_mol,
-                    (uint8_t*)sc.d_keep};
-    grid = ma_pmd_record_wgs(n) < wide ? ma_pmd_record_wgs(n) : wide;
-    if (stage_launch(ctx, STG_MA_SCORE_MOLECULES, k_ma_score_molecules, dim3((unsigned)grid), dim3(MAQ_THREADS), 0, ctx->stream, mv,
-                     (unsigned long long*)sc.d_bins))
+    MaPmdMolView mv{n, f.v.revcom, f.v.use, f.mate, (const int64_t*)sc.d_rec.p, threshold, (int64_t*)sc.d_mol, (uint8_t*)sc.d_keep};
+    if (stage_launch(ctx, STG_MA_SCORE_MOLECULES, k_ma_score_molecules, f.rec_grid, dim3(MAQ_THREADS), 0, ctx->stream, mv, (unsigned long long*)sc.d_bins))
       return MIA_HIP_ERR_NOMEM;
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(sc.bins, sc.d_bins, (size_t)MA_PMD_BINS * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -999,9 +987,9 @@ extern "C" int mia_hip_get_ma_score(mia_hip_ctx* ctx, int64_t* rec_score, int64_
   auto& sc = ctx->score;
   if (n > 0 && (rec_score || mol_score || keep)) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (rec_score) HIPCHK(hipMemcpyAsync(rec_score, sc.d_rec, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (mol_score) HIPCHK(hipMemcpyAsync(mol_score, sc.d_mol, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (keep) HIPCHK(hipMemcpyAsync(keep, sc.d_keep, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ma_down(ctx, rec_score, sc.d_rec, (size_t)n * 8));
+    HIPCHK(ma_down(ctx, mol_score, sc.d_mol, (size_t)n * 8));
+    HIPCHK(ma_down(ctx, keep, sc.d_keep, (size_t)n));
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   if (hist) memcpy(hist, sc.bins, sizeof(int64_t) * MA_PMD_HIST);

@@ -20,7 +20,7 @@
 // k_ma_collapse_decide  a lane per column of the count array: its cluster by bisecting cnt_off (the last cluster that begins at or in
 //                       front of it), the five words, the decision, the byte, hist through LDS atomics.
 //
-// hist is flushed with one 64-bit vector atomic per non-empty bin and workgroup.  No workgroup waits for another except inside
+// hist goes through the wavefronts' own copies in LDS (ma_wave_bins.h).  No workgroup waits for another except inside
 // ma_scan_before.  No scratch; vector stores only; no inline assembly, no cooperative launch.  All counts are integer sums and every
 // byte of SEQ' is written by the one lane that decides its column: the result does not depend on the grid or on the records' order.
 #pragma once
@@ -29,6 +29,7 @@
 
 #include "ma_collapse_body.h"
 #include "ma_scan_dev.h"
+#include "ma_wave_bins.h"
 
 namespace mia {
 
@@ -45,20 +46,6 @@ __device__ __forceinline__ int64_t maj_from64(int64_t x, int lane) {
 }
 __device__ __forceinline__ uint32_t maj_count(bool flag) { return (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(flag)); }
 
-__device__ __forceinline__ void maj_bins_zero(uint32_t (*s_bins)[MA_COL_HIST]) {
-  for (int b = threadIdx.x; b < MAJ_WAVES * MA_COL_HIST; b += MAJ_THREADS) (&s_bins[0][0])[b] = 0;
-  __syncthreads();
-}
-__device__ __forceinline__ void maj_bins_flush(uint32_t (*s_bins)[MA_COL_HIST], unsigned long long* out) {
-  __syncthreads();
-  for (int b = threadIdx.x; b < MA_COL_HIST; b += MAJ_THREADS) {
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int w = 0; w < MAJ_WAVES; w++) sum += s_bins[w][b];
-    if (sum) atomicAdd(&out[b], sum);
-  }
-}
-
 // SEQ' = SEQ: words = the 16-byte words of the string, its last one padded (both buffers are allocated that far)
 __global__ __launch_bounds__(MAJ_THREADS) void k_ma_collapse_copy(const char* seq, char* out, int64_t words) {
   for (int64_t w = (int64_t)blockIdx.x * MAJ_THREADS + threadIdx.x; w < words; w += (int64_t)gridDim.x * MAJ_THREADS)
@@ -72,9 +59,9 @@ __global__ __launch_bounds__(MAJ_THREADS) void k_ma_collapse_plan(MaRecords v, M
   __shared__ long long s_len[MAJ_THREADS];
   __shared__ uint32_t s_bins[MAJ_WAVES][MA_COL_HIST];
   const int tid = threadIdx.x;
-  uint32_t* const mine = s_bins[tid >> 6];
+  uint32_t* const mine = ma_wave_bins_mine(s_bins);
   if (tid == 0) s_first = ma_scan_ticket(ctl);
-  maj_bins_zero(s_bins);
+  ma_wave_bins_zero(s_bins);
   const int64_t t = (int64_t)s_first;
   if (t >= n_wgs) return;
   const int64_t c = t * MAJ_THREADS + tid;
@@ -106,7 +93,7 @@ __global__ __launch_bounds__(MAJ_THREADS) void k_ma_collapse_plan(MaRecords v, M
   }
   __syncthreads();
   if (c < d.C) cnt_off[c] = (int64_t)s_first + s_len[tid];
-  maj_bins_flush(s_bins, hist);
+  ma_wave_bins_flush(s_bins, hist);
 }
 
 // cnt: five words per column of the straddling clusters, zero; out: SEQ' (a copy of SEQ)
@@ -116,7 +103,7 @@ __global__ __launch_bounds__(MAJ_THREADS) void k_ma_collapse_count(MaRecords v, 
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = (int)maj_lane();
   uint32_t* const mine = s_bins[wave];
-  maj_bins_zero(s_bins);
+  ma_wave_bins_zero(s_bins);
   const int64_t n_chunks = ma_col_chunks(d.M);
   for (int64_t g = (int64_t)blockIdx.x * MAJ_WAVES + wave; g < n_chunks; g += (int64_t)gridDim.x * MAJ_WAVES) {
     const int64_t g0 = g * MA_COL_K;
@@ -176,15 +163,15 @@ __global__ __launch_bounds__(MAJ_THREADS) void k_ma_collapse_count(MaRecords v, 
       j = jend;
     }
   }
-  maj_bins_flush(s_bins, hist);
+  ma_wave_bins_flush(s_bins, hist);
 }
 
 // Q = cnt_off[C]: the columns of the count array
 __global__ __launch_bounds__(MAJ_THREADS) void k_ma_collapse_decide(MaRecords v, MaColDedup d, const int32_t* rep_f, const int32_t* rep_b, const int64_t* cnt_off,
                                                                      const uint32_t* cnt, int64_t Q, char* out, unsigned long long* hist) {
   __shared__ uint32_t s_bins[MAJ_WAVES][MA_COL_HIST];
-  uint32_t* const mine = s_bins[threadIdx.x >> 6];
-  maj_bins_zero(s_bins);
+  uint32_t* const mine = ma_wave_bins_mine(s_bins);
+  ma_wave_bins_zero(s_bins);
   for (int64_t s = (int64_t)blockIdx.x * MAJ_THREADS + threadIdx.x; s < Q; s += (int64_t)gridDim.x * MAJ_THREADS) {
     int64_t lo = 0, hi = d.C;                                 // the last cluster with cnt_off[c] <= s: cnt_off[lo] <= s < cnt_off[hi]
     while (hi - lo > 1) {
@@ -210,7 +197,7 @@ __global__ __launch_bounds__(MAJ_THREADS) void k_ma_collapse_decide(MaRecords v,
     if (dec.split) atomicAdd(&mine[bin + MA_COL_SPLIT], 1u);
     if (dec.what) atomicAdd(&mine[bin + dec.what], 1u);
   }
-  maj_bins_flush(s_bins, hist);
+  ma_wave_bins_flush(s_bins, hist);
 }
 
 }  // namespace mia

@@ -20,8 +20,8 @@
 //                      orbit of run 0 are ever marked, and after round j all of them within 2^(j+1) steps are.
 // k_ma_dedup_clusters  the ordered scan again, over the marks: a run's cluster number and the anchor run of every cluster.  Runs of a
 //                      cluster are consecutive, so a cluster's size is the distance between the first entries of two anchor runs and no
-//                      sum is needed; the histogram goes through a copy per wavefront in LDS and is flushed with one 64-bit atomic per
-//                      non-empty bin and workgroup; keep and rep are scattered to the records of every molecule.
+//                      sum is needed; the histogram goes through a copy per wavefront in LDS (ma_wave_bins.h); keep and rep are
+//                      scattered to the records of every molecule.
 //
 // No workgroup waits for another except inside ma_scan_before.  No scratch; vector stores only.
 #pragma once
@@ -30,6 +30,7 @@
 
 #include "ma_dedup_body.h"
 #include "ma_scan_dev.h"
+#include "ma_wave_bins.h"
 
 namespace mia {
 
@@ -251,23 +252,16 @@ __global__ __launch_bounds__(MAD_THREADS) void k_ma_dedup_cluster_scan(const uin
 __global__ __launch_bounds__(MAD_THREADS) void k_ma_dedup_hist(const uint32_t* anchor, const unsigned long long* ctl, const uint32_t* run_first,
                                                                const unsigned long long* run_key, int W, unsigned long long* hist) {
   __shared__ uint32_t s_bins[MAD_WAVES][MA_DEDUP_HIST];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  uint32_t* const mine = s_bins[wave];
-  for (int b = tid; b < MAD_WAVES * MA_DEDUP_HIST; b += MAD_THREADS) (&s_bins[0][0])[b] = 0;
-  __syncthreads();
+  const int tid = threadIdx.x;
+  uint32_t* const mine = ma_wave_bins_mine(s_bins);
+  ma_wave_bins_zero(s_bins);
   const int64_t C = (int64_t)ctl[MAR_ROWS];
   for (int64_t c = (int64_t)blockIdx.x * MAD_THREADS + tid; c < C; c += (int64_t)gridDim.x * MAD_THREADS) {
     const uint32_t ka = anchor[c], kb = anchor[c + 1];
     const int64_t size = (int64_t)run_first[kb] - (int64_t)run_first[ka];
     atomicAdd(&mine[ma_dedup_size_bin(ma_dedup_key_forward(run_key[ka], W), size)], 1u);
   }
-  __syncthreads();
-  for (int b = tid; b < MA_DEDUP_HIST; b += MAD_THREADS) {
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int w = 0; w < MAD_WAVES; w++) sum += s_bins[w][b];
-    if (sum) atomicAdd(&hist[b], sum);
-  }
+  ma_wave_bins_flush(s_bins, hist);
 }
 
 // keep and rep of the records of every molecule

@@ -6,17 +6,16 @@
 // their characters in the same 16-byte words.
 //
 // HISTOGRAM.  1 267 bins (ctx[2][20][6] | len[2][513] | halves), few and unevenly hit: a pile of duplicate reads puts every event
-// of a wavefront into the same 41.  Every event is one LDS atomic on the wavefront's own copy of the bins (4 copies of 1 267 words,
-// 19.8 KiB per workgroup): wavefronts never contend with each other, and no event reaches global memory before the flush.
+// of a wavefront into the same 41.  Every event is one LDS atomic on the wavefront's own copy of the bins (ma_wave_bins.h: 4 copies
+// of 1 267 words, 19.8 KiB per workgroup).
 // WIDTH.  The LDS words are 32-bit.  A record adds at most one event to a bin and mia_hip_ma_tally takes fewer than 2^31 records,
 // so no word overflows however long the grid strides.
-// FLUSH.  The four copies are summed per bin and added to the int64 result with one 64-bit vector atomic per bin that is not
-// zero per workgroup -- integer adds: the result does not depend on the grid or on the order of the records.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ma_ends_body.h"
+#include "ma_wave_bins.h"
 
 namespace mia {
 
@@ -27,19 +26,7 @@ MIA_HD inline int64_t ma_ends_chunks(int64_t n) { return (n + MAE_THREADS - 1) /
 
 __global__ __launch_bounds__(MAE_THREADS) void k_ma_ends(MaEndsView v, unsigned long long* out) {
   __shared__ uint32_t s_bins[MAE_WAVES][MA_ENDS_BINS];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  uint32_t* const mine = s_bins[wave];
-  for (int b = tid; b < MAE_WAVES * MA_ENDS_BINS; b += MAE_THREADS) (&s_bins[0][0])[b] = 0;
-  __syncthreads();
-  for (int64_t r = (int64_t)blockIdx.x * MAE_THREADS + tid; r < v.n; r += (int64_t)gridDim.x * MAE_THREADS)
-    ma_ends_record(v, r, [&](int bin) { atomicAdd(&mine[bin], 1u); });
-  __syncthreads();
-  for (int b = tid; b < MA_ENDS_BINS; b += MAE_THREADS) {
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int w = 0; w < MAE_WAVES; w++) sum += s_bins[w][b];
-    if (sum) atomicAdd(&out[b], sum);
-  }
+  ma_wave_bins_records(s_bins, v.n, out, [&](int64_t r, auto&& count) { ma_ends_record(v, r, count); });
 }
 
 }  // namespace mia

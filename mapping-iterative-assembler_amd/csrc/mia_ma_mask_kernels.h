@@ -1,15 +1,13 @@
 // mia_ma_mask_kernels.h -- the end mask (ma_hip -E, -x, -f 96) over the records mia_hip_ma_tally left on the device.  Three launches
 // (ma_mask_body.h holds what a lane does in each):
 //
-// k_ma_mask_bounds runs over the FLAT columns exactly as k_ma_profile does: a lane takes MA_MASK_LANE = 16 positions at a time -- one
-// 16-byte load of SEQ and one of SMP --, finds the record of the first by bisecting col_off and walks on from there; a workgroup takes
-// 4 096 positions, the grid strides over those chunks.  A lane keeps the first and the last column outside the zones of the record
+// k_ma_mask_bounds runs over the FLAT columns (the shared walk: ma_flat_body.h): a lane takes a stretch of MA_MASK_LANE = 16 positions
+// at a time, a workgroup 4 096, the grid strides over those chunks.  A lane keeps the first and the last column outside the zones of the record
 // it is in in two registers and sends them when the record changes and at the end of its stretch: one 32-bit vector atomic minimum on
 // lo[r] and one maximum on hi[r] per (lane, record), none where the lane met no such column, and plain stores where the record lies
 // wholly inside the lane's stretch (no other lane sees it).  lo is preset to all ones and hi to 0, so the order of arrival does not
 // matter.  Every zone column (substitution mode: every substituted column) is one LDS atomic on the wavefront's own copy of
-// hist[2][2][16]; the one flush sums the four copies and adds what is not zero with 64-bit vector atomics.  A workgroup meets fewer
-// than 2^32 columns, so the 32-bit LDS words hold.
+// hist[2][2][16] (ma_wave_bins.h).  A workgroup meets fewer than 2^32 columns, so the 32-bit LDS words hold.
 //
 // k_ma_mask_layout runs a RECORD PER LANE: ma_mask_record walks a over the '-' columns behind a1 and b over those in front of b1
 // (bounded by the record's own '-' runs at its two seams), writes first, count and start', and the workgroup's kept columns go through
@@ -32,6 +30,7 @@
 
 #include "ma_mask_body.h"
 #include "ma_scan_dev.h"
+#include "ma_wave_bins.h"
 
 namespace mia {
 
@@ -44,28 +43,11 @@ MIA_HD inline int64_t ma_mask_chunks(int64_t T) { return (T + MAM_WG_COLS - 1) /
 MIA_HD inline int64_t ma_mask_layout_wgs(int64_t n) { return (n + MAM_PER_WG - 1) / MAM_PER_WG; }
 MIA_HD inline int64_t ma_mask_padded(int64_t T) { return (T + MA_MASK_LANE - 1) / MA_MASK_LANE * MA_MASK_LANE; }
 
-// the wavefronts' copies of bins first .. first + COUNT - 1: zero, (count), then flush what is not zero
-template <int COUNT>
-__device__ __forceinline__ void mam_bins_zero(uint32_t (*s_bins)[COUNT]) {
-  for (int b = threadIdx.x; b < MAM_WAVES * COUNT; b += MAM_THREADS) (&s_bins[0][0])[b] = 0;
-  __syncthreads();
-}
-template <int COUNT>
-__device__ __forceinline__ void mam_bins_flush(uint32_t (*s_bins)[COUNT], unsigned long long* out) {
-  __syncthreads();
-  for (int b = threadIdx.x; b < COUNT; b += MAM_THREADS) {
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int w = 0; w < MAM_WAVES; w++) sum += s_bins[w][b];
-    if (sum) atomicAdd(&out[b], sum);
-  }
-}
-
-__global__ __launch_bounds__(MAM_THREADS) void k_ma_mask_bounds(MaProfView v, int32_t n5, int32_t n3, int32_t mode, int32_t single_stranded, uint32_t* lo,
+__global__ __launch_bounds__(MAM_THREADS) void k_ma_mask_bounds(MaFlatView v, int32_t n5, int32_t n3, int32_t mode, int32_t single_stranded, uint32_t* lo,
                                                                  uint32_t* hi, unsigned long long* bins) {
   __shared__ uint32_t s_bins[MAM_WAVES][MA_MASK_HIST];
-  uint32_t* const mine = s_bins[threadIdx.x >> 6];
-  mam_bins_zero(s_bins);
+  uint32_t* const mine = ma_wave_bins_mine(s_bins);
+  ma_wave_bins_zero(s_bins);
   const int64_t n_chunks = ma_mask_chunks(v.T);
   for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x)
     ma_mask_stretch(
@@ -76,7 +58,7 @@ __global__ __launch_bounds__(MAM_THREADS) void k_ma_mask_bounds(MaProfView v, in
           if (b1) atomicMax(&hi[r], b1);
         },
         [&](int bin) { atomicAdd(&mine[bin], 1u); });
-  mam_bins_flush(s_bins, bins);
+  ma_wave_bins_flush(s_bins, bins);
 }
 
 // Workgroups take their place by ticket (ma_scan_dev.h; ctl[MAR_ROWS] = the kept columns of the whole file).  Workgroup t decides
@@ -88,9 +70,9 @@ __global__ __launch_bounds__(MAM_THREADS) void k_ma_mask_layout(MaMaskRecView m,
   __shared__ long long s_len[MAM_PER_WG];
   __shared__ uint32_t s_bins[MAM_WAVES][SCALARS];
   const int tid = threadIdx.x;
-  uint32_t* const mine = s_bins[tid >> 6];
+  uint32_t* const mine = ma_wave_bins_mine(s_bins);
   if (tid == 0) s_first = ma_scan_ticket(ctl);
-  mam_bins_zero(s_bins);
+  ma_wave_bins_zero(s_bins);
   const int64_t t = (int64_t)s_first;
   if (t >= n_wgs) return;
   const int64_t r = t * MAM_PER_WG + tid;
@@ -105,15 +87,15 @@ __global__ __launch_bounds__(MAM_THREADS) void k_ma_mask_layout(MaMaskRecView m,
   }
   __syncthreads();
   if (r < m.v.n) new_off[r] = (int64_t)s_first + s_len[tid];
-  mam_bins_flush(s_bins, bins + MA_MASK_EMPTIED);
+  ma_wave_bins_flush(s_bins, bins + MA_MASK_EMPTIED);
 }
 
 // chunks = ma_mask_chunks(padded new_T) workgroup-sized pieces of the new strings, then the pairs in pieces of MAM_THREADS
 __global__ __launch_bounds__(MAM_THREADS) void k_ma_mask_apply(MaMaskApplyView m, const int32_t* count, int64_t n_ins, char* seq_out, char* smp_out,
                                                                 uint8_t* pair_keep, int32_t* new_ins_pos, unsigned long long* bins) {
   __shared__ uint32_t s_bins[MAM_WAVES][MA_MASK_HIST];
-  uint32_t* const mine = s_bins[threadIdx.x >> 6];
-  mam_bins_zero(s_bins);
+  uint32_t* const mine = ma_wave_bins_mine(s_bins);
+  ma_wave_bins_zero(s_bins);
   const int64_t padded = ma_mask_padded(m.new_T), n_chunks = ma_mask_chunks(padded);
   for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const int64_t base = c * MAM_WG_COLS + (int64_t)threadIdx.x * MA_MASK_LANE;
@@ -123,7 +105,7 @@ __global__ __launch_bounds__(MAM_THREADS) void k_ma_mask_apply(MaMaskApplyView m
     *reinterpret_cast<uint4*>(seq_out + base) = make_uint4(so.w[0], so.w[1], so.w[2], so.w[3]);
     *reinterpret_cast<uint4*>(smp_out + base) = make_uint4(mo.w[0], mo.w[1], mo.w[2], mo.w[3]);
   }
-  mam_bins_flush(s_bins, bins + MA_MASK_STAY);
+  ma_wave_bins_flush(s_bins, bins + MA_MASK_STAY);
   uint32_t dropped = 0;
   for (int64_t k = (int64_t)blockIdx.x * MAM_THREADS + threadIdx.x; k < n_ins; k += (int64_t)gridDim.x * MAM_THREADS) {
     int64_t lo = 0, hi = m.v.n;            // the record of the k-th listed pair: rec_ins[lo] <= k < rec_ins[hi]

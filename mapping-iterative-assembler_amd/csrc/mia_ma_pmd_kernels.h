@@ -1,9 +1,8 @@
 // mia_ma_pmd_kernels.h -- the damage score (ma_hip -L, -K, -S, -f 97) over the records mia_hip_ma_tally left on the device.  Two
 // launches (ma_pmd_body.h holds what a lane does in either):
 //
-// k_ma_score_cols runs over the FLAT columns exactly as k_ma_damage_hits does: a lane takes MA_PMD_LANE = 16 positions at a time -- one
-// 16-byte load of SEQ and one of SMP --, finds the record of the first by bisecting col_off and walks on from there; a workgroup takes
-// 4 096 positions, the grid strides over those chunks.  The 775 words of the weight table are staged in LDS once per workgroup, in
+// k_ma_score_cols runs over the FLAT columns (the shared walk: ma_flat_body.h): a lane takes a stretch of MA_PMD_LANE = 16 positions at
+// a time, a workgroup 4 096, the grid strides over those chunks.  The 775 words of the weight table are staged in LDS once per workgroup, in
 // front of the chunks, so a column costs one LDS read on top of what the profile does with it.  A lane sums the weights of the record
 // it is in in one register (|w| <= 2^20: sixteen of them stay inside int32) and sends the sum when the record changes and at the end
 // of its stretch: at most one 64-bit vector atomic add per (lane, record) whose sum is NOT zero, into score[r], which only needs to be
@@ -13,15 +12,15 @@
 //
 // k_ma_score_molecules runs a RECORD PER LANE: the lower-numbered record of a molecule adds the halves, decides keep against the
 // threshold, stores S and keep to both records (plain vector stores: no other lane writes them) and adds the molecule to
-// hist[strand][bin] -- with the orphan and kept-record counts 130 bins, one LDS atomic on the wavefront's own copy (4 copies, 2 KiB
-// per workgroup).  A record adds at most three events and mia_hip_ma_tally takes fewer than 2^31 records: a 32-bit LDS word does not
-// overflow before the one flush, which sums the four copies per bin and adds what is not zero to the int64 result with one 64-bit
-// vector atomic.
+// hist[strand][bin] -- with the orphan and kept-record counts 130 bins, one LDS atomic on the wavefront's own copy (ma_wave_bins.h: 4
+// copies, 2 KiB per workgroup).  A record adds at most three events and mia_hip_ma_tally takes fewer than 2^31 records: a 32-bit LDS
+// word does not overflow before the one flush.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ma_pmd_body.h"
+#include "ma_wave_bins.h"
 
 namespace mia {
 
@@ -32,7 +31,7 @@ constexpr int MAQ_WGS_PER_CU = 4;          // persistent grids: at most this man
 MIA_HD inline int64_t ma_pmd_chunks(int64_t T) { return (T + MAQ_WG_COLS - 1) / MAQ_WG_COLS; }
 MIA_HD inline int64_t ma_pmd_record_wgs(int64_t n) { return (n + MAQ_THREADS - 1) / MAQ_THREADS; }
 
-__global__ __launch_bounds__(MAQ_THREADS) void k_ma_score_cols(MaProfView v, const int32_t* __restrict__ w, unsigned long long* score) {
+__global__ __launch_bounds__(MAQ_THREADS) void k_ma_score_cols(MaFlatView v, const int32_t* __restrict__ w, unsigned long long* score) {
   __shared__ int32_t s_w[MA_PMD_WEIGHTS];
   for (int b = threadIdx.x; b < MA_PMD_WEIGHTS; b += MAQ_THREADS) s_w[b] = w[b];
   __syncthreads();
@@ -45,19 +44,7 @@ __global__ __launch_bounds__(MAQ_THREADS) void k_ma_score_cols(MaProfView v, con
 
 __global__ __launch_bounds__(MAQ_THREADS) void k_ma_score_molecules(MaPmdMolView v, unsigned long long* out) {
   __shared__ uint32_t s_bins[MAQ_WAVES][MA_PMD_BINS];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  uint32_t* const mine = s_bins[wave];
-  for (int b = tid; b < MAQ_WAVES * MA_PMD_BINS; b += MAQ_THREADS) (&s_bins[0][0])[b] = 0;
-  __syncthreads();
-  for (int64_t r = (int64_t)blockIdx.x * MAQ_THREADS + tid; r < v.n; r += (int64_t)gridDim.x * MAQ_THREADS)
-    ma_pmd_record(v, r, [&](int bin) { atomicAdd(&mine[bin], 1u); });
-  __syncthreads();
-  for (int b = tid; b < MA_PMD_BINS; b += MAQ_THREADS) {
-    unsigned long long sum = 0;
-#pragma unroll
-    for (int k = 0; k < MAQ_WAVES; k++) sum += s_bins[k][b];
-    if (sum) atomicAdd(&out[b], sum);
-  }
+  ma_wave_bins_records(s_bins, v.n, out, [&](int64_t r, auto&& count) { ma_pmd_record(v, r, count); });
 }
 
 }  // namespace mia

@@ -1,25 +1,25 @@
 // mia_ma_profile_kernels.h -- the substitution profile (ma_hip -f 9, -f 91) over the records mia_hip_ma_tally left on the device.
 // One launch, k_ma_profile, over the FLAT columns: the records' SEQ and SMP strings lie end to end (col_off), flat position x is
-// one column event.  A lane takes MA_PROF_LANE = 16 positions at a time -- one 16-byte load from each string -- finds the record
-// of the first by bisecting col_off and walks on from there (ma_prof_stretch, ma_profile_body.h); a wavefront takes 1 024
-// consecutive positions, a workgroup 4 096, the grid strides over the workgroup chunks.
+// one column event.  A lane takes a stretch of MA_PROF_LANE = 16 positions at a time (the shared walk: ma_flat_body.h, with the
+// profile's rule ma_prof_stretch, ma_profile_body.h); a wavefront takes 1 024 consecutive positions, a workgroup 4 096, the grid
+// strides over the workgroup chunks.
 //
 // HISTOGRAM.  808 bins (count[31][5][5] | del[31] | bad_code | beyond), filled very unevenly: in a real assembly most events are
 // (MIDDLE, X, X).  Those four bins never touch memory in the loop: per position a ballot per bin and a population count into a
 // wave-uniform register (MA_PROF_HOT counters per wavefront).  Every other event is one LDS atomic on the wavefront's own copy of
-// the bins (4 copies of 808 words, 12.6 KiB per workgroup), so wavefronts never contend with each other and a wavefront's lanes
-// only where they hit the same rare bin at the same step.
+// the bins (ma_wave_bins.h: 4 copies of 808 words, 12.6 KiB per workgroup), so a wavefront's lanes contend only where they hit the
+// same rare bin at the same step.
 // WIDTH.  The LDS words and the hot counters are 32-bit.  A wavefront adds at most 1 024 events per chunk and a workgroup flushes
 // after at most MAP_FLUSH_CHUNKS = 2^20 chunks: no word exceeds 2^30 between flushes.  (With a grid of g workgroups that is
 // reached from T = g * 2^32 flat positions on.)
-// FLUSH.  The four copies are summed per bin and added to the int64 result with one 64-bit vector atomic per bin that is not
-// zero per workgroup -- integer adds: the result does not depend on the grid or on the order of the records.
+// FLUSH.  ma_wave_bins_flush, followed by a barrier where the copies are zeroed again for the next MAP_FLUSH_CHUNKS chunks.
 // No scratch (the 16 positions are four unrolled words of four characters each, all in registers), no launch but this one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ma_profile_body.h"
+#include "ma_wave_bins.h"
 
 namespace mia {
 
@@ -30,15 +30,14 @@ constexpr int MAP_WGS_PER_CU = 4;          // persistent grid: at most this many
 
 MIA_HD inline int64_t ma_prof_chunks(int64_t T) { return (T + MAP_WG_COLS - 1) / MAP_WG_COLS; }
 
-__global__ __launch_bounds__(MAP_THREADS) void k_ma_profile(MaProfView v, unsigned long long* out) {
+__global__ __launch_bounds__(MAP_THREADS) void k_ma_profile(MaFlatView v, unsigned long long* out) {
   __shared__ uint32_t s_bins[MAP_WAVES][MA_PROF_BINS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  uint32_t* const mine = s_bins[wave];
+  uint32_t* const mine = ma_wave_bins_mine(s_bins);
   const int64_t n_chunks = ma_prof_chunks(v.T);
   int64_t c = blockIdx.x;
   while (c < n_chunks) {                                    // (c is the same in every thread of the workgroup)
-    for (int b = tid; b < MAP_WAVES * MA_PROF_BINS; b += MAP_THREADS) (&s_bins[0][0])[b] = 0;
-    __syncthreads();
+    ma_wave_bins_zero(s_bins);
     uint32_t hot0 = 0, hot1 = 0, hot2 = 0, hot3 = 0;
     for (int64_t k = 0; k < MAP_FLUSH_CHUNKS && c < n_chunks; k++, c += gridDim.x) {
       const int64_t base = c * MAP_WG_COLS + (int64_t)tid * MA_PROF_LANE;
@@ -58,13 +57,7 @@ __global__ __launch_bounds__(MAP_THREADS) void k_ma_profile(MaProfView v, unsign
       atomicAdd(&mine[ma_prof_hot_bin(2)], hot2);
       atomicAdd(&mine[ma_prof_hot_bin(3)], hot3);
     }
-    __syncthreads();
-    for (int b = tid; b < MA_PROF_BINS; b += MAP_THREADS) {
-      unsigned long long sum = 0;
-#pragma unroll
-      for (int w = 0; w < MAP_WAVES; w++) sum += s_bins[w][b];
-      if (sum) atomicAdd(&out[b], sum);
-    }
+    ma_wave_bins_flush(s_bins, out);
     __syncthreads();
   }
 }
